@@ -23,6 +23,14 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   -> ONE JSON 
             that are NOT registered (BASELINE configs[1] read literally), the Vesta commit (the curve every
             reference proof uses), the host-pointer h2_commit including the PCIe copy of the scalars, and
             configs[3]: create_proof of examples/simple_example at k = 20.
+  --full    a plain run only sets up, warms up, times the K steps and prints the line (the headline and the
+            roofline figures of the timed region).  Every other leg -- `kernel_ms_isolated`, clock, generic, skewed
+            columns, checks, config5, NTT, cpu_baseline, extra, the N > 1 exchange legs -- runs only with --full;
+            without it those fields are null or empty.
+  --dump-outputs DIR  writes DIR/commitment_affine_xy.npy after the timed steps: the commitment of the last timed
+            step (rank 0) as a canonical affine point, float64 of shape (2, 16) = x and y as sixteen 16-bit limbs,
+            least significant first (exact in float64; the identity is all zeros).  The Jacobian triple the C ABI
+            returns is not unique (it depends on the order of a bucket's additions), the affine point is.
 The oracle is used here only as the timed CPU baseline and to generate inputs -- never in the GPU path.
 """
 from __future__ import annotations
@@ -74,6 +82,14 @@ def _newest_pmc():
         return None, None
 
 
+def _dump_outputs(out_dir, curve, xyz, co):
+    """--dump-outputs: the commitment of the last timed step as canonical affine (x, y), each a row of sixteen 16-bit limbs in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    xy = co.jac_to_affine_ints(curve, xyz) or (0, 0)          # None = the identity
+    limbs = np.array([[(v >> (16 * i)) & 0xFFFF for i in range(16)] for v in xy], dtype=np.float64)
+    np.save(os.path.join(out_dir, "commitment_affine_xy.npy"), limbs)
+
+
 class _ClockSampler:
     """Samples the shader clock and the socket power from sysfs every ~2 ms on a thread while a load runs."""
 
@@ -120,7 +136,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-create-proof", action="store_true", help="skip the configs[3] leg (create_proof simple-example k = 20)")
     ap.add_argument("--minimal", action="store_true",
-                    help="only the timed commits and the NTT leg (the workload of the PMC passes: no generic / skewed / Vesta / host-pointer legs)")
+                    help="with --full: only the timed commits and the NTT leg (the workload of the PMC passes: no generic / skewed / Vesta / host-pointer legs)")
     ap.add_argument("--config5", action="store_true", help="run the configs[4] leg (64 column commits + the split commit) at N = 1 too")
     ap.add_argument("--columns", type=int, default=4, help="distinct scalar columns resident in HBM")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("H2_BENCH_STREAMS", "3")),
@@ -133,7 +149,15 @@ def main():
                          "take a few hundred ms of sustained load to settle (the first ~20 launches of a cold run are 10-15 %% slower)")
     ap.add_argument("--lane-fraction", type=float, default=None,
                     help="share of the wave slots one accumulate launch claims (default 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (isolated kernel, clock, generic, skewed, checks, config5, NTT, CPU baseline, "
+                         "extra); --no-cpu-baseline / --no-create-proof / --minimal / --config5 select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's commitment to DIR/commitment_affine_xy.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    minimal = args.minimal or not args.full          # a plain run drops what --minimal drops, and the legs gated on args.full below
 
     import torch
     import torch.distributed as dist
@@ -280,13 +304,15 @@ def main():
         prof[name] = (ms.value, cnt.value)
         busy[name] = bz.value
     lib.h2_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, curve, d_out[args.steps - 1].cpu().numpy().view(np.uint64), co)      # row i = timed step i
     first = d_out[0].cpu().numpy().view(np.uint64).copy()   # output of timed step 0 = commit(cols[0], blinds[0]); d_out is reused below
     sc_full = np.ascontiguousarray(np.concatenate([cols[0], blinds_host[0:1]]))          # what Params::commit hands best_multiexp:
     bases_full = np.ascontiguousarray(np.concatenate([bases, w_host.reshape(1, 8)]))     # poly ++ [r], g ++ [w] (commitment.rs:120-129)
 
     # ---- the same kernel alone on the chip (one stream, full lane fraction): what the multi-stream figure dilutes ----
     iso = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         check(lib.h2_set_option(b"msm_lane_fraction", 1.0), "h2_set_option")
         t_w = time.perf_counter()                  # the host work above let the clocks drop: warm up by time, untimed
         while time.perf_counter() - t_w < 0.1:
@@ -311,8 +337,8 @@ def main():
     # ---- shader clock and socket power under the two loads above (amdgpu hwmon, sampled from a thread): the sustained rate is the
     # accumulate's issue bound AT THE CLOCK THE POWER LIMIT LEAVES, so the line carries that clock ----
     clock = None
-    hw = _hwmon_dir(local_rank) if not args.minimal and (rank == 0 or world > 1) else None
-    if world > 1 and not args.minimal:
+    hw = _hwmon_dir(local_rank) if not minimal and (rank == 0 or world > 1) else None
+    if world > 1 and not minimal:
         # N > 1: EVERY rank samples its own GPU for 0.3 s under the timed region's schedule, all at once (the sockets of one node draw on
         # one power envelope and one cooling loop), and rank 0 lists the medians
         own = [0.0, 0.0]
@@ -370,7 +396,7 @@ def main():
     # ---- the same multiexp WITHOUT registered bases (`best_multiexp(coeffs, bases)` as the reference calls it, bases read
     # from HBM each time, endomorphism split instead of the precomputed table): reported beside the headline ----
     generic = None
-    if rank == 0 and not args.minimal:
+    if rank == 0 and not minimal:
         d_bases = torch.from_numpy(bases_full.view(np.int64)).to(dev)
         d_sc = torch.from_numpy(sc_full.view(np.int64)).to(dev)
         d_gen = torch.zeros(12, dtype=torch.int64, device=dev)
@@ -448,7 +474,7 @@ def main():
 
     # ---- skewed columns: 90 % zeros, and every scalar < 2^16 -- same kernels, same partition ----
     skew = {}
-    if rank == 0 and not args.minimal:
+    if rank == 0 and not minimal:
         z = cols[0].copy()
         z[np.arange(n) % 10 != 0] = 0
         small = fields.to_limbs([((i * 2654435761) & 0xFFFF) for i in range(1 << 12)], sf)
@@ -471,14 +497,14 @@ def main():
             del d_c
 
     # ---- parity spot check of the timed outputs (rank 0: first column vs the split-and-sum identity) ----
-    parts = [] if args.minimal else [h.best_multiexp(cols[0][i * n // 4:(i + 1) * n // 4], bases[i * n // 4:(i + 1) * n // 4], curve) for i in range(4)]
-    if not args.minimal:
+    parts = [] if minimal else [h.best_multiexp(cols[0][i * n // 4:(i + 1) * n // 4], bases[i * n // 4:(i + 1) * n // 4], curve) for i in range(4)]
+    if not minimal:
         parts.append(h.best_multiexp(blinds_host[0:1], w_host.reshape(1, 8), curve))          # + r * w
-    split_ok = None if args.minimal else co.jac_to_affine_ints(curve, h.points_sum(np.stack(parts), curve)) == co.jac_to_affine_ints(curve, first)
+    split_ok = None if minimal else co.jac_to_affine_ints(curve, h.points_sum(np.stack(parts), curve)) == co.jac_to_affine_ints(curve, first)
 
     # ---- multi-GPU exchange step: one range-split MSM, partials all-gathered over RCCL, summed locally ----
     split_msm_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         shared = co.random_field(sf, 4242, n)           # same column on every rank
         total = parallel.split_msm(shared, bases, curve, rank, world, device=comm_dev)
         whole = h.best_multiexp(shared, bases, curve) if rank == 0 else None
@@ -491,7 +517,7 @@ def main():
     # partials exchanged by a single all-gather and summed locally.  Runs for N > 1 (and at N = 1 with --config5, where the
     # "exchange" is a gather of one).  Every figure is the max over ranks of a barrier-bracketed region.
     config5 = None
-    if (world > 1 or args.config5) and not args.minimal:
+    if (world > 1 or args.config5) and not minimal:
         def _maxr(x):
             if world == 1:
                 return float(x)
@@ -567,7 +593,7 @@ def main():
 
     # ---- NTT leg (reported beside the headline value; Fp, k = 20 and 2^22 round trip) ----
     ntt = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import pasta
         for log_n in (20, 22):
             a = co.random_field(h.FP, 7 + log_n, 1 << log_n)
@@ -670,7 +696,7 @@ def main():
 
     # ---- CPU baseline: C restatement of the reference algorithm on this box's host cores ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = co.lib().orc_get_threads()
         co.best_multiexp(curve, sc_full, bases_full)                      # warm-up run (page faults, thread pool)
         runs = []
@@ -690,7 +716,7 @@ def main():
 
     # ---- first-class companions of the headline (the bench line must carry them) ----
     extra = {}
-    if rank == 0 and not args.minimal:
+    if rank == 0 and not minimal:
         # (1) the Vesta commit: the curve every reference proof commits on (benches/plonk.rs:6); same kernels, other moduli
         vs = co.field_of_curve(h.VESTA, "scalar")
         v_bases = co.generate_bases(h.VESTA, 0x56455354, n)

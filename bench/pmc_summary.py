@@ -5,9 +5,9 @@ Optional third / fourth argument (round 4): the same two counters over bench/ube
 of bytes in the NTT's access patterns -- the calibration behind the read correction (see `calibration` in the output).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_f -o f --output-format csv -- python bench.py --steps 3 --warmup 1 --prewarm-ms 0 --minimal --no-cpu-baseline --streams 1
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_w -o w --output-format csv -- python bench.py --steps 3 --warmup 1 --prewarm-ms 0 --minimal --no-cpu-baseline --streams 1
-    python bench/pmc_summary.py gpurun_out/pmc_f/f_counter_collection.csv gpurun_out/pmc_w/w_counter_collection.csv > profiles/r03_pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE -d OUT/pmc_f -o f --output-format csv -- python bench.py --full --steps 3 --warmup 1 --prewarm-ms 0 --minimal --no-cpu-baseline --streams 1
+    rocprofv3 --pmc WRITE_SIZE -d OUT/pmc_w -o w --output-format csv -- python bench.py --full --steps 3 --warmup 1 --prewarm-ms 0 --minimal --no-cpu-baseline --streams 1
+    python bench/pmc_summary.py OUT/pmc_f/f_counter_collection.csv OUT/pmc_w/w_counter_collection.csv > profiles/r03_pmc_traffic.json
 
 Counter values are KiB per dispatch.  MI355X_MICROARCH.md: on gfx950 FETCH_SIZE under-reports wide coalesced streaming
 reads by exactly 2x (calibrated for 16 B/lane streams); the x2 is applied to the streaming kernels named in STREAMING and
@@ -67,7 +67,7 @@ def main():
         calibration["read_correction"] = round(1.0 / (sum(rr) / len(rr)), 3) if rr else None
         calibration["conclusion"] = ("FETCH_SIZE reports half the bytes for EVERY read pattern measured (streaming, 128-byte rows, 64-byte and 16-byte "
                                      "gathered runs): the x2 applies to the twiddle gathers as well; WRITE_SIZE is exact")
-    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 3 --warmup 1 "
+    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 3 --warmup 1 "
                      "--prewarm-ms 0 --minimal --no-cpu-baseline --streams 1, one MI355X; summarised by bench/pmc_summary.py",
            "calibration": calibration,
            "units": __doc__.split("Counter values")[1].strip().replace("\n", " "),

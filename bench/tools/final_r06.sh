@@ -16,7 +16,7 @@ timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 el "pytest -m gpu rc=$? ($(grep -E 'passed|failed' $O/pytest.log | tail -1))"
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 el "smoke rc=$? ($(tail -1 $O/smoke.log))"
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 el "bench rc=$?"
 timeout 120 build/h2bench commit 20 20,100 5 3 0 3 > $O/h2bench_commit.txt 2>&1
 timeout 120 build/h2bench ntt 16,18,20,21,22,24 0 1 > $O/h2bench_ntt.txt 2>&1
@@ -33,13 +33,13 @@ import socket
 s = socket.socket(); s.bind(("127.0.0.1", 0)); print(s.getsockname()[1])
 PY
 )
-H2_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus 8 --steps 5 --warmup 1 --no-cpu-baseline --no-create-proof --prewarm-ms 50 > $O/bench_8rank_rehearsal.out 2> $O/bench_8rank_rehearsal.err
+H2_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus 8 --steps 5 --warmup 1 --no-cpu-baseline --no-create-proof --prewarm-ms 50 > $O/bench_8rank_rehearsal.out 2> $O/bench_8rank_rehearsal.err
 el "8-rank rehearsal rc=$?"
 grep '^{' $O/bench_8rank_rehearsal.out | tail -1 > $O/bench_8rank_rehearsal.json
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-create-proof > $O/stats_bench.json 2>/dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-create-proof > $O/stats_bench.json 2>/dev/null
 el "rocprofv3 3 streams rc=$?"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -o bench1 -- python $R/bench.py --streams 1 --steps 40 --no-cpu-baseline --no-create-proof > $O/stats1_bench.json 2>/dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -o bench1 -- python $R/bench.py --full --streams 1 --steps 40 --no-cpu-baseline --no-create-proof > $O/stats1_bench.json 2>/dev/null
 el "rocprofv3 1 stream rc=$?"
 cd $R
 for d in stats stats1; do

@@ -40,7 +40,7 @@ for arm in shipped fermat; do
   echo "== $arm"
   [ $arm = fermat ] && cp build/ab/lib_fermat.so halo2_amd/libhalo2_mi355x.so
   timeout 200 python /tmp/inv_time.py 2>&1 | tail -5
-  timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --prewarm-ms 50 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --prewarm-ms 50 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 e=d['extra']['create_proof_simple_example_k20']

@@ -1,6 +1,6 @@
 """bench.py's driver contract, on a real GPU: one JSON line with the required keys (incl. `roofline` and
-`cpu_baseline`), and the N > 1 path (torch.distributed.run, one rank per GPU) exercised with two ranks over gloo
-on whatever GPUs the box has."""
+`cpu_baseline`, which --full fills in), and the N > 1 path (torch.distributed.run, one rank per GPU) exercised with two ranks over gloo
+on whatever GPUs the box has; a plain run (no --full) times its steps alone and --dump-outputs writes what they computed."""
 import json
 import os
 import socket
@@ -30,7 +30,7 @@ def _last_json(out: str):
 
 
 def test_bench_single_gpu_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
@@ -61,7 +61,7 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, H2_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                          "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert d["n_gpus"] == 2 and d["checks"]["split_msm_allgather"] is True and d["checks"]["split_sum_identity"] is True
@@ -80,7 +80,7 @@ def test_bench_eight_ranks_gloo_rehearsal():
     env = dict(os.environ, H2_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "5",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-create-proof", "--prewarm-ms", "50"],
+                          "--warmup", "1", "--no-cpu-baseline", "--no-create-proof", "--prewarm-ms", "50", "--full"],
                          capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert out.stdout.strip().splitlines()[-1].startswith("{")            # the line is the LAST thing on stdout
@@ -106,10 +106,40 @@ def test_bench_batched_steps():
     """--batch K: K consecutive steps go to h2_commit_batch_device as one column-batched call; a step is still one full commit, the line
     says so (`config.columns_per_call`, `roofline.columns_per_launch`) and the first output still equals the split-and-sum identity."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "3",
-                          "--no-cpu-baseline", "--no-create-proof", "--prewarm-ms", "20"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--no-cpu-baseline", "--no-create-proof", "--prewarm-ms", "20", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert d["config"]["columns_per_call"] == 3 and d["steps"] == 6
     assert abs(d["roofline"]["columns_per_launch"] - 3.0) < 1e-6 and d["roofline"]["launches"] == 2
     assert abs(d["ms_per_step"] * 1e-3 * d["value"] * 1e6 - (1 << 20)) / (1 << 20) < 0.02
     assert d["checks"]["split_sum_identity"] is True
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps commits, prints the headline fields and none of the --full legs; --dump-outputs writes the
+    last timed step's commitment as canonical affine limbs in float64, and that point is Params::commit of the step's column and blind by the
+    oracle's best_multiexp on the inputs bench.py seeds."""
+    import numpy as np
+
+    from halo2_amd import PALLAS
+    from oracle import c_oracle as co
+
+    steps = 7
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = _last_json(out.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["roofline"]["launches"] == steps and d["roofline"]["columns_per_launch"] == 1.0      # one commit per step
+    assert abs(d["ms_per_step"] * 1e-3 * d["value"] * 1e6 - (1 << 20)) / (1 << 20) < 0.02
+    assert d["cpu_baseline"] is None and d["ntt"] == {} and d["generic_best_multiexp"] is None and d["extra"] == {}
+    assert d["checks"]["split_sum_identity"] is None and d["kernel_ms_isolated"] == {}
+    xy = np.load(tmp_path / "commitment_affine_xy.npy")
+    assert xy.dtype == np.float64 and xy.shape == (2, 16) and np.all((xy >= 0) & (xy < 1 << 16) & (xy == np.floor(xy)))
+    got = tuple(sum(int(v) << (16 * i) for i, v in enumerate(row)) for row in xy)
+    curve, n, c = PALLAS, 1 << 20, (steps - 1) % 4          # step i commits column i % --columns (default 4) with its blind
+    sf = co.field_of_curve(curve, "scalar")
+    scalars = np.concatenate([co.random_field(sf, 1000 + c, n), co.random_field(sf, 0xB11D, 4)[c:c + 1]])
+    bases = np.concatenate([co.generate_bases(curve, 0x48414C4F32, n), co.generate_bases(curve, 0x77, 1)])
+    assert got == co.jac_to_affine_ints(curve, co.best_multiexp(curve, np.ascontiguousarray(scalars), np.ascontiguousarray(bases)))
