@@ -21,12 +21,19 @@
 //     CALLER's queue would run behind the accumulate it was meant to run beside; the caller's stream only waits for the result.  8 CUs are left
 //     without an accumulate workgroup and the chain links are fenced onto them by LDS requests (a chain link is one wave holding a SIMD).
 //     Throughput form (another stream's generic multiexp is in flight, below 2^22 points): ONE group, everything on the caller's stream.
+//   * SIZE LIMITS: group_geometry decides them (a pass-1 bin must hold ~16 K entries at most, and at most 4096 bins per group).  The latency
+//     form takes 2^18 + 1 .. 5 120 255 scalars, the throughput form's single group up to 2 560 127.  Beyond that this returns
+//     H2_ERR_BATCH_SHAPE and msm_launch runs round 5's slice split: a lone call from 5 120 256 scalars, a call that finds another in flight
+//     from 2 560 128 to 2^22 - 1.  (h2_profile_enable and H2_TIMELINE=1 never come here: msm_launch keeps their calls on the plain two-pass
+//     sort.)  h2_msm_last_path reports the form a call took.
 //
 // Measured against round 5's form on one box (profiles/r06_generic_grouped.txt): 2^20 one call 1.50-1.58 against 1.55-1.62 ms, three streams
 // 1.16-1.20 against 1.33-1.43; 2^21 2.59-2.62 against 2.84-2.87; 2^22 4.98-5.13 against 5.68-5.74 ms.  DESIGN.md section 4.4 has the reasons.
 //
 // Results are the same group element as every other form (the order of additions inside a bucket is free: SURVEY.md appendix A.1);
 // parity (bit-exact canonical affine coordinates against the C restatement of the reference): tests/test_gpu_generic_grouped.py, tests/test_gpu_parity.py, build/h2bench msm / parity.
+#include <cassert>
+
 #include "msm_internal.cuh"
 
 namespace h2 {
@@ -102,7 +109,8 @@ template <int FB, int FS>
 int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, hipStream_t st) {
     static const bool on = [] { const char *e = ab_env("H2_GENERIC_GROUPED"); return !(e && atoi(e) == 0); }();       // 0: round 5's slice split (A/B)
     static const size_t min_n = [] { const char *e = ab_env("H2_GENERIC_GROUPED_MIN"); return e ? (size_t)atol(e) : ((size_t)1 << 18) + 1; }();
-    if (!on || scalars_n < min_n || scalars_n > ((size_t)1 << 24) || sh.c < 8 || sh.c > kMaxC || sh.W < 3 || sh.W > 16 || sh.NB < 128) return H2_ERR_BATCH_SHAPE;
+    // (no upper bound on scalars_n here: group_geometry below declines every size beyond the layouts' limits, see the header)
+    if (!on || scalars_n < min_n || sh.c < 8 || sh.c > kMaxC || sh.W < 3 || sh.W > 16 || sh.NB < 128) return H2_ERR_BATCH_SHAPE;
     const u32 m = (u32)scalars_n, cols = 2 * m, W = (u32)sh.W, NB = sh.NB, c = (u32)sh.c;
     int rc;
     static const bool fold_late = [] { const char *e = ab_env("H2_GG_FOLD_LATE"); return e && atoi(e) == 1; }();       // experiments (laboratory build)
@@ -176,7 +184,9 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     static const int lds_env = [] { const char *e = ab_env("H2_GG_LDS"); return e ? atoi(e) : -1; }();
     const bool lds_fence = lds_env >= 0 ? lds_env == 1 : (!throughput && G > 1);
     const u32 spare = spare_env >= 0 ? (u32)spare_env : (lds_fence ? std::max(1u, lanes / 512u / 32u) : 0u);      // one CU in 32: 8 of an MI355X's 256 (one per XCD)
-    const u32 usable = std::max(512u, (u32)(lanes * fraction) / 512u * 512u - 512u * std::min(spare, 64u));
+    // (signed: a small fraction -- or few CUs -- must not wrap below the spare CUs' share and hand the accumulate every lane there is)
+    const long long want_lanes = (long long)((u32)(lanes * fraction) / 512u * 512u) - 512LL * std::min(spare, 64u);
+    const u32 usable = (u32)std::max<long long>(512, want_lanes);
     size_t head_slots = 0, hist_words = 0, tagged_words = 0, plan_words = 0;
     for (int g = 0; g < G; ++g) {
         grp[g].T = (u32)std::min<size_t>(usable, std::max<size_t>(512, (grp[g].emax / lane_div + 511) / 512 * 512));
@@ -185,6 +195,11 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
         tagged_words = std::max(tagged_words, grp[g].emax);
         plan_words = std::max(plan_words, grp[g].plan_words);
     }
+    cx.last.path = throughput ? H2_MSM_PATH_GROUPED_THROUGHPUT : H2_MSM_PATH_GROUPED_LATENCY;       // h2_msm_last_path
+    cx.last.groups = G;
+    cx.last.acc_lanes = 0;
+    for (int g = 0; g < G; ++g) cx.last.acc_lanes = std::max(cx.last.acc_lanes, grp[g].T);
+    cx.last.c = (int)c;
     const int bb = (int)c - 1;
     const u32 wideS = 1u << (bb / 2), wideNR = NB / wideS;
     int cb = 0;
@@ -207,10 +222,11 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
         if ((rc = cx.fold_ctr.reserve((size_t)kMaxCols * 64)) != H2_OK) return rc;
         H2_HIP(hipMemsetAsync(cx.fold_ctr.ptr, 0, (size_t)kMaxCols * 64, st));
     }
-    if (!cx.attr_grouped_set) {
+    if (!cx.attr_grouped_set) {       // (one flag per context: both curves' chain links, whichever curve comes first)
         H2_HIP(hipFuncSetAttribute((const void *)msm_d1_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
         H2_HIP(hipFuncSetAttribute((const void *)msm_s2_bins, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-        H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FB>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         cx.attr_grouped_set = true;
     }
     // Hardware queues.  HIP multiplexes streams onto a handful of hardware queues (four per priority level), and every packet of a queue waits
@@ -226,10 +242,13 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     if (G > 1 && !cx.gstream[0])
         for (int i = 0; i < 3; ++i) H2_HIP(hipStreamCreateWithFlags(&cx.gstream[i], hipStreamNonBlocking));
     hipStream_t const caller = st;
-    if (G > 1) st = cx.gstream[1];
+    if (G > 1) {
+        assert(cx.gstream[0] && cx.gstream[1] && cx.gstream[2]);
+        st = cx.gstream[1];
+    }
     for (int i = 0; i < 4 + 3 * G; ++i)
         if (!cx.gev[i]) H2_HIP(hipEventCreateWithFlags(&cx.gev[i], hipEventDisableTiming));
-    hipStream_t sort_s = cx.gstream[0];
+    hipStream_t const sort_s = G > 1 ? cx.gstream[0] : nullptr;      // (one group: no side stream -- a context that never ran the latency form has none)
     hipEvent_t ev_fork = cx.gev[0], ev_conv = cx.gev[1];
     auto ev_sorted = [&](int g) { return cx.gev[2 + 3 * g]; };
     auto ev_acc = [&](int g) { return cx.gev[3 + 3 * g]; };
@@ -311,8 +330,10 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
 
     // ---- sorts: the first group on the caller's stream, the others on the side stream behind it (they share hist / tagged / plan)
     sort_group(0, st);
-    H2_HIP(hipEventRecord(ev_sorted(0), st));
-    H2_HIP(hipStreamWaitEvent(sort_s, ev_sorted(0), 0));
+    if (G > 1) {
+        H2_HIP(hipEventRecord(ev_sorted(0), st));
+        H2_HIP(hipStreamWaitEvent(sort_s, ev_sorted(0), 0));
+    }
     for (int g = 1; g < G; ++g) {
         sort_group(g, sort_s);
         H2_HIP(hipEventRecord(ev_sorted(g), sort_s));

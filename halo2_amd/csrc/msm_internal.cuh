@@ -292,6 +292,13 @@ struct MsmContext {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_conv = nullptr, ev_acc_a = nullptr, ev_join = nullptr;
     u32 lanes[2][3] = {{0, 0, 0}, {0, 0, 0}};  // resident lanes of msm_accumulate<FP / FQ, plain / GLV> on this device
+    // h2_msm_last_path: the form the last generic multiexp of this context took (host bookkeeping, written where the form is decided)
+    struct LastPath {
+        int path = 0;          // H2_MSM_PATH_*; 0: no generic multiexp yet
+        int groups = 0;
+        u32 acc_lanes = 0;     // the largest T of its accumulate launches
+        int c = 0;
+    } last;
 };
 
 MsmContext &msm_ctx(hipStream_t st = nullptr);          // msm_launch.hip

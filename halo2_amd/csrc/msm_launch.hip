@@ -256,6 +256,14 @@ bool msm_other_generic_in_flight(const MsmContext *self) {
     }
     return false;
 }
+// h2_msm_last_path: the context of (current device, st) if one exists -- the query must not create one
+static MsmContext *msm_ctx_find(hipStream_t st) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(g_ctx_mu);
+    auto it = g_ctxs.find(std::make_pair(dev, st));
+    return it == g_ctxs.end() ? nullptr : it->second.get();
+}
 // h2_trim: the per-(device, stream) scratch of this device goes back to the allocator (the device is idle by then)
 void msm_release_workspaces() {
     msm_release_host_pipe();
@@ -454,6 +462,12 @@ template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a
         else if (scalars_n >= ((size_t)1 << 19)) split_k = 3;
     }
     if (split_k) head_slots = 2 * (size_t)T;               // each group's T range heads
+    if (!a.table && a.phase == 0 && !fold_only && !a.add_into && !a.slice_sums_only) {      // a whole generic multiexp (h2_msm_last_path)
+        cx.last.path = split_k ? H2_MSM_PATH_SLICE_SPLIT : use_sort2 ? H2_MSM_PATH_TWO_PASS : H2_MSM_PATH_ONE_PASS;
+        cx.last.groups = split_k ? 2 : 1;
+        cx.last.acc_lanes = T;
+        cx.last.c = sh.c;
+    }
     // pass 2 of the two-pass sort in its one-launch form (a workgroup per pass-1 bin)?  Decided here, before anything is launched,
     // because a column-batched commit exists in that form only.
     bool s2_bins_form = false;
@@ -1168,13 +1182,39 @@ extern "C" int h2_msm_batch_device(int curve, const void *const *d_scalars, cons
     hipStream_t user = (hipStream_t)stream;
     H2_HIP(hipEventRecord(bs.fork, user));
     for (size_t i = 0; i < want; ++i) H2_HIP(hipStreamWaitEvent(bs.s[i], bs.fork, 0));
-    for (size_t i = 0; i < count && rc == H2_OK; ++i)
+    size_t ran = 0;
+    for (size_t i = 0; i < count && rc == H2_OK; ++i, ++ran)
         rc = h2_msm_device(curve, d_scalars[i], d_bases_xy[i], n[i], form, out_kind, d_outs[i], bs.s[i % want]);
     for (size_t i = 0; i < want; ++i) {
         H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
         H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
     }
+    if (rc == H2_OK && ran) {         // h2_msm_last_path on the caller's stream: the form of the last multiexp of the batch
+        MsmContext::LastPath lp;
+        {
+            MsmContext &last = msm_ctx(bs.s[(ran - 1) % want]);
+            std::lock_guard<std::mutex> cl(last.mu);
+            lp = last.last;
+        }
+        if (lp.path) {
+            MsmContext &cx = msm_ctx(user);
+            std::lock_guard<std::mutex> cl(cx.mu);
+            cx.last = lp;
+        }
+    }
     return rc;
+}
+
+extern "C" int h2_msm_last_path(void *stream, int *path, int *groups, unsigned *acc_lanes, int *window_bits) {
+    MsmContext *cx = msm_ctx_find((hipStream_t)stream);
+    if (!cx) return H2_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    if (!cx->last.path) return H2_ERR_ARGS;
+    if (path) *path = cx->last.path;
+    if (groups) *groups = cx->last.groups;
+    if (acc_lanes) *acc_lanes = cx->last.acc_lanes;
+    if (window_bits) *window_bits = cx->last.c;
+    return H2_OK;
 }
 
 extern "C" int h2_points_sum_device(int curve, const void *d_points_xyz, size_t count, int form, int out_kind, void *d_out, void *stream) {

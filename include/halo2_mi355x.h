@@ -479,8 +479,32 @@ int h2_profile_read(int slot, double *total_ms, uint64_t *launches);
  * issued on several streams overlapping on the device, total_ms counts shared time once per launch; busy_ms is the time
  * the device spent on the kernel, so busy_ms / launches never exceeds the wall time per launch. */
 int h2_profile_read_busy(int slot, double *total_ms, double *busy_ms, uint64_t *launches);
-/* ENVIRONMENT.  libhalo2_mi355x.so reads ONE environment variable, the diagnostic H2_TIMELINE below; it never changes a result or an
- * algorithm.  Every A/B switch and sweep knob of the experiments behind DESIGN_LOG.md is compiled out of this library (csrc/common.h,
+/* Profiling (h2_profile_enable(1) or (2)) and the timeline (H2_TIMELINE=1) never change a result, but they DO change the algorithm of a
+ * generic multiexp (h2_msm_device without a registered basis): from 65536 scalars on every such call takes the plain two-pass sort
+ * (H2_MSM_PATH_TWO_PASS below; the endomorphism split inside the sort), never the grouped form or the slice split, so that the
+ * bracketed stages are the ones a single stream runs. */
+
+/* The form the last generic multiexp (h2_msm_device / h2_msm_batch_device without a registered basis) enqueued on `stream` of the
+ * current device took.  Host-side bookkeeping of the call that enqueued it: no device work, no synchronisation.  The calls of
+ * h2_msm_batch_device run on the library's streams; the last of them is also recorded for the caller's `stream`.
+ *   path         H2_MSM_PATH_*:
+ *                ONE_PASS           one-pass counting sort (below 65536 scalars)
+ *                TWO_PASS           two-pass sort, one accumulate (65536 .. 2^18 scalars; every size from 65536 under profiling / timeline)
+ *                SLICE_SPLIT        two-pass sort, the upper and lower window slices accumulated in turn (sizes the grouped form declines)
+ *                GROUPED_LATENCY    grouped form, a lone call: `groups` groups on the library's own streams (2^18 + 1 .. 5120255 scalars)
+ *                GROUPED_THROUGHPUT grouped form, another stream's generic multiexp in flight: one group on `stream` (up to 2560127 scalars)
+ *   groups       accumulate launches over disjoint window slices (1 for one pass / two pass, 2 for the slice split)
+ *   acc_lanes    the largest lane count (threads) of the call's bucket-accumulation launches
+ *   window_bits  the window width c
+ * Any output pointer may be NULL.  H2_ERR_ARGS when no generic multiexp has been enqueued on that stream (the query creates nothing). */
+#define H2_MSM_PATH_ONE_PASS 1
+#define H2_MSM_PATH_TWO_PASS 2
+#define H2_MSM_PATH_SLICE_SPLIT 3
+#define H2_MSM_PATH_GROUPED_LATENCY 4
+#define H2_MSM_PATH_GROUPED_THROUGHPUT 5
+int h2_msm_last_path(void *stream, int *path, int *groups, unsigned *acc_lanes, int *window_bits);
+/* ENVIRONMENT.  libhalo2_mi355x.so reads ONE environment variable, the diagnostic H2_TIMELINE below; it never changes a result (it does
+ * change the form of a large generic multiexp, see above).  Every A/B switch and sweep knob of the experiments behind DESIGN_LOG.md is compiled out of this library (csrc/common.h,
  * ab_env()) and lives only in the laboratory build of the same sources (`make -C halo2_amd/csrc ab` -> build/ab/libhalo2_mi355x_ab.so)
  * that the A/B parity tests and bench/tools load; tests/test_abi_and_host.py holds the shipped binary to that.
  *

@@ -55,6 +55,7 @@ def test_argument_validation_without_gpu():
     assert lib.h2_ntt(0, p(z4), 33, p(z4[0]), 1) == _lib.H2_ERR_ARGS                 # log_n > 32
     assert lib.h2_ntt(3, p(z4), 2, p(z4[0]), 1) == _lib.H2_ERR_ARGS                  # bad field
     assert lib.h2_bases_free(123456) == _lib.H2_ERR_HANDLE
+    assert lib.h2_msm_last_path(None, None, None, None, None) == _lib.H2_ERR_ARGS    # no generic multiexp on that stream yet
     # round-2 entries: the opening argument's policies are host logic; bad handles / curves are refused before any device work
     assert lib.h2_ipa_default_switch_rounds(20, 1) == 6 and lib.h2_ipa_default_switch_rounds(16, 1) == 2 and lib.h2_ipa_default_switch_rounds(24, 1) == 5
     assert lib.h2_ipa_default_switch_rounds(19, 1) == 5 and lib.h2_ipa_default_switch_rounds(21, 1) == 6 and lib.h2_ipa_default_switch_rounds(22, 1) == 5

@@ -15,6 +15,28 @@ from oracle import pasta as o
 pytestmark = pytest.mark.gpu
 
 
+def _path_codes():
+    import os
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "halo2_mi355x.h")).read()
+    return {k: int(v) for k, v in re.findall(r"#define H2_MSM_PATH_([A-Z_]+) (\d+)", hdr)}
+
+
+PATH = _path_codes()        # H2_MSM_PATH_* of the header: ONE_PASS, TWO_PASS, SLICE_SPLIT, GROUPED_LATENCY, GROUPED_THROUGHPUT
+
+
+def last_path(stream=None):
+    """h2_msm_last_path on `stream` (default: torch's current stream): (path, groups, acc_lanes, window_bits)."""
+    import ctypes as C
+
+    import torch
+    s = (stream or torch.cuda.current_stream()).cuda_stream
+    p, g, t, c = C.c_int(), C.c_int(), C.c_uint(), C.c_int()
+    rc = h.lib().h2_msm_last_path(C.c_void_p(s), C.byref(p), C.byref(g), C.byref(t), C.byref(c))
+    assert rc == 0, f"h2_msm_last_path: {rc}"
+    return p.value, g.value, t.value, c.value
+
+
 def affine_of(curve, jac):
     return co.jac_to_affine_ints(curve, np.ascontiguousarray(jac, dtype=np.uint64))
 
@@ -66,15 +88,20 @@ def test_grouped_generic_multiexp_both_forms_side_by_side(curve, n):
     d_b_can = _dev(co.from_mont(bf, bases.reshape(2 * n, 4)).reshape(n, 8))
     d_s_can = _dev(co.from_mont(sf, sc[2]))
     streams = [torch.cuda.Stream() for _ in range(3)]
+    torch.cuda.synchronize()
     for rep in range(3):
-        outs = []
+        outs, paths = [], []
         for i in range(6):
             with torch.cuda.stream(streams[i % 3]):
                 if i == 5:
                     outs.append((2, True, h.best_multiexp(d_s_can, d_b_can, curve, form=h.FORM_CANONICAL, affine=True)))
                 else:
                     outs.append((i % 3, False, h.best_multiexp(d_s[i % 3], d_b, curve)))
+                paths.append(last_path())                               # the form of the call just enqueued on this stream
         torch.cuda.synchronize()
+        # the first call finds nothing in flight; the ones enqueued behind it on the other streams find it (or each other) running
+        assert paths[0][:2] == (PATH["GROUPED_LATENCY"], 3), (rep, paths)
+        assert any(p[:2] == (PATH["GROUPED_THROUGHPUT"], 1) for p in paths[1:]), (rep, paths)
         for which, is_affine, out in outs:
             got = out.cpu().numpy().view(np.uint64)
             if is_affine:                                                # canonical affine coordinates out: compare as integers

@@ -645,16 +645,9 @@ def test_generic_multiexp_endomorphism_edge_scalars(curve):
     """Scalars that stress the device-side endomorphism split of the generic path (glv.cuh): 0, +-1, lambda and its
     neighbours (k2 = +-1, k1 = 0), powers of two around the 128-bit half length, the largest scalars, and every digit
     position set to +-2^(c-1) (the extreme signed digits)."""
-    sm = o.CURVES[curve][1]
+    from glv_edge_scalars import endomorphism_edge_values
     sf = fields.CURVE_FIELDS[curve][1]
-    lam = {0: 0x6819a58283e528e511db4d81cf70f5a0fed467d47c033af2aa9d2e050aa0e4f,
-           1: 0x2d33357cb532458ed3552a23a8554e5005270d29d19fc7d27b7fd22f0201b547}[curve]
-    assert (lam * lam + lam + 1) % sm == 0
-    vals = [0, 1, 2, sm - 1, sm - 2, lam, lam + 1, lam - 1, sm - lam, (sm - lam) - 1, lam * lam % sm, 1 << 127, 1 << 128,
-            (1 << 128) - 1, (1 << 128) + 1, 1 << 129, 1 << 254, (sm - 1) // 2, (sm + 1) // 2, 0x8000, 0x8001, 0x7FFF,
-            sum(0x8000 << (16 * i) for i in range(15)), sum(0x8000 << (13 * i) for i in range(19)) % sm,
-            sum(0x200 << (10 * i) for i in range(25)) % sm, (lam << 1) % sm, (lam * 0x8000) % sm]
-    vals = [v % sm for v in vals]
+    vals = endomorphism_edge_values(curve)
     for n in (len(vals), 5000):                       # c = 10 and c = 13 shapes
         reps = -(-n // len(vals))
         sc = fields.to_limbs((vals * reps)[:n], sf, True)
@@ -676,21 +669,12 @@ def test_generic_multiexp_top_window_boundaries_at_size(curve):
     else zero), so that no cancellation between terms can hide a wrong digit.  (Real halves rarely get there: the top window of a
     split Pallas scalar exceeds 2^15 for 5 % of the halves, 23 % on Vesta -- which is why cutting that window unsigned to save the
     carry slice, tried in round 5, bought nothing: DESIGN.md section 4.4.)"""
-    sm = o.CURVES[curve][1]
+    from glv_edge_scalars import top_window_boundary_values
     sf = fields.CURVE_FIELDS[curve][1]
-    lam = {0: 0x6819a58283e528e511db4d81cf70f5a0fed467d47c033af2aa9d2e050aa0e4f,
-           1: 0x2d33357cb532458ed3552a23a8554e5005270d29d19fc7d27b7fd22f0201b547}[curve]
     n = 1 << 19
     import random
     rng = random.Random(1900 + curve)
-    tops = [0, 1, 0x7FFF, 0x8000, 0x8001, 0xFFFE, 0xFFFF]
-    below = [0, 0x7FFF, 0x8000, 0x8001, 0xFFFF]
-    halves = [(t << 112) | (b << 96) | rng.getrandbits(96) for t in tops for b in below] + [(1 << 128) - 1, 1 << 127, (1 << 127) - 1]
-    crafted = []
-    for k1 in halves:
-        for k2 in (0, halves[rng.randrange(len(halves))]):
-            for s1, s2 in ((1, 1), (-1, 1), (1, -1)):
-                crafted.append((s1 * k1 + s2 * k2 * lam) % sm)
+    crafted = top_window_boundary_values(curve, rng)
     bases = co.generate_bases(curve, 1919, n)
     sc = co.random_field(sf, 1920 + curve, n)
     idx = rng.sample(range(n), len(crafted))
@@ -747,8 +731,11 @@ def test_best_multiexp_host_slices_range_pipeline(curve, canonical, affine):
 @pytest.mark.parametrize("env,args", [
     ({"H2_NTT_MAXR": "11"}, ["ntt", "5,11,13,21,22", "0", "1"]),          # 11-stage passes: 2^21 = 11 + 10, 2^22 = 11 + 11 (odd stage counts open with a radix-2 round)
     ({"H2_NTT_MAXR": "12"}, ["ntt", "12,23,24", "1", "1"]),               # 12-stage passes on Fq: 2^24 = 12 + 12, one 4096-row column per tile
-    ({"H2_GENERIC_SPLIT": "0", "H2_MSM_HOST_CHUNKS": "1"}, ["msm", "19", "0"]),      # round 4's forms: one accumulate, one piece from host slices
-    ({"H2_GENERIC_SPLIT": "5"}, ["msm", "19", "1"]),                      # another cut of the window slices
+    # (H2_GENERIC_GROUPED=0: at 2^19 the grouped form runs first and returns, so without it the split switches are never read)
+    ({"H2_GENERIC_GROUPED": "0", "H2_GENERIC_SPLIT": "0", "H2_MSM_HOST_CHUNKS": "1"}, ["msm", "19", "0"]),      # round 4's forms: one accumulate, one piece from host slices
+    ({"H2_GENERIC_GROUPED": "0", "H2_GENERIC_SPLIT": "5"}, ["msm", "19", "1"]),                      # another cut of the window slices
+    ({"H2_GG_FORM": "2"}, ["msm", "19", "1"]),                            # the grouped form's throughput form on a fresh context (no side streams)
+    ({"H2_GENERIC_GROUPS": "1,1,3,4"}, ["msm", "19", "1"]),               # four groups (kMaxGroups), one-slice links at the top of the chain
     ({"H2_MSM_HOST_CHUNKS": "5", "H2_MSM_HOST_GRAPHS": "0"}, ["msm", "19", "0"]),    # five ragged ranges, plain launches
     ({"H2_MSM_HOST_CHUNKS": "2", "H2_MSM_HOST_THREAD": "1"}, ["msm", "20", "1"]),    # two ranges, captured sequences replayed from a helper thread
 ])
