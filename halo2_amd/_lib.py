@@ -68,6 +68,8 @@ SIGNATURES = {
     "h2_fold_scalars": ([C.c_int, u64p, C.c_size_t, u64p, C.c_int], C.c_int),
     "h2_fold_scalars_device": ([C.c_int, vp, C.c_size_t, u64p, C.c_int, vp], C.c_int),
     "h2_ipa_round_scalars_device": ([C.c_int, vp, C.c_uint, C.c_uint, u64p, C.c_int, vp, vp, vp], C.c_int),
+    "h2_ipa_s_combine": ([C.c_int, C.c_uint, C.c_size_t, u64p, u64p, C.c_int, C.c_int, u64p], C.c_int),
+    "h2_ipa_s_combine_device": ([C.c_int, C.c_uint, C.c_size_t, u64p, u64p, C.c_int, C.c_int, vp, vp], C.c_int),
     "h2_ipa_rounds_device": ([C.c_int, C.c_uint, C.c_uint, C.c_uint64, C.c_int, vp, vp, u64p, u64p, u64p, vp, vp, IPA_WRITE_POINT_FN,
                              IPA_SQUEEZE_FN, vp, u64p, u64p, vp], C.c_int),
     "h2_ipa_rounds": ([C.c_int, C.c_uint, C.c_uint, C.c_uint64, C.c_int, u64p, u64p, u64p, u64p, u64p, IPA_WRITE_POINT_FN, IPA_SQUEEZE_FN, vp,

@@ -168,6 +168,27 @@ def ipa_round_scalars(p_prime, k: int, j: int, challenges, field: int, out_l, ou
                                             out_r.data_ptr(), _stream_ptr()), "h2_ipa_round_scalars_device")
 
 
+def ipa_s_combine(k: int, challenges, coeffs, field: int, out, form: int = FORM_MONTGOMERY, accumulate: bool = False):
+    """out[j] (+)= sum_b coeffs[b] * prod_{i : bit i of j set} u_b[k-1-i] for j < 2^k: `compute_s(u_b, coeffs[b])` of the verifier
+    (poly/commitment/verifier.rs:156-172) summed over a batch of proofs (see h2_ipa_s_combine).  challenges: (batch, k, 4) or
+    (batch * k, 4) limbs, u_0 .. u_{k-1} of each proof in transcript order; coeffs: (batch, 4).  `out`: a (2^k, 4) CUDA tensor
+    (asynchronous on the current stream) or a C-contiguous uint64 numpy array, written in place and returned."""
+    coeffs = _np(np.asarray(coeffs, dtype=np.uint64).reshape(-1, 4), 4)
+    batch = coeffs.shape[0]
+    ch = _np(np.asarray(challenges, dtype=np.uint64).reshape(-1, 4), 4)
+    if ch.shape[0] != batch * k or out.shape[0] != 1 << k or batch == 0:
+        raise ValueError("ipa_s_combine: shapes do not match (k, batch)")
+    acc = 1 if accumulate else 0
+    if _is_torch(out):
+        check(lib().h2_ipa_s_combine_device(field, k, batch, _p(ch), _p(coeffs), form, acc, _dev_vec(out).data_ptr(), _stream_ptr()),
+              "h2_ipa_s_combine_device")
+        return out
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags["C_CONTIGUOUS"] and out.ndim == 2 and out.shape[1] == 4):
+        raise ValueError("ipa_s_combine: `out` must be a C-contiguous (2^k, 4) uint64 array (written in place)")
+    check(lib().h2_ipa_s_combine(field, k, batch, _p(ch), _p(coeffs), form, acc, _p(out)), "h2_ipa_s_combine")
+    return out
+
+
 def sort_field(a, field: int, form: int = FORM_MONTGOMERY):
     """`Vec<F>::sort()` as the lookup prover uses it (plonk/lookup/prover.rs:574): ascending by canonical value.  CUDA tensor,
     in place."""

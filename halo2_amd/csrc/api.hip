@@ -192,6 +192,7 @@ extern "C" int h2_trim(void) {
     h2::ntt_release_workspaces();
     h2::poly_release_workspaces();
     h2::ipa_release_workspaces();
+    h2::verify_release_workspaces();
     h2::eval_release_workspaces();
     h2::lookup_release_workspaces();
     return H2_OK;

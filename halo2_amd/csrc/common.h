@@ -113,6 +113,7 @@ void msm_release_workspaces();
 void ntt_release_workspaces();
 void poly_release_workspaces();
 void ipa_release_workspaces();
+void verify_release_workspaces();
 void eval_release_workspaces();
 void lookup_release_workspaces();
 

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import fields
 from ._lib import FORM_MONTGOMERY
-from .arithmetic import best_multiexp, points_sum, scale_add
+from .arithmetic import best_multiexp, ipa_s_combine, points_sum, scale_add
 from .commitment import Blind, Params
 from .multiopen import construct_intermediate_sets
 from .transcript import _Blake2bTranscript
@@ -69,10 +69,14 @@ class Blake2bRead(_Blake2bTranscript):
 # ---- MSM and Guard (poly/commitment/msm.rs, verifier.rs:12-61) ----------------------------------------------------------------------
 class MSM:
     """A linear combination of commitments waiting to be checked against the identity.  `other` keys points by x as the
-    reference does (msm.rs:17, :63-84): a point and its negation share an entry."""
+    reference does (msm.rs:17, :63-84): a point and its negation share an entry.
 
-    def __init__(self, params: Params):
+    `defer_constant=True` keeps the G_0 constant (`add_constant_term`) as a host scalar in `g_constant` instead of an n-element
+    device vector: a batch verifier (halo2_amd/batch.py) folds it into one combined vector for the whole batch."""
+
+    def __init__(self, params: Params, defer_constant: bool = False):
         self.params = params
+        self.g_constant = 0 if defer_constant else None
         self.sf = fields.CURVE_FIELDS[params.curve][1]
         self.bm = fields.MODULUS[fields.CURVE_FIELDS[params.curve][0]]
         self.m = fields.MODULUS[self.sf]
@@ -82,7 +86,8 @@ class MSM:
         self.other = {}
 
     def clone(self) -> "MSM":
-        c = MSM(self.params)
+        c = MSM(self.params, defer_constant=self.g_constant is not None)
+        c.g_constant = self.g_constant
         c.g_scalars = None if self.g_scalars is None else self.g_scalars.clone()
         c.w_scalar, c.u_scalar = self.w_scalar, self.u_scalar
         c.other = {x: list(v) for x, v in self.other.items()}
@@ -107,6 +112,8 @@ class MSM:
             self.append_term(scalar, (x, y))
         if other.g_scalars is not None:
             self.add_to_g_scalars(other.g_scalars)
+        if other.g_constant:
+            self.add_constant_term(other.g_constant)
         if other.w_scalar is not None:
             self.add_to_w_scalar(other.w_scalar)
         if other.u_scalar is not None:
@@ -118,6 +125,9 @@ class MSM:
 
     def add_constant_term(self, constant: int) -> None:                                  # msm.rs:86-95
         import torch
+        if self.g_constant is not None:
+            self.g_constant = (self.g_constant + constant) % self.m
+            return
         if self.g_scalars is None:
             self.g_scalars = torch.zeros((self.params.n, 4), dtype=torch.int64, device=self._dev())
         cur = fields.from_limbs(self.g_scalars[0].cpu().numpy().view(np.uint64).reshape(1, 4), self.sf, True)[0]
@@ -141,6 +151,8 @@ class MSM:
         import torch
         if self.g_scalars is not None:
             scale_add(self.g_scalars, fields.scalar_limbs(factor % self.m, self.sf, True), torch.zeros_like(self.g_scalars), self.sf)
+        if self.g_constant is not None:
+            self.g_constant = self.g_constant * factor % self.m
         for v in self.other.values():
             v[0] = v[0] * factor % self.m
         if self.w_scalar is not None:
@@ -151,6 +163,10 @@ class MSM:
     def eval(self) -> bool:
         """msm.rs:131-175: is the combination the identity?  The g part is a commit over the registered generators; the
         handful of other terms, w and u one small generic multiexp; the two partial sums are added on the device."""
+        if self.g_constant:                                                               # a deferred G_0 constant joins the g part
+            constant, self.g_constant = self.g_constant, None
+            self.add_constant_term(constant)
+            self.g_constant = 0
         bf = fields.CURVE_FIELDS[self.params.curve][0]
         scalars, bases = [], []
         for x, (scalar, y) in self.other.items():
@@ -193,6 +209,23 @@ def compute_b(x: int, u, m: int) -> int:
     return tmp
 
 
+@dataclass
+class Accumulator:
+    """poly/commitment/verifier.rs:22-30: the claimed G'_0 = <s, g> of an opening and the challenges u_0 .. u_{k-1} it is
+    computed from -- what a recursive verifier carries forward instead of checking the 2^k-point commit itself."""
+    g: tuple | None
+    u: list
+
+
+def s_vector(params: Params, u, coeff: int = 1):
+    """compute_s(u, coeff) (verifier.rs:156-172) as an (n, 4) Montgomery CUDA tensor, by one h2_ipa_s_combine_device launch."""
+    import torch
+    sf = fields.CURVE_FIELDS[params.curve][1]
+    out = torch.empty((params.n, 4), dtype=torch.int64, device=fields.current_device())
+    return ipa_s_combine(params.k, fields.to_limbs(list(u), sf, True), fields.scalar_limbs(coeff % fields.MODULUS[sf], sf, True), sf,
+                         out)
+
+
 class Guard:
     def __init__(self, msm: MSM, neg_c: int, u):
         self.msm, self.neg_c, self.u = msm, neg_c, list(u)
@@ -200,6 +233,17 @@ class Guard:
     def use_challenges(self) -> MSM:                                                     # verifier.rs:35-41
         self.msm.add_to_g_scalars(compute_s(self.u, self.neg_c, self.msm.sf, self.msm._dev()))
         return self.msm
+
+    def compute_g(self):                                                                 # verifier.rs:53-58
+        """G'_0 = <compute_s(u, 1), g> as an affine (x, y) (None for the identity): the s vector by the batched challenge-product
+        kernel with one proof and coefficient 1, then one commit over the registered g."""
+        params = self.msm.params
+        return _affine(params, params.commit_unblinded(s_vector(params, self.u)).cpu().numpy().view(np.uint64))
+
+    def use_g(self, g):                                                                  # verifier.rs:43-51
+        """Appends [neg_c] g to the MSM in place of the s vector; returns (msm, Accumulator(g, u))."""
+        self.msm.append_term(self.neg_c, g)
+        return self.msm, Accumulator(g, list(self.u))
 
 
 def commitment_verify_proof(params: Params, msm: MSM, transcript: Blake2bRead, x: int, v: int) -> Guard:
@@ -402,28 +446,44 @@ def verify_proof_many(params: Params, vk: VerifyingKey, instances, proof: bytes)
         return False
 
 
-def _verify(params: Params, vk: VerifyingKey, instances, proof: bytes) -> bool:
-    import torch
-    cs, domain = vk.cs, vk.domain
-    sf, m, n = domain.field, domain.m, params.n
-    bf = cs.blinding_factors
-    usable = n - (bf + 1)
-    dev = fields.current_device()
-    host = lambda t: t.cpu().numpy().view(np.uint64)
-    num_proofs = len(instances)
-    instance_commitments = []
-    for instance_columns in instances:                                                    # :77-101
-        if len(instance_columns) != cs.num_instance_columns:
+def _check_instances(params: Params, vk: VerifyingKey, instances) -> None:
+    """:77-101 before any commit: the column count of every circuit instance and the length of every column."""
+    usable = params.n - (vk.cs.blinding_factors + 1)
+    for instance_columns in instances:
+        if len(instance_columns) != vk.cs.num_instance_columns:
             raise VerificationError("InvalidInstances")
-        cms = []
         for values in instance_columns:
             if len(values) > usable:
                 raise VerificationError("InstanceTooLarge")
-            lag = torch.zeros((n, 4), dtype=torch.int64, device=dev)
-            if len(values):
-                lag[:len(values)] = torch.from_numpy(fields.to_limbs(values, sf, True).view(np.int64)).to(dev)
-            cms.append(_affine(params, host(params.commit_lagrange(lag, Blind(field=sf)))))
-        instance_commitments.append(cms)
+
+
+def _instance_lagrange(params: Params, values, sf: int, dev):
+    """One instance column as its (n, 4) Montgomery Lagrange vector on the device (the rows past `values` are zero)."""
+    import torch
+    lag = torch.zeros((params.n, 4), dtype=torch.int64, device=dev)
+    if len(values):
+        lag[:len(values)] = torch.from_numpy(fields.to_limbs(values, sf, True).view(np.int64)).to(dev)
+    return lag
+
+
+def _verify(params: Params, vk: VerifyingKey, instances, proof: bytes) -> bool:
+    guard = _verify_guard(params, vk, instances, proof, MSM(params))
+    return guard.use_challenges().eval()                                                  # SingleVerifier::process, :48-62
+
+
+def _verify_guard(params: Params, vk: VerifyingKey, instances, proof: bytes, msm: MSM, instance_commitments=None) -> Guard:
+    """plonk/verifier.rs:65-347 up to the Guard that a VerificationStrategy finishes (`strategy.process(|msm| ...)`).
+    `instance_commitments`: the (x, y) commitments of the instance columns when the caller has committed them already (a batch)."""
+    cs, domain = vk.cs, vk.domain
+    sf, m, n = domain.field, domain.m, params.n
+    bf = cs.blinding_factors
+    dev = fields.current_device()
+    host = lambda t: t.cpu().numpy().view(np.uint64)
+    num_proofs = len(instances)
+    if instance_commitments is None:                                                      # :77-101
+        _check_instances(params, vk, instances)
+        instance_commitments = [[_affine(params, host(params.commit_lagrange(_instance_lagrange(params, values, sf, dev), Blind(field=sf))))
+                                 for values in instance_columns] for instance_columns in instances]
     t = Blake2bRead(params.curve, proof)
     t.common_scalar(fields.scalar_limbs(vk.vk_repr % m, sf, True))                        # :106
 
@@ -501,5 +561,40 @@ def _verify(params: Params, vk: VerifyingKey, instances, proof: bytes) -> bool:
     queries += [Q(rot(r), vk.fixed_commitments[c], e) for (c, r), e in zip(cs.fixed_queries, fixed_evals)]
     queries += [Q(x, c, e) for c, e in zip(vk.permutation_commitments, sigma_evals)]
     queries += [Q(x, h_commitment, expected_h_eval), Q(x, random_poly_commitment, random_eval)]   # vanishing/verifier.rs:119-139
-    guard = multiopen_verify_proof(params, t, queries, MSM(params))                       # :347
-    return guard.use_challenges().eval()                                                  # SingleVerifier::process, :48-62
+    return multiopen_verify_proof(params, t, queries, msm)                                # :347
+
+
+# ---- verification strategies (plonk/verifier.rs:21-63; tests/plonk_api.rs:513-545) ------------------------------------------------
+class SingleVerifier:
+    """One proof, one `MSM::eval` (verifier.rs:35-63): what verify_proof / verify_proof_many do."""
+
+    def __init__(self, params: Params):
+        self.msm = MSM(params)
+
+    def process(self, f) -> bool:
+        return f(self.msm).use_challenges().eval()
+
+
+class AccumulationVerifier:
+    """The accumulation strategy of the reference's own test (tests/plonk_api.rs:513-545): G'_0 is computed (`compute_g`),
+    appended as a point (`use_g`) and the MSM evaluated; the Accumulator (G, u) of the last proof is kept in `accumulator`."""
+
+    def __init__(self, params: Params):
+        self.msm = MSM(params)
+        self.accumulator = None
+
+    def process(self, f) -> bool:
+        guard = f(self.msm)
+        g = guard.compute_g()
+        msm, self.accumulator = guard.use_g(g)
+        return msm.eval()
+
+
+def verify_proof_with_strategy(params: Params, vk: VerifyingKey, strategy, instances, proof: bytes):
+    """The reference's generic `verify_proof(params, vk, strategy, instances, transcript)` (verifier.rs:65-347): the proof is
+    read up to its Guard, which `strategy.process` finishes.  Returns the strategy's output (True / False for the two strategies
+    here); a malformed or rejected proof is False."""
+    try:
+        return strategy.process(lambda msm: _verify_guard(params, vk, list(instances), proof, msm))
+    except VerificationError:
+        return False

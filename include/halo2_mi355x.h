@@ -269,6 +269,15 @@ int h2_fold_scalars_device(int field, void *d_a, size_t half, const uint64_t *fa
  * d_cl, d_cr: 2^k elements each, in the form of d_p.  1 <= k <= 30, j < k. */
 int h2_ipa_round_scalars_device(int field, const void *d_p, unsigned k, unsigned j, const uint64_t *challenges, int form,
                                 void *d_cl, void *d_cr, void *stream);
+/* Guard::use_challenges summed over a batch (poly/commitment/verifier.rs:35-41, compute_s :156-172; plonk/verifier/batch.rs:79-127):
+ *   out[j] (+)= sum_{b < batch} coeffs[b] * prod_{i : bit i of j set} challenges[b*k + (k-1-i)],   0 <= j < 2^k
+ * i.e. the sum of coeffs[b] * compute_s(u_b, 1).  challenges: batch*k scalars (proof-major, u_0..u_{k-1} in transcript order),
+ * coeffs: batch scalars, both host memory in `form`; out / d_out: 2^k scalars in `form`.  accumulate = 0 overwrites, 1 adds.
+ * 1 <= k <= 30, 1 <= batch <= 2^24.  With batch = 1 and coefficient 1 this is the s vector of Guard::compute_g (:22-33). */
+int h2_ipa_s_combine(int field, unsigned k, size_t batch, const uint64_t *challenges, const uint64_t *coeffs, int form,
+                     int accumulate, uint64_t *out);
+int h2_ipa_s_combine_device(int field, unsigned k, size_t batch, const uint64_t *challenges, const uint64_t *coeffs, int form,
+                            int accumulate, void *d_out, void *stream);
 /* The whole round loop of commitment::create_proof (prover.rs:104-142) in one call, p' and b resident: per round the two inner
  * products (:109-110), the L_j / R_j scalars over the original generators (above), their commit, the two points to the
  * transcript (:121-122), the challenge and its inverse (:124-125), the p' / b folds (:128-133) and the blind bookkeeping
