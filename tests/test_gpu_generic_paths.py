@@ -173,7 +173,9 @@ SWEEP = [
 
 def test_last_path_before_any_call_is_refused():
     import torch
-    s = torch.cuda.Stream()
+    # torch hands streams out round-robin from a pool of 32 per priority: a default-priority stream may be one that an earlier test
+    # already ran a multiexp on; no test uses the high-priority pool, so this one is fresh
+    s = torch.cuda.Stream(priority=-1)
     assert h.lib().h2_msm_last_path(C.c_void_p(s.cuda_stream), None, None, None, None) == _lib.H2_ERR_ARGS
 
 
