@@ -240,19 +240,11 @@ template __global__ void msm_accumulate<FP, false, false>(const u32 *__restrict_
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FP, true, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
 template __global__ void msm_accumulate<FP, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
 template __global__ void msm_accumulate<FQ, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FQ, true, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);

@@ -540,4 +540,28 @@ template __global__ void msm_combine<FQ>(const u32 *__restrict__ slice_sums, int
 template __global__ void msm_combine_ranges<FP>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
 template __global__ void msm_combine_ranges<FQ>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
 
+// ---- host: the five launches of the carry-free fold, for every caller (declared in msm_internal.cuh)
+template <int FB>
+void fold9_group(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
+                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
+                 const ColOut &co, const ColStride &cs) {
+    const u32 fz = cs.joined ? 1 : cols, ftb = cs.joined ? cols * tb : tb;       // joined columns: one pass over the cols x tb buckets
+    int cb = 0;
+    while ((1u << cb) < wideS) ++cb;
+    u32 *lines = lines9 + 36 * (size_t)slice0 * (wideS + wideNR);
+    hipLaunchKernelGGL((fold9_finish<FB>), dim3((ftb + 255) / 256, 1, fz), dim3(256), 0, st, heads9, starts, buckets9, heavy, ftb, T, lane_div, cs);
+    hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows, fz), dim3(256), 0, st, heads9, starts, hscratch, (const u32 *)heavy, ftb, T, lane_div, cs);
+    hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows, 1, fz), dim3(64), 0, st, (const u32 *)hscratch, buckets9, (const u32 *)heavy, cs);
+    // line sums, then the bit planes of the line weights and their combination in one launch (fold9_planes)
+    hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(wideS + wideNR - 1, nslices, cols), dim3(256), 0, st, (const u32 *)buckets9, lines, wideS, wideNR, cs);
+    hipLaunchKernelGGL((fold9_planes<FB>), dim3(c - 1, nslices, cols), dim3(256), 0, st, (const u32 *)lines, planes9 + 36 * (size_t)slice0 * 32, ctr + slice0, wideS, wideNR,
+                       cb, out + 32 * (size_t)slice0, out_kind, out_mont ? 1 : 0, co, cs);
+}
+template void fold9_group<FP>(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
+                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
+                 const ColOut &co, const ColStride &cs);
+template void fold9_group<FQ>(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
+                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
+                 const ColOut &co, const ColStride &cs);
+
 }  // namespace h2

@@ -40,6 +40,8 @@ namespace h2 {
 
 namespace {
 
+constexpr u32 kLaneDiv = 16;      // entries per lane the accumulates aim at (full-size columns)
+
 struct Group {
     u32 w0 = 0, ns = 0;     // window slices [w0, w0 + ns)
     u32 tb = 0;             // its buckets: ns * NB
@@ -103,28 +105,23 @@ bool group_geometry(u32 cols, u32 nb, Group &g) {
     return false;
 }
 
-}  // namespace
+// What one grouped call decides before it reserves or enqueues anything: the form, the groups and the sizes its reservations follow from.
+struct GroupedPlan {
+    bool throughput;        // one group on the caller's stream (another stream's generic multiexp is in flight), else the latency form
+    bool lds_fence;         // the chain links are fenced onto CUs without an accumulate workgroup by LDS requests
+    int G;
+    Group grp[MsmContext::kMaxGroups];
+    size_t head_slots, hist_words, tagged_words, plan_words;
+    u32 wideS, wideNR;      // the bucket matrix of a slice (fold9_rowcol / fold9_planes)
+};
 
-template <int FB, int FS>
-int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, hipStream_t st) {
+// H2_ERR_BATCH_SHAPE when the shape is not the grouped form's own (the header has the limits).  The laboratory build's switches of the grouped
+// form are read here, once (the shipped library: every one at its default).
+int grouped_plan(const MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, GroupedPlan &gp) {
     static const bool on = [] { const char *e = ab_env("H2_GENERIC_GROUPED"); return !(e && atoi(e) == 0); }();       // 0: round 5's slice split (A/B)
-    static const size_t min_n = [] { const char *e = ab_env("H2_GENERIC_GROUPED_MIN"); return e ? (size_t)atol(e) : ((size_t)1 << 18) + 1; }();
-    // (no upper bound on scalars_n here: group_geometry below declines every size beyond the layouts' limits, see the header)
-    if (!on || scalars_n < min_n || sh.c < 8 || sh.c > kMaxC || sh.W < 3 || sh.W > 16 || sh.NB < 128) return H2_ERR_BATCH_SHAPE;
-    const u32 m = (u32)scalars_n, cols = 2 * m, W = (u32)sh.W, NB = sh.NB, c = (u32)sh.c;
-    int rc;
-    static const bool fold_late = [] { const char *e = ab_env("H2_GG_FOLD_LATE"); return e && atoi(e) == 1; }();       // experiments (laboratory build)
-    static const int lowprio = [] { const char *e = ab_env("H2_GG_LOWPRIO"); return e ? atoi(e) : 0; }();       // mask: 1 finish, 2 heavy, 4 rowcol, 8 planes (upper groups)
-    static const int acc_block = [] { const char *e = ab_env("H2_GG_ACC_BLOCK"); return e && atoi(e) == 256 ? 256 : 512; }();       // 256: A/B
-    static const int skip = [] { const char *e = ab_env("H2_GG_SKIP"); return e ? atoi(e) : 0; }();       // TIMING ONLY, WRONG RESULTS: drop side-stream fold stages (1 finish, 2 heavy, 4 rowcol, 8 planes, 16 chain)
-    static const bool big_all = [] { const char *e = ab_env("H2_GG_BIG"); return !(e && atoi(e) == 0); }();
     static const int form_env = [] { const char *e = ab_env("H2_GG_FORM"); return e ? atoi(e) : 0; }();        // 1: latency form always, 2: throughput form always (A/B)
-    // (from 2^22 points on the whole sort in front of a single group costs more than the grouping loses: 837 against 900 M scalar-mults/s on three streams)
-    const bool throughput = form_env == 2 || (form_env != 1 && scalars_n < ((size_t)1 << 22) && msm_other_generic_in_flight(&cx));
-    // ---- the groups, upper slices first.  Nine slices: 4 + 3 + 2 -- the first group's sort is all that stands in front of the first
-    // addition, the last group's fold all that stands behind the last.  (H2_GENERIC_GROUPS="a,b,c": laboratory build only.)
-    int sizes[MsmContext::kMaxGroups] = {0, 0, 0, 0}, G = 0;
-    static const std::vector<int> env_sizes = [] {
+    static const int spare_env = [] { const char *e = ab_env("H2_GG_SPARE"); return e ? atoi(e) : -1; }();     // CUs left without an accumulate workgroup
+    static const std::vector<int> env_sizes = [] {                                                             // H2_GENERIC_GROUPS="a,b,c"
         std::vector<int> v;
         if (const char *e = ab_env("H2_GENERIC_GROUPS"))
             for (const char *p = e; *p;) {
@@ -134,89 +131,86 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
             }
         return v;
     }();
-    {
-        int sum = 0;
-        for (int v : env_sizes) sum += v;
-        if (!env_sizes.empty() && env_sizes.size() <= (size_t)MsmContext::kMaxGroups && sum == (int)W && *std::min_element(env_sizes.begin(), env_sizes.end()) >= 1) {
-            for (int v : env_sizes) sizes[G++] = v;
-        } else {
-            if (throughput) {
-                // independent calls on other streams are in flight: their sorts and folds hide beside this call's accumulate anyway, every accumulate
-                // launch that starts beside them runs ragged, and side streams of several calls would share hardware queues: ONE group, everything on
-                // the caller's stream (2^20: 1.16-1.22 ms per call on three streams against 1.26-1.46 for any grouping; 2^22: 862 M/s)
-                sizes[0] = (int)W;
-                G = 1;
-            } else {
-                // a call alone: 5 + 2 + 2 of nine slices -- the first group's sort is all that stands in front of the first addition, the last
-                // (smallest) group's fold all that stands behind the last
-                const int last = std::max(1, (int)W * 2 / 9), mid = last, top = (int)W - last - mid;
-                sizes[0] = top; sizes[1] = mid; sizes[2] = last;
-                G = 3;
-            }
-        }
+    // (no upper bound on scalars_n here: group_geometry below declines every size beyond the layouts' limits, see the header)
+    if (!on || scalars_n < ((size_t)1 << 18) + 1 || sh.c < 8 || sh.c > kMaxC || sh.W < 3 || sh.W > 16 || sh.NB < 128) return H2_ERR_BATCH_SHAPE;
+    const u32 cols = 2 * (u32)scalars_n, W = (u32)sh.W, NB = sh.NB;
+    // (from 2^22 points on the whole sort in front of a single group costs more than the grouping loses: 837 against 900 M scalar-mults/s on three streams)
+    gp.throughput = form_env == 2 || (form_env != 1 && scalars_n < ((size_t)1 << 22) && msm_other_generic_in_flight(&cx));
+    // ---- the groups, upper slices first (H2_GENERIC_GROUPS="a,b,c": laboratory build only)
+    int sizes[MsmContext::kMaxGroups] = {0, 0, 0, 0}, sum = 0;
+    int &G = gp.G = 0;
+    for (int v : env_sizes) sum += v;
+    if (!env_sizes.empty() && env_sizes.size() <= (size_t)MsmContext::kMaxGroups && sum == (int)W && *std::min_element(env_sizes.begin(), env_sizes.end()) >= 1) {
+        for (int v : env_sizes) sizes[G++] = v;
+    } else if (gp.throughput) {
+        // independent calls on other streams are in flight: their sorts and folds hide beside this call's accumulate anyway, every accumulate
+        // launch that starts beside them runs ragged, and side streams of several calls would share hardware queues: ONE group, everything on
+        // the caller's stream (2^20: 1.16-1.22 ms per call on three streams against 1.26-1.46 for any grouping; 2^22: 862 M/s)
+        sizes[0] = (int)W;
+        G = 1;
+    } else {
+        // a call alone: 5 + 2 + 2 of nine slices -- the first group's sort is all that stands in front of the first addition, the last
+        // (smallest) group's fold all that stands behind the last
+        const int last = std::max(1, (int)W * 2 / 9), mid = last, top = (int)W - last - mid;
+        sizes[0] = top; sizes[1] = mid; sizes[2] = last;
+        G = 3;
     }
-    Group grp[MsmContext::kMaxGroups];
-    {
-        u32 hi = W;
-        size_t ent = 0, sts = 0, bkt = 0;
-        for (int g = 0; g < G; ++g) {
-            grp[g].ns = (u32)sizes[g];
-            grp[g].w0 = hi - (u32)sizes[g];
-            hi = grp[g].w0;
-            if (!group_geometry(cols, NB, grp[g])) return H2_ERR_BATCH_SHAPE;
-            grp[g].ent_off = ent;
-            grp[g].starts_off = sts;
-            grp[g].bucket_off = bkt;
-            ent += grp[g].emax;
-            sts += (size_t)grp[g].tb + 2;
-            bkt += grp[g].tb;
-        }
-        if (ent >= ((size_t)1 << 31)) return H2_ERR_BATCH_SHAPE;
+    Group *grp = gp.grp;
+    u32 hi = W;
+    size_t ent = 0, sts = 0, bkt = 0;
+    for (int g = 0; g < G; ++g) {
+        grp[g].ns = (u32)sizes[g];
+        grp[g].w0 = hi - (u32)sizes[g];
+        hi = grp[g].w0;
+        if (!group_geometry(cols, NB, grp[g])) return H2_ERR_BATCH_SHAPE;
+        grp[g].ent_off = ent;
+        grp[g].starts_off = sts;
+        grp[g].bucket_off = bkt;
+        ent += grp[g].emax;
+        sts += (size_t)grp[g].tb + 2;
+        bkt += grp[g].tb;
     }
-    const u32 tb = W * NB, lane_div = 16;
+    if (ent >= ((size_t)1 << 31)) return H2_ERR_BATCH_SHAPE;
     const double fraction = a.lane_fraction > 0.0 ? a.lane_fraction : g_lane_fraction.load();
     // The latency form leaves one CU per XCD without an accumulate workgroup and FENCES the chain kernels onto them: every accumulate workgroup asks
     // for 64 KiB of LDS it never touches, every link of the Horner chain for 100 KiB -- so a chain wave (one wave at raised priority issuing
     // dependent multiply-adds back to back: it takes ~90 % of its SIMD) can only land on a CU that holds no accumulate workgroup, instead of
     // starving two accumulate waves for its whole 130-180 us while every other lane of the launch waits for them (measured: the second group's
-    // accumulate 494 -> 429 us; profiles/r06_generic_grouped.txt).  H2_GG_SPARE / H2_GG_LDS: laboratory build only.
-    static const int spare_env = [] { const char *e = ab_env("H2_GG_SPARE"); return e ? atoi(e) : -1; }();
-    static const int lds_env = [] { const char *e = ab_env("H2_GG_LDS"); return e ? atoi(e) : -1; }();
-    const bool lds_fence = lds_env >= 0 ? lds_env == 1 : (!throughput && G > 1);
-    const u32 spare = spare_env >= 0 ? (u32)spare_env : (lds_fence ? std::max(1u, lanes / 512u / 32u) : 0u);      // one CU in 32: 8 of an MI355X's 256 (one per XCD)
+    // accumulate 494 -> 429 us; profiles/r06_generic_grouped.txt).  H2_GG_SPARE: laboratory build only.
+    gp.lds_fence = !gp.throughput && G > 1;
+    const u32 spare = spare_env >= 0 ? (u32)spare_env : (gp.lds_fence ? std::max(1u, lanes / 512u / 32u) : 0u);      // one CU in 32: 8 of an MI355X's 256 (one per XCD)
     // (signed: a small fraction -- or few CUs -- must not wrap below the spare CUs' share and hand the accumulate every lane there is)
     const long long want_lanes = (long long)((u32)(lanes * fraction) / 512u * 512u) - 512LL * std::min(spare, 64u);
     const u32 usable = (u32)std::max<long long>(512, want_lanes);
-    size_t head_slots = 0, hist_words = 0, tagged_words = 0, plan_words = 0;
+    gp.head_slots = gp.hist_words = gp.tagged_words = gp.plan_words = 0;
     for (int g = 0; g < G; ++g) {
-        grp[g].T = (u32)std::min<size_t>(usable, std::max<size_t>(512, (grp[g].emax / lane_div + 511) / 512 * 512));
-        head_slots += grp[g].T;
-        hist_words = std::max(hist_words, (size_t)grp[g].B1 * grp[g].gs.nh);
-        tagged_words = std::max(tagged_words, grp[g].emax);
-        plan_words = std::max(plan_words, grp[g].plan_words);
+        grp[g].T = (u32)std::min<size_t>(usable, std::max<size_t>(512, (grp[g].emax / kLaneDiv + 511) / 512 * 512));
+        gp.head_slots += grp[g].T;
+        gp.hist_words = std::max(gp.hist_words, (size_t)grp[g].B1 * grp[g].gs.nh);
+        gp.tagged_words = std::max(gp.tagged_words, grp[g].emax);
+        gp.plan_words = std::max(gp.plan_words, grp[g].plan_words);
     }
-    cx.last.path = throughput ? H2_MSM_PATH_GROUPED_THROUGHPUT : H2_MSM_PATH_GROUPED_LATENCY;       // h2_msm_last_path
-    cx.last.groups = G;
-    cx.last.acc_lanes = 0;
-    for (int g = 0; g < G; ++g) cx.last.acc_lanes = std::max(cx.last.acc_lanes, grp[g].T);
-    cx.last.c = (int)c;
-    const int bb = (int)c - 1;
-    const u32 wideS = 1u << (bb / 2), wideNR = NB / wideS;
-    int cb = 0;
-    while ((1u << cb) < wideS) ++cb;
-    // ---- every workspace before anything is enqueued (a reservation that grows frees and synchronises)
-    const u32 row = (cols + 7) & ~7u;
+    gp.wideS = 1u << ((sh.c - 1) / 2);
+    gp.wideNR = NB / gp.wideS;
+    return H2_OK;
+}
+
+// every workspace, attribute, stream and event of the call before anything is enqueued (a reservation that grows frees and synchronises)
+int grouped_reserve(MsmContext &cx, const GroupedPlan &gp, u32 m, u32 W, u32 NB, hipStream_t st) {
+    const int G = gp.G;
+    const u32 cols = 2 * m, tb = W * NB, row = (cols + 7) & ~7u;
+    int rc;
     if ((rc = cx.digits.reserve((size_t)W * row * 2 + 64)) != H2_OK) return rc;
-    if ((rc = cx.hist.reserve(hist_words * 4)) != H2_OK) return rc;
-    if ((rc = cx.tagged.reserve(tagged_words * 4)) != H2_OK) return rc;
-    if ((rc = cx.plan.reserve(plan_words * 4)) != H2_OK) return rc;
+    if ((rc = cx.hist.reserve(gp.hist_words * 4)) != H2_OK) return rc;
+    if ((rc = cx.tagged.reserve(gp.tagged_words * 4)) != H2_OK) return rc;
+    if ((rc = cx.plan.reserve(gp.plan_words * 4)) != H2_OK) return rc;
     if ((rc = cx.starts.reserve(((size_t)tb + 2 * G) * 4)) != H2_OK) return rc;
     if ((rc = cx.entries.reserve((size_t)W * cols * 4)) != H2_OK) return rc;
     if ((rc = cx.heavy.reserve((size_t)G * (kMaxHeavy + 2) * 4)) != H2_OK) return rc;
     if ((rc = cx.hscratch.reserve((size_t)G * kMaxHeavy * kHeavyBlocks * 144)) != H2_OK) return rc;
-    if ((rc = cx.partial.reserve((size_t)W * (wideS + wideNR + 32) * 144)) != H2_OK) return rc;
+    if ((rc = cx.partial.reserve((size_t)W * (gp.wideS + gp.wideNR + 32) * 144)) != H2_OK) return rc;
     if ((rc = cx.ssums.reserve((size_t)(W + G + 1) * 128)) != H2_OK) return rc;
-    if ((rc = cx.seg9.reserve((head_slots + (size_t)tb) * 144)) != H2_OK) return rc;
+    if ((rc = cx.seg9.reserve((gp.head_slots + (size_t)tb) * 144)) != H2_OK) return rc;
     if ((rc = cx.bases9.reserve((size_t)m * 128 + 64)) != H2_OK) return rc;
     if (cx.fold_ctr.cap < (size_t)kMaxCols * 64) {      // fold9_planes' arrival counters: zero once, every launch leaves them at zero
         if ((rc = cx.fold_ctr.reserve((size_t)kMaxCols * 64)) != H2_OK) return rc;
@@ -241,13 +235,33 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     // stays on the caller's stream.
     if (G > 1 && !cx.gstream[0])
         for (int i = 0; i < 3; ++i) H2_HIP(hipStreamCreateWithFlags(&cx.gstream[i], hipStreamNonBlocking));
+    for (int i = 0; i < 4 + 3 * G; ++i)
+        if (!cx.gev[i]) H2_HIP(hipEventCreateWithFlags(&cx.gev[i], hipEventDisableTiming));
+    return H2_OK;
+}
+
+}  // namespace
+
+template <int FB, int FS>
+int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, hipStream_t st) {
+    GroupedPlan gp;
+    int rc;
+    if ((rc = grouped_plan(cx, a, sh, scalars_n, lanes, gp)) != H2_OK) return rc;
+    const int G = gp.G;
+    const Group *grp = gp.grp;
+    const u32 m = (u32)scalars_n, cols = 2 * m, W = (u32)sh.W, NB = sh.NB, c = (u32)sh.c, row = (cols + 7) & ~7u;
+    const u32 wideS = gp.wideS, wideNR = gp.wideNR;
+    cx.last.path = gp.throughput ? H2_MSM_PATH_GROUPED_THROUGHPUT : H2_MSM_PATH_GROUPED_LATENCY;       // h2_msm_last_path
+    cx.last.groups = G;
+    cx.last.acc_lanes = 0;
+    for (int g = 0; g < G; ++g) cx.last.acc_lanes = std::max(cx.last.acc_lanes, grp[g].T);
+    cx.last.c = (int)c;
+    if ((rc = grouped_reserve(cx, gp, m, W, NB, st)) != H2_OK) return rc;
     hipStream_t const caller = st;
     if (G > 1) {
         assert(cx.gstream[0] && cx.gstream[1] && cx.gstream[2]);
         st = cx.gstream[1];
     }
-    for (int i = 0; i < 4 + 3 * G; ++i)
-        if (!cx.gev[i]) H2_HIP(hipEventCreateWithFlags(&cx.gev[i], hipEventDisableTiming));
     hipStream_t const sort_s = G > 1 ? cx.gstream[0] : nullptr;      // (one group: no side stream -- a context that never ran the latency form has none)
     hipEvent_t ev_fork = cx.gev[0], ev_conv = cx.gev[1];
     auto ev_sorted = [&](int g) { return cx.gev[2 + 3 * g]; };
@@ -255,17 +269,14 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     auto ev_chain = [&](int g) { return cx.gev[4 + 3 * g]; };
     auto fold_s = [&](int g) { return g == G - 1 ? st : cx.gstream[(g & 1) ? 2 : 0]; };          // the last group folds behind its accumulate
 
-    ColIn ci;
     ColOut co;
     ColStride cs;
-    memset(&ci, 0, sizeof ci);
     memset(&co, 0, sizeof co);
     memset(&cs, 0, sizeof cs);
-    const ColStride cs0 = cs;
     const bool mont = a.form == H2_FORM_MONTGOMERY;
     uint16_t *digits = cx.digits.as<uint16_t>();
     u32 *hist1 = cx.hist.as<u32>(), *tagged = cx.tagged.as<u32>();
-    u32 *heads_all = cx.seg9.as<u32>(), *buckets_all = heads_all + 36 * head_slots;
+    u32 *heads_all = cx.seg9.as<u32>(), *buckets_all = heads_all + 36 * gp.head_slots;
     u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)W * (wideS + wideNR), *ssums = cx.ssums.as<u32>();
     const u32 *pts = cx.bases9.as<u32>();
 
@@ -289,43 +300,22 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     }
     auto sort_group = [&](int g, hipStream_t s_) {
         const Group &q = grp[g];
-        u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + q.gs.nh, *big = bin_start + q.gs.nh + 1, *gcnt = big + 64;
+        u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + q.gs.nh, *big = bin_start + q.gs.nh + 1;
         u32 *starts = cx.starts.as<u32>() + q.starts_off, *entries = cx.entries.as<u32>() + q.ent_off, *heavy = cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2);
-        const size_t nbk = (size_t)1 << q.gs.lowb;
         hipLaunchKernelGGL(msm_d1_count, dim3(q.B1), dim3(512), q.gs.nh * 4, s_, (const uint16_t *)digits, q.gs, hist1);
         hipLaunchKernelGGL(msm_s1_prefix, dim3((q.gs.nh + 15) / 16), dim3(1024), 0, s_, hist1, bin_count, q.B1, q.gs.nh, heavy, big, starts + q.tb + 1, cs);
         hipLaunchKernelGGL(msm_d1_scatter, dim3(q.B1), dim3(512), ((size_t)q.gs.nh * 3 + 1 + (size_t)q.gs.S * q.ns) * 4, s_, (const uint16_t *)digits, q.gs,
                            (const u32 *)hist1, (const u32 *)bin_count, bin_start, tagged);
         // pass 2: a workgroup per bin; it also clears the group's raw bucket slots.  A bin beyond its stage (the carry slice of the split
         // is ONE bucket; columns of repeated scalars) goes to the chunked msm_s2_big_* kernels, which return at once when the list is empty
-        hipLaunchKernelGGL(msm_s2_bins, dim3(q.gs.nh), dim3(1024), (nbk * 2 + q.cap) * 4, s_, (const u32 *)tagged, (const uint16_t *)nullptr, (const u32 *)bin_start, q.p2,
-                           q.tb, (u32)q.cap, starts, entries, big, (big_all || !g) ? kMaxBig : 0u, buckets_all + 36 * q.bucket_off, cs);
-        if (!big_all && g) return;
-        hipLaunchKernelGGL(msm_s2_big_count, dim3(kBigChunks, kMaxBig), dim3(256), nbk * 4, s_, (const u32 *)tagged, (const uint16_t *)nullptr, (const u32 *)bin_start, q.p2,
-                           (const u32 *)big, gcnt, cs);
-        hipLaunchKernelGGL(msm_s2_big_prefix, dim3(kMaxBig), dim3(256), nbk * 4, s_, (const u32 *)bin_start, q.p2, q.tb, (const u32 *)big, gcnt, starts, cs);
-        hipLaunchKernelGGL(msm_s2_big_scatter, dim3(kBigChunks, kMaxBig), dim3(256), nbk * 4, s_, (const u32 *)tagged, (const uint16_t *)nullptr, (const u32 *)bin_start, q.p2,
-                           (const u32 *)big, (const u32 *)gcnt, entries, cs);
+        sort2_pass2_bins(s_, tagged, (const uint16_t *)nullptr, bin_start, q.p2, q.tb, q.cap, starts, entries, big, kMaxBig, buckets_all + 36 * q.bucket_off, 1u, cs);
     };
     // a group's fold down to its slice sums: finish (range heads into their buckets), the heavy buckets, line sums, planes
     auto fold_group = [&](int g, hipStream_t s_) {
         const Group &q = grp[g];
-        const u32 *starts = cx.starts.as<u32>() + q.starts_off;
-        u32 *gbuckets = buckets_all + 36 * q.bucket_off, *heavy = cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2);
-        u32 *hscr = cx.hscratch.as<u32>() + (size_t)g * kMaxHeavy * kHeavyBlocks * 36;
-        const int sk = g < G - 1 ? skip : 0, lp = g < G - 1 ? lowprio : 0;
-        ColStride cs = cs0, csf = cs0, csh = cs0, csr = cs0, csp = cs0;
-        csf.lowprio = (lp & 1) ? 1u : 0u;
-        csh.lowprio = (lp & 2) ? 1u : 0u;
-        csr.lowprio = (lp & 4) ? 1u : 0u;
-        csp.lowprio = (lp & 8) ? 1u : 0u;
-        (void)cs;
-        if (!(sk & 1)) hipLaunchKernelGGL((fold9_finish<FB>), dim3((q.tb + 255) / 256), dim3(256), 0, s_, (const u32 *)heads_of[g], starts, gbuckets, heavy, q.tb, q.T, lane_div, csf);
-        if (!(sk & 2)) hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows), dim3(256), 0, s_, (const u32 *)heads_of[g], starts, hscr, (const u32 *)heavy, q.tb, q.T, lane_div, csh);
-        if (!(sk & 2)) hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows), dim3(64), 0, s_, (const u32 *)hscr, gbuckets, (const u32 *)heavy, csh);
-        if (!(sk & 4)) hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(wideS + wideNR - 1, q.ns), dim3(256), 0, s_, (const u32 *)gbuckets, lines9 + 36 * (size_t)q.w0 * (wideS + wideNR), wideS, wideNR, csr);
-        if (!(sk & 8)) hipLaunchKernelGGL((fold9_planes<FB>), dim3(c - 1, q.ns), dim3(256), 0, s_, (const u32 *)(lines9 + 36 * (size_t)q.w0 * (wideS + wideNR)), planes9 + 36 * (size_t)q.w0 * 32,
-                           cx.fold_ctr.as<u32>() + q.w0, wideS, wideNR, cb, ssums + 32 * (size_t)q.w0, kOutSliceSum, mont, co, csp);
+        fold9_group<FB>(s_, heads_of[g], cx.starts.as<u32>() + q.starts_off, buckets_all + 36 * q.bucket_off, cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2),
+                        cx.hscratch.as<u32>() + (size_t)g * kMaxHeavy * kHeavyBlocks * 36, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
+                        q.tb, q.T, kLaneDiv, (int)c, wideS, wideNR, q.w0, q.ns, 1u, co, cs);
     };
 
     // ---- sorts: the first group on the caller's stream, the others on the side stream behind it (they share hist / tagged / plan)
@@ -343,34 +333,23 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     for (int g = 0; g < G; ++g) {
         const Group &q = grp[g];
         if (g) H2_HIP(hipStreamWaitEvent(st, ev_sorted(g), 0));
-        if (acc_block == 512)
-            hipLaunchKernelGGL((msm_accumulate<FB, false, true, 512>), dim3(q.T / 512), dim3(512), lds_fence ? 65536 : 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu,
-                               (const u32 *)(cx.entries.as<u32>() + q.ent_off), (const u32 *)(cx.starts.as<u32>() + q.starts_off), heads_of[g],
-                               buckets_all + 36 * q.bucket_off, q.tb, q.T, lane_div, cs);
-        else
-        hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(q.T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu,
+        hipLaunchKernelGGL((msm_accumulate<FB, false, true, 512>), dim3(q.T / 512), dim3(512), gp.lds_fence ? 65536 : 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu,
                            (const u32 *)(cx.entries.as<u32>() + q.ent_off), (const u32 *)(cx.starts.as<u32>() + q.starts_off), heads_of[g],
-                           buckets_all + 36 * q.bucket_off, q.tb, q.T, lane_div, cs);
-        if (g < G - 1 && !fold_late) {
+                           buckets_all + 36 * q.bucket_off, q.tb, q.T, kLaneDiv, cs);
+        if (g < G - 1) {
             hipStream_t fs = fold_s(g);
             H2_HIP(hipEventRecord(ev_acc(g), st));
             H2_HIP(hipStreamWaitEvent(fs, ev_acc(g), 0));
             fold_group(g, fs);
             if (g) H2_HIP(hipStreamWaitEvent(fs, ev_chain(g - 1), 0));
             // A_g = Horner(group g) + D_(g-1);  D_g = 2^(c ns_(g+1)) A_g, an XYZZ point behind the slice sums
-            if (!(skip & 16)) hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), lds_fence ? 100 * 1024 : 0, fs, (const u32 *)(ssums + 32 * (size_t)q.w0), (int)q.ns, (int)c, ssums + 32 * (size_t)(W + g), kOutSliceSum, 1,
+            hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), gp.lds_fence ? 100 * 1024 : 0, fs, (const u32 *)(ssums + 32 * (size_t)q.w0), (int)q.ns, (int)c, ssums + 32 * (size_t)(W + g), kOutSliceSum, 1,
                                (int)(c * grp[g + 1].ns), g ? (const u32 *)(ssums + 32 * (size_t)(W + g - 1)) : (const u32 *)nullptr, 1);
             H2_HIP(hipEventRecord(ev_chain(g), fs));
         }
     }
-    if (fold_late)
-        for (int g = 0; g < G - 1; ++g) {
-            fold_group(g, st);
-            hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)(ssums + 32 * (size_t)grp[g].w0), (int)grp[g].ns, (int)c, ssums + 32 * (size_t)(W + g), kOutSliceSum, 1,
-                               (int)(c * grp[g + 1].ns), g ? (const u32 *)(ssums + 32 * (size_t)(W + g - 1)) : (const u32 *)nullptr, 1);
-        }
     fold_group(G - 1, st);
-    if (G > 1 && !fold_late) H2_HIP(hipStreamWaitEvent(st, ev_chain(G - 2), 0));
+    if (G > 1) H2_HIP(hipStreamWaitEvent(st, ev_chain(G - 2), 0));
     hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)(ssums + 32 * (size_t)grp[G - 1].w0), (int)grp[G - 1].ns, (int)c, (u32 *)a.d_out, a.out_kind,
                        mont ? 1 : 0, 0, G > 1 ? (const u32 *)(ssums + 32 * (size_t)(W + G - 2)) : (const u32 *)nullptr, 1);
     H2_HIP(hipGetLastError());

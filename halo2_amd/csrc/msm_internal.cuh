@@ -273,7 +273,7 @@ struct MsmContext {
         if (gdone) (void)hipEventDestroy(gdone);
         gdone = nullptr;
     }
-    bool attr_set = false, attr2_set = false, attr_bins_set = false, attr_grouped_set = false;
+    bool attr_set = false, attr_grouped_set = false;
     // the grouped form of a large generic multiexp (msm_generic.hip), latency form: gstream[1] carries the call's accumulates (and whatever is
     // serial with them), gstream[0] and [2] everything that runs beside them (the bases' conversion, the later groups' sorts, the groups' folds and
     // links of the Horner chain) -- three streams created back to back, so that they sit on different hardware queues whatever queue the CALLER's stream shares
@@ -291,7 +291,7 @@ struct MsmContext {
     // slices' accumulate; fork / conv / acc_a / join order the two streams
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_conv = nullptr, ev_acc_a = nullptr, ev_join = nullptr;
-    u32 lanes[2][3] = {{0, 0, 0}, {0, 0, 0}};  // resident lanes of msm_accumulate<FP / FQ, plain / GLV> on this device
+    u32 lanes[2][2] = {{0, 0}, {0, 0}};  // resident lanes of msm_accumulate<FP / FQ, 8 x 32 / M9> on this device
     // h2_msm_last_path: the form the last generic multiexp of this context took (host bookkeeping, written where the form is decided)
     struct LastPath {
         int path = 0;          // H2_MSM_PATH_*; 0: no generic multiexp yet
@@ -342,6 +342,52 @@ struct MsmArgs {
     void *const *col_outs = nullptr;
 };
 static constexpr int H2_ERR_BATCH_SHAPE = -1000;     // internal: never leaves the library
+
+// What one call of msm_launch decides before it enqueues or reserves anything (msm_plan, msm_launch.hip): the shape, which sort / accumulate /
+// fold forms the call takes, their geometries and the sizes its reservations follow from.  Plain data: no pointer into a context.
+struct MsmPlan {
+    MsmShape sh;
+    size_t m, scalars_n;  // digit columns (twice the scalars under the endomorphism split); scalars (+ blind) before the split
+    size_t all_items;     // W * m: the most entries the sorted list can hold (per column)
+    bool fold_only;       // a.fold_from: nothing but the fold of buckets summed elsewhere
+    bool add_only;        // a.add_into: a range of a chunked commit stops at its finished buckets
+    bool glv;             // generic path: k = k1 + k2 lambda, two half-length digit columns per scalar
+    bool m9;              // the accumulate runs on the carry-free layer (registered tables; generic bases converted per call)
+    bool pair;            // registered pair commit: two bucket slices, two outputs
+    u32 K;                // columns of a batched commit (1: a single multiexp)
+    bool joined;          // ... whose sorted lists form ONE list (ColStride::joined)
+    u32 tb, nblocks;      // total buckets; scan blocks over them
+    u32 T, lane_div;      // lanes of the accumulate; entries per lane it aims at
+    size_t head_slots;    // range heads parked in cx.seg9, in front of the K x tb bucket slots
+    bool use_sort2;       // two-pass sort (S2 filled), else the one-pass sort
+    Sort2 S2;
+    bool s2_bins_form;    // pass 2 in its one-launch form (a workgroup per pass-1 bin) with an LDS stage of s2_cap_entries
+    size_t s2_cap_entries, plan_words;
+    u32 max_big;          // oversized pass-2 bins handed to the chunked msm_s2_big_* kernels (0: none, their launches are skipped)
+    bool zero_in_sort;    // the one-launch pass 2 also clears the raw bucket slots
+    bool fold9;           // the fold on the carry-free layer (fold9_* kernels), else the 8 x 32 finisher and fold
+    bool wide_reduce;     // more than 2^15 buckets a slice on the 8 x 32 fold: row / column sums first
+    u32 wideS, wideNR;    // the bucket matrix of a slice: wideS columns x wideNR rows
+    bool try_grouped;     // a whole large generic multiexp: msm_generic_grouped is asked first
+    int split_k;          // != 0: slice split, the lower group's slice count
+    ColIn ci;             // column-batched commit: the per-column pointers and the distances between the per-column work areas
+    ColOut co;
+    ColStride cs;
+};
+
+// Launched from more than one place (msm_launch.hip, msm_generic.hip), defined beside the kernels they launch.
+// msm_fold.hip: the carry-free fold of a contiguous GROUP of slices [slice0, slice0 + nslices) down to its slice sums -- finish (range heads into
+// their buckets), the heavy buckets, line sums, bit planes.  heads9 / starts / buckets9 / heavy / hscratch are the group's own; lines9 / planes9 /
+// ctr / out are those of slice 0 (the group's lie slice0 slices in).  tb: the group's buckets (per column); cols: columns of a batched commit --
+// grid z of every launch, except that JOINED columns (cs.joined) are finished as one list of cols x tb buckets.
+template <int FB>
+void fold9_group(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
+                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
+                 const ColOut &co, const ColStride &cs);
+// msm_sort.hip: pass 2 of a two-pass sort in its one-launch form -- msm_s2_bins (a workgroup per pass-1 bin; it lists the bins beyond its LDS stage
+// in `big` and clears the raw bucket slots `zero9` when given) and, when max_big is non-zero, the chunked msm_s2_big_* kernels over that list
+void sort2_pass2_bins(hipStream_t st, const u32 *tagged, const uint16_t *tagged_low, const u32 *bin_start, const Sort2 &S2, u32 tb, size_t cap_entries,
+                      u32 *starts, u32 *entries, u32 *big, u32 max_big, u32 *zero9, u32 cols, const ColStride &cs);
 
 
 // msm_generic.hip: the grouped form of a large generic multiexp (unregistered bases, endomorphism split, window slices sorted and
@@ -515,19 +561,11 @@ extern template __global__ void msm_accumulate<FP, false, false>(const u32 *__re
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FP, true, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
 extern template __global__ void msm_accumulate<FP, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
 extern template __global__ void msm_accumulate<FQ, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FQ, true, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);

@@ -51,10 +51,9 @@ bool sort2_geometry(u32 stride, int c, int *lowb_out, int *lb_out, int *side_out
     // -- windows of 18 bits and more at 2^20 points, where those are too few -- in a 16-bit SIDE array next to the tagged list
     // (pass 1 writes 6 bytes per entry instead of 4; without it c = 20 meant 4096 bins and 6-entry runs)
     int lowb = std::min(31 - lb, bucket_bits - 9), side = 0;
-    static const bool side_ok = [] { const char *e = ab_env("H2_SORT_SIDE"); return !(e && atoi(e) == 0); }();      // A/B switch
     // ... only where the entry's own spare bits would leave more than 1024 bins: at 17-bit windows over 2^20 points (1024 bins
     // without it) the side array buys nothing and costs 50 % more tagged traffic (measured: 1027 against 1026-1038 M/s)
-    if (side_ok && bucket_bits - lowb > 10 && bucket_bits - 9 <= 14 && W <= 64) {
+    if (bucket_bits - lowb > 10 && bucket_bits - 9 <= 14 && W <= 64) {
         lowb = bucket_bits - 9;
         side = 1;
     }
@@ -62,8 +61,7 @@ bool sort2_geometry(u32 stride, int c, int *lowb_out, int *lb_out, int *side_out
     const size_t nh = (size_t)1 << (bucket_bits - lowb);
     // pass-1 stage in LDS: 2048 scalars' digits per workgroup, 1024 where narrower windows mean more digits per scalar (13-bit tables:
     // 20 digits) -- only for callers that ask (s1_out); the others keep the fixed 2048 they were measured with
-    static const u32 s1_env = [] { const char *e = ab_env("H2_S1_SCALARS"); int v = e ? atoi(e) : 0; return (u32)(v == 512 || v == 1024 || v == 2048 ? v : 0); }();   // sweeps only
-    u32 s1 = s1_out && s1_env ? s1_env : kS1Scalars;
+    u32 s1 = kS1Scalars;
     if (s1_out && (nh * 3 + 1 + (size_t)s1 * W) * 4 > kLdsCap) s1 = 1024;
     if ((nh * 3 + 1 + (size_t)s1 * W) * 4 > kLdsCap) return false;
     if (s1_out) *s1_out = s1;
@@ -278,54 +276,204 @@ void msm_release_workspaces() {
     }
 }
 
-template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a, hipStream_t st) {
+// The accumulate runs on the carry-free layer for registered tables (stored in M9 form: h2_bases_register) and for the generic path's endomorphism
+// split (bases converted per call); only a generic call with a blind term keeps the 8 x 32 layer.
+static bool msm_glv(const MsmArgs &a) { return !a.table && !a.d_extra_scalar && glv_applies(a.n_used); }
+static bool msm_m9(const MsmArgs &a) { return a.table || msm_glv(a); }
+
+// the fields every two-pass shape fills the same way (`scalars` per pass-1 launch, pass-2 windows over `window` buckets); the arms of msm_plan
+// set what differs: stride, extra_col, side, col0, the pair fields
+static void sort2_fill(Sort2 &S2, const MsmArgs &a, const MsmShape &sh, size_t scalars, size_t all_items, int lowb, int lb, u32 nh, u32 s1, u32 window) {
+    S2.m = (u32)scalars; S2.c = sh.c; S2.W = sh.W; S2.mont = a.form == H2_FORM_MONTGOMERY;
+    S2.extra_col = 0xFFFFFFFFu;
+    S2.lowb = lowb; S2.lb = lb; S2.nh = nh;
+    S2.s1_scalars = s1; S2.nb = sh.NB; S2.B1 = (u32)((scalars + s1 - 1) / s1);
+    S2.K2 = kS2Chunk; S2.B2 = (u32)((all_items + kS2Chunk - 1) / kS2Chunk);
+    S2.lds_window = std::min<u32>(window, 32768u);
+}
+// Every decision of one call, before anything is enqueued or reserved: no HIP call, no context.  `lanes`: the lanes of this call's accumulate
+// kernel the chip holds at once; `instrumented` (h2_profile_enable, H2_TIMELINE=1) keeps a call off the grouped form and the slice split.
+// H2_ERR_ARGS / H2_ERR_BATCH_SHAPE when the shape takes no form (or not the batched / slice-sums form it asks for).
+static int msm_plan(const MsmArgs &a, u32 lanes, bool instrumented, MsmPlan *plan) {
+    MsmPlan &p = *plan;
+    memset(&p, 0, sizeof p);
     size_t m = a.n_used + (a.d_extra_scalar ? 1 : 0);
-    int rc;
-    const bool fold_only = a.fold_from != nullptr;
-    if (m == 0 && a.add_into) return H2_OK;          // an empty range adds nothing
-    if (m == 0 && !fold_only) {
-        if ((rc = cx.ssums.reserve(128)) != H2_OK) return rc;
-        H2_HIP(hipMemsetAsync(cx.ssums.ptr, 0, 128, st));
-        hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), 1, 0, (u32 *)a.d_out, a.out_kind,
-                           a.form == H2_FORM_MONTGOMERY);
-        H2_HIP(hipGetLastError());
-        return H2_OK;
-    }
+    p.fold_only = a.fold_from != nullptr;
+    p.add_only = a.add_into && !p.fold_only;
     // generic path: every scalar is split k = k1 + k2 lambda (glv.cuh) into two half-length digit columns, i for P_i and
     // n + i for phi(P_i): as many bucket additions (2n x 9 windows against n x 16), half the doublings in the final Horner
-    const bool glv = !a.table && !a.d_extra_scalar && glv_applies(a.n_used);
-    const size_t scalars_n = m;
+    const bool glv = p.glv = msm_glv(a);
+    const bool m9 = p.m9 = msm_m9(a);
+    const size_t scalars_n = p.scalars_n = m;
     if (glv) m *= 2;
-    if (fold_only && m < 1) m = 1;                   // only the bucket geometry (c) matters to the fold
-    MsmShape sh = make_shape(m, a.c, a.table, glv);
-    const u32 K = a.ncols > 1 ? (u32)a.ncols : 1u;
-    if (K > 1 && (K > (u32)kMaxCols || !a.table || a.pair_shift >= 0 || a.add_into || fold_only || !a.col_scalars || !a.col_outs || a.n_used == 0))
+    if (p.fold_only && m < 1) m = 1;                   // only the bucket geometry (c) matters to the fold
+    p.m = m;
+    MsmShape &sh = p.sh;
+    sh = make_shape(m, a.c, a.table, glv);
+    const u32 K = p.K = a.ncols > 1 ? (u32)a.ncols : 1u;
+    if (K > 1 && (K > (u32)kMaxCols || !a.table || a.pair_shift >= 0 || a.add_into || p.fold_only || !a.col_scalars || !a.col_outs || a.n_used == 0))
         return H2_ERR_BATCH_SHAPE;
-    const bool pair = a.table && a.pair_shift >= 0;
-    if (pair) {                       // one bucket slice per output
+    p.pair = a.table && a.pair_shift >= 0;
+    if (p.pair) {                     // one bucket slice per output
         sh.slices = 2;
         sh.total_buckets = 2 * sh.NB;
     }
-    const u32 tb = sh.total_buckets, segs = tb / kSeg;
-    const size_t all_items = (size_t)sh.W * m;
+    const u32 tb = p.tb = sh.total_buckets;
+    const size_t all_items = p.all_items = (size_t)sh.W * m;
     if (all_items >= ((size_t)1 << 31)) return H2_ERR_ARGS;  // entry = table index | sign << 31
-    const u32 nblocks = (tb + kScanBlock - 1) / kScanBlock;
+    p.nblocks = (tb + kScanBlock - 1) / kScanBlock;
+    // one round of resident lanes; small problems use fewer lanes so a range keeps >= 16 entries
+    // a lane fraction < 1 (h2_set_option) leaves wave slots free so that the latency-bound sort / reduce kernels
+    // of a commit running on ANOTHER stream can overlap this kernel (independent column commits)
+    const double fraction = a.lane_fraction > 0.0 ? a.lane_fraction : g_lane_fraction.load();
+    const u32 usable = std::max(256u, (u32)(lanes * fraction) / 256u * 256u);
+    // entries per lane of the accumulate: 16 for full-size columns; small commits are chains of latency-bound kernels and run
+    // shorter with more, shorter lanes (one registered commit at 2^11 .. 2^15 points: 3-7 % faster at 8; H2_MSM_DIV: sweeps only)
+    static const u32 env_div = [] { const char *e = ab_env("H2_MSM_DIV"); int v = e ? atoi(e) : 0; return (u32)(v >= 1 && v <= 64 ? v : 0); }();
+    p.lane_div = env_div ? env_div : (all_items < ((size_t)1 << 20) ? 8u : 16u);
+    // Column-batched commits are JOINED (ColStride::joined) unless H2_BATCH_JOIN=0: the K sorted lists form one, which ONE launch of
+    // msm_accumulate cuts into equal ranges -- the chip is tiled exactly as by a single commit (a launch per column leaves its last
+    // round of workgroups ragged, and K of them next to each other share CUs unevenly), and the finisher meets T range heads per
+    // batch instead of per column.
+    static const bool join_env = [] { const char *e = ab_env("H2_BATCH_JOIN"); return !(e && e[0] == '0'); }();
+    const bool joined = p.joined = K > 1 && join_env;
+    const u32 T = p.T = (u32)std::min<size_t>(usable, std::max<size_t>(256, ((joined ? K : 1) * all_items / p.lane_div + 255) / 256 * 256));
+    p.head_slots = joined ? (size_t)T : (size_t)T * K;
+    // two-pass sort (registered path): always for windows beyond 16 bits, else for large bucket counts
+    Sort2 &S2 = p.S2;
+    S2.pair_shift = -1; S2.run_lanes = 16;
+    if (p.pair) {
+        // key = side * NB + bucket over both slices (the generic path's multi-slice geometry), entry = table index
+        int lb = 0, lowb = 0;
+        u32 nh = 0, s1 = 0;
+        if (!pair_geometry(m, sh.c, a.stride, &lowb, &lb, &nh, &s1)) return H2_ERR_ARGS;
+        p.use_sort2 = true;
+        sort2_fill(S2, a, sh, m, all_items, lowb, lb, nh, s1, tb);
+        S2.stride = a.stride; S2.pair_shift = a.pair_shift; S2.pair_n = a.pair_n;
+    } else if (a.table && (sh.c > kMaxC || (sh.NB >= 4096 && (m >= 8192 || K > 1)))) {
+        // (a column-batched commit exists in the two-pass form only, so it takes it from 13-bit tables on whatever the column length:
+        // eight 2^12-point columns in one launch set are 0.3 ms against 0.9 ms for eight chains of one-pass sorts)
+        int lowb = 0, lb = 0, side = 0;
+        u32 s1 = kS1Scalars;
+        if (sort2_geometry(a.stride, sh.c, &lowb, &lb, &side, &s1)) {
+            p.use_sort2 = true;
+            sort2_fill(S2, a, sh, m, all_items, lowb, lb, sh.NB >> lowb, s1, sh.NB);
+            S2.stride = a.stride; S2.side = side; S2.col0 = a.col0;
+            if (a.d_extra_scalar) S2.extra_col = a.extra_col;
+        }
+    } else if (glv && scalars_n >= 65536) {
+        // generic path, large: sort key = window * NB + bucket over all slices, entry = digit column (< 2 * scalars)
+        int lb = 0, kb = 0;
+        while (((u64)(m - 1) >> lb) != 0) ++lb;
+        while (((u64)(tb - 1) >> kb) != 0) ++kb;
+        // bins of ~16 K entries (kb - 11 bucket bits per bin: 1152 bins for 9 slices of 2^15 buckets), so that pass 2 is the
+        // one-launch form with a bin per workgroup in LDS (9 bits = the chunked pass 2 of round 2).
+        // Up to 2^19 scalars only: the carry slice of the split (the window above the top of a 128-bit half) puts ~n / 2 entries
+        // into ONE bucket, and a bin that large was scattered by a single workgroup (2^19: sort 0.28 -> 0.16 ms; 2^20: 0.30 -> 0.61).
+        // With the oversized-bin kernels (msm_s2_big_*) that bin is chunked over 64 workgroups: 2^20 takes the one-launch form with
+        // 10 bits (1.83 -> 1.71 ms on one box; 11 bits 1.80, 12 bits 1.83); from 2^21 the forms are equal within 1 %.
+        const int bin_bits = scalars_n <= ((size_t)1 << 19) ? 11 : scalars_n <= ((size_t)1 << 20) ? 10 : 9;
+        const int lowb = std::min(31 - lb, std::max(1, kb - bin_bits));
+        const u32 nh = (tb + (1u << lowb) - 1) >> lowb;
+        const u32 s1 = 1024;
+        const bool fits = ((size_t)nh * 3 + 1 + (size_t)s1 * 2 * sh.W) * 4 <= kLdsCap;
+        if (lowb >= 1 && nh <= 4096 && fits) {
+            p.use_sort2 = true;
+            sort2_fill(S2, a, sh, scalars_n, all_items, lowb, lb, nh, s1, tb);
+        }
+    }
+    if (sh.c > kMaxC && !p.use_sort2) return H2_ERR_ARGS;   // choose_c only picks wide windows the two-pass sort can take
+    if (K > 1 && !p.use_sort2) return H2_ERR_BATCH_SHAPE;
+    p.wide_reduce = sh.NB > 32768u;                       // implies the registered path (one slice)
+    // the fold on the carry-free layer (fold9_* kernels: registered tables from 16-bit windows, paired commits, and the window
+    // slices of a large generic multiexp); a range of a chunked commit hands finished buckets on in the reference's form
+    // (add_into), so it keeps the 8 x 32 finisher
+    p.fold9 = sh.NB >= 128 && sh.slices <= 16 && m9 && !a.add_into && !p.fold_only;      // (16: arrival counters of fold9_planes)
+    if (K > 1 && !p.fold9) return H2_ERR_BATCH_SHAPE;
+    if (a.slice_sums_only && !(p.fold9 && glv)) return H2_ERR_BATCH_SHAPE;
+    // The grouped form (round 6, msm_generic.hip; generic multiexps beyond 2^18 points): the endomorphism split once, the window slices
+    // sorted / accumulated / folded in groups, upper slices first.  It answers H2_ERR_BATCH_SHAPE before enqueueing anything when the shape
+    // is not its own; round 5's slice split below then still applies (and is the A/B arm, H2_GENERIC_GROUPED=0 in the laboratory build).
+    p.try_grouped = glv && p.fold9 && a.phase == 0 && !a.slice_sums_only && K == 1 && !instrumented;
+    // Slice split (round 5; generic multiexps from 2^19 points): the sorted list is ordered by (slice, bucket), so the upper slices
+    // [split_k, slices) and the lower ones [0, split_k) are two contiguous halves of it.  They are accumulated one after the other on
+    // `st`; as soon as the UPPER group is in its buckets its fold and its Horner chain -- (slices - 1) c ~ 128 dependent doublings, 0.25 ms
+    // on one quad of lanes, which used to follow the whole accumulate -- run on a side stream beside the lower group's accumulate and
+    // fold.  What is left behind the accumulate: the lower group's fold, (split_k - 1) c doublings and one addition.  The bases'
+    // conversion to M9 form runs on the side stream beside the sort.  H2_GENERIC_SPLIT=0: off (A/B); = k: force the lower group's size.
+    static const int split_env = [] { const char *e = ab_env("H2_GENERIC_SPLIT"); return e ? atoi(e) : -1; }();
+    if (p.try_grouped && sh.slices >= 6 && split_env != 0) {
+        if (split_env > 0) p.split_k = std::min<int>(split_env, (int)sh.slices - 2);
+        else if (scalars_n >= ((size_t)1 << 19)) p.split_k = 3;
+    }
+    if (p.split_k) p.head_slots = 2 * (size_t)T;             // each group's T range heads
+    // pass 2 of the two-pass sort in its one-launch form (a workgroup per pass-1 bin; the chunked form otherwise)?  Decided here, before
+    // anything is launched, because a column-batched commit exists in that form only.
+    if (p.use_sort2) {
+        const size_t nbk = (size_t)1 << S2.lowb;
+        // LDS stage: the average bin + 25 % (two workgroups per CU where that fits: 2^20 scalars at 17 bits, 15 K-entry bins), at
+        // most what one workgroup can have; a bin beyond its stage takes the direct-scatter branch.
+        const size_t cap_max = nbk * 8 + 64 < kLdsCap ? (kLdsCap - nbk * 8) / 4 : 0;
+        p.s2_cap_entries = std::min(cap_max, std::max<size_t>(4096, all_items / S2.nh * 5 / 4 + 1024));
+        const size_t nbins = ((size_t)tb + nbk - 1) >> S2.lowb;
+        p.s2_bins_form = S2.lowb <= 12 && nbins == S2.nh && p.s2_cap_entries && all_items / S2.nh <= p.s2_cap_entries * 9 / 10;
+        p.plan_words = (size_t)S2.nh * 2 + 1 + (size_t)S2.B2 * 2 + 1 +
+                       std::max<size_t>(((size_t)S2.nh + S2.B2 + 1) << S2.lowb, 64 + (((size_t)kMaxBig * (kBigChunks + 1)) << S2.lowb));
+        p.plan_words = (p.plan_words + 3) & ~(size_t)3;
+    }
+    if (K > 1 && !p.s2_bins_form) return H2_ERR_BATCH_SHAPE;
+    if (p.wide_reduce || p.fold9) {
+        p.wideS = 1u << ((sh.c - 1) / 2);
+        p.wideNR = sh.NB / p.wideS;
+    }
+    // the one-launch pass 2 also clears the raw bucket slots (its workgroups own disjoint bucket ranges)
+    p.zero_in_sort = m9 && p.use_sort2 && p.s2_bins_form && !p.fold_only;
+    // oversized pass-2 bins (degenerate columns) go to the chunked msm_s2_big_* kernels only where a bin can be large enough for
+    // that to matter: below 3 * 2^20 entries per column (2^18 scalars) the bin's own workgroup streams it (<= 2^17 entries: tens of
+    // microseconds, and only for such columns), and every commit saves three launches that would find an empty list
+    p.max_big = all_items >= ((size_t)3 << 20) ? kMaxBig : 0u;
+    // column-batched commit: the per-column pointers and the distances between the per-column work areas (32-bit words)
+    if (K > 1) {
+        for (u32 k = 0; k < K; ++k) {
+            p.ci.scalars[k] = (const u32 *)a.col_scalars[k];
+            p.ci.blinds[k] = a.col_blinds ? (const u32 *)a.col_blinds[k] : nullptr;
+            p.co.out[k] = (u32 *)a.col_outs[k];
+            if (!p.ci.scalars[k] || !p.co.out[k] || (a.d_extra_scalar && !p.ci.blinds[k])) return H2_ERR_ARGS;
+        }
+        ColStride &cs = p.cs;
+        cs.hist = (u32)((size_t)S2.B1 * S2.nh);
+        cs.plan = (u32)p.plan_words;
+        cs.items = (u32)all_items;
+        cs.entries = joined ? 0u : (u32)all_items;
+        cs.joined = joined ? S2.nh : 0u;
+        cs.starts = joined ? tb : tb + 2;
+        cs.heavy = kMaxHeavy + 2;
+        cs.hscratch = kMaxHeavy * kHeavyBlocks * 36;
+        cs.heads = T * 36;
+        cs.buckets = tb * 36;
+        cs.lines = sh.slices * (p.wideS + p.wideNR) * 36;
+        cs.planes = sh.slices * 32 * 36;
+        cs.ctr = 16;
+    }
+    return H2_OK;
+}
+// ---- context set-up: the LDS attributes of the sort kernels, once per (device, stream) context (the attribute is per device), and how many
+// lanes of this call's accumulate kernel the chip holds at once
+template <int FB> static int msm_context_setup(MsmContext &cx, bool m9, u32 *lanes_out) {
     if (!cx.attr_set) {
         H2_HIP(hipFuncSetAttribute((const void *)msm_count, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
         H2_HIP(hipFuncSetAttribute((const void *)msm_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
+        for (const void *k : {(const void *)msm_s2_count, (const void *)msm_s2_scatter, (const void *)msm_s2_bins, (const void *)msm_s1_scatter<FP, false>,
+                              (const void *)msm_s1_scatter<FQ, false>, (const void *)msm_s1_scatter<FP, true>, (const void *)msm_s1_scatter<FQ, true>})
+            H2_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
         cx.attr_set = true;
     }
-    // registered tables are stored in M9 form (h2_bases_register); the generic path converts its bases per call (below)
-    static const bool glv_on_fe9 = [] { const char *e = ab_env("H2_GENERIC_FE9"); return !(e && atoi(e) == 0); }();
-    const bool m9 = (a.table && !glv) || (glv && glv_on_fe9);
-    u32 &lanes = cx.lanes[FB][m9 ? 2 : glv ? 1 : 0];
-    if (!lanes) {  // how many lanes of the accumulate kernel the chip holds at once
+    u32 &lanes = cx.lanes[FB][m9 ? 1 : 0];
+    if (!lanes) {
         int dev = 0, cus = 0, per_cu = 0;
         H2_HIP(hipGetDevice(&dev));
         H2_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         if (m9) H2_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)msm_accumulate<FB, false, true>, 256, 0));
-        else if (glv) H2_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)msm_accumulate<FB, true>, 256, 0));
-        else if (false) H2_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)msm_accumulate<FB, false, true>, 256, 0));
         else H2_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)msm_accumulate<FB, false>, 256, 0));
         // the M9 accumulate is sized for H2_ACC9_WAVES workgroups per CU even where its register count would let a third one in:
         // the wave slots and registers left over are what the sort / fold kernels of commits on OTHER streams run in
@@ -334,559 +482,347 @@ template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a
         if (m9) per_cu = std::min(per_cu, acc_waves);
         lanes = (u32)cus * (u32)std::max(per_cu, 1) * 256u;
     }
-    // one round of resident lanes; small problems use fewer lanes so a range keeps >= 16 entries
-    // a lane fraction < 1 (h2_set_option) leaves wave slots free so that the latency-bound sort / reduce kernels
-    // of a commit running on ANOTHER stream can overlap this kernel (independent column commits)
-    const double fraction = a.lane_fraction > 0.0 ? a.lane_fraction : g_lane_fraction.load();
-    // H2_ACC_OVERSUB = k (sweeps only): k times as many, k times shorter lanes than the chip holds at once -- workgroups then enter as
-    // slots free up, which evens out a launch that found some CUs half taken by other streams' sort / fold kernels, at the price of
-    // k times the range heads for the finisher
-    static const u32 oversub = [] { const char *e = ab_env("H2_ACC_OVERSUB"); int v = e ? atoi(e) : 0; return (u32)(v >= 1 && v <= 8 ? v : 1); }();
-    const u32 usable = std::max(256u, (u32)(lanes * fraction) / 256u * 256u) * (a.table ? oversub : 1u);
-    // entries per lane of the accumulate: 16 for full-size columns; small commits are chains of latency-bound kernels and run
-    // shorter with more, shorter lanes (one registered commit at 2^11 .. 2^15 points: 3-7 % faster at 8; H2_MSM_DIV: sweeps only)
-    static const u32 env_div = [] { const char *e = ab_env("H2_MSM_DIV"); int v = e ? atoi(e) : 0; return (u32)(v >= 1 && v <= 64 ? v : 0); }();
-    const u32 lane_div = env_div ? env_div : (all_items < ((size_t)1 << 20) ? 8u : 16u);
-    // Column-batched commits are JOINED (ColStride::joined) unless H2_BATCH_JOIN=0: the K sorted lists form one, which ONE launch of
-    // msm_accumulate cuts into equal ranges -- the chip is tiled exactly as by a single commit (a launch per column leaves its last
-    // round of workgroups ragged, and K of them next to each other share CUs unevenly), and the finisher meets T range heads per
-    // batch instead of per column.
-    static const bool join_env = [] { const char *e = ab_env("H2_BATCH_JOIN"); return !(e && e[0] == '0'); }();
-    const bool joined = K > 1 && join_env;
-    u32 T = (u32)std::min<size_t>(usable, std::max<size_t>(256, ((joined ? K : 1) * all_items / lane_div + 255) / 256 * 256));
-    size_t head_slots = joined ? (size_t)T : (size_t)T * K;            // range heads parked in cx.seg9, in front of the K x tb bucket slots
-    const u32 max_heavy = kMaxHeavy;
-    // two-pass sort (registered path): always for windows beyond 16 bits, else for large bucket counts
-    Sort2 S2;
-    memset(&S2, 0, sizeof S2);
-    S2.pair_shift = -1;
-    static const u32 run_lanes_env = [] { const char *e = ab_env("H2_S1_RUN_LANES"); int v = e ? atoi(e) : 0; return (u32)(v == 8 || v == 16 || v == 32 || v == 64 ? v : 16); }();
-    S2.run_lanes = run_lanes_env;
-    bool use_sort2 = false;
-    if (pair) {
-        // key = side * NB + bucket over both slices (the generic path's multi-slice geometry), entry = table index
-        int lb = 0, lowb = 0;
-        u32 nh = 0, s1 = 0;
-        if (!pair_geometry(m, sh.c, a.stride, &lowb, &lb, &nh, &s1)) return H2_ERR_ARGS;
-        use_sort2 = true;
-        S2.m = (u32)m; S2.c = sh.c; S2.W = sh.W; S2.mont = a.form == H2_FORM_MONTGOMERY;
-        S2.stride = a.stride; S2.extra_col = 0xFFFFFFFFu;
-        S2.lowb = lowb; S2.lb = lb; S2.nh = nh;
-        S2.s1_scalars = s1;
-        S2.nb = sh.NB;
-        S2.B1 = (u32)((m + s1 - 1) / s1);
-        S2.K2 = kS2Chunk;
-        S2.B2 = (u32)((all_items + kS2Chunk - 1) / kS2Chunk);
-        S2.lds_window = std::min<u32>(tb, 32768u);
-        S2.pair_shift = a.pair_shift;
-        S2.pair_n = a.pair_n;
-    } else if (a.table && (sh.c > kMaxC || (sh.NB >= 4096 && (m >= 8192 || K > 1)))) {
-        // (a column-batched commit exists in the two-pass form only, so it takes it from 13-bit tables on whatever the column length:
-        // eight 2^12-point columns in one launch set are 0.3 ms against 0.9 ms for eight chains of one-pass sorts)
-        static const int force_old = [] { const char *e = ab_env("H2_MSM_SORT"); return e && atoi(e) == 1 ? 1 : 0; }();
-        int lowb = 0, lb = 0, side = 0;
-        u32 s1 = kS1Scalars;
-        if (sort2_geometry(a.stride, sh.c, &lowb, &lb, &side, &s1) && (sh.c > kMaxC || !force_old)) {
-            use_sort2 = true;
-            S2.m = (u32)m; S2.c = sh.c; S2.W = sh.W; S2.mont = a.form == H2_FORM_MONTGOMERY;
-            S2.stride = a.stride; S2.extra_col = a.d_extra_scalar ? a.extra_col : 0xFFFFFFFFu;
-            S2.lowb = lowb; S2.lb = lb; S2.nh = sh.NB >> lowb;
-            S2.side = side;
-            S2.s1_scalars = s1;
-            S2.nb = sh.NB;
-            S2.B1 = (u32)((m + s1 - 1) / s1);
-            S2.K2 = kS2Chunk;
-            S2.B2 = (u32)((all_items + kS2Chunk - 1) / kS2Chunk);
-            S2.lds_window = std::min<u32>(sh.NB, 32768u);
-            S2.col0 = a.col0;
-        }
-    } else if (glv && scalars_n >= 65536) {
-        // generic path, large: sort key = window * NB + bucket over all slices, entry = digit column (< 2 * scalars)
-        static const int force_old = [] { const char *e = ab_env("H2_MSM_SORT"); return e && atoi(e) == 1 ? 1 : 0; }();
-        int lb = 0, kb = 0;
-        while (((u64)(m - 1) >> lb) != 0) ++lb;
-        while (((u64)(tb - 1) >> kb) != 0) ++kb;
-        // bins of ~16 K entries (kb - 11 bucket bits per bin: 1152 bins for 9 slices of 2^15 buckets), so that pass 2 is the
-        // one-launch form with a bin per workgroup in LDS; H2_GLV_BIN_BITS: sweeps only (9 = the chunked pass 2 of round 2)
-        // Up to 2^19 scalars only: the carry slice of the split (the window above the top of a 128-bit half) puts ~n / 2 entries
-        // into ONE bucket, and a bin that large was scattered by a single workgroup (2^19: sort 0.28 -> 0.16 ms; 2^20: 0.30 -> 0.61).
-        // With the oversized-bin kernels (msm_s2_big_*) that bin is chunked over 64 workgroups: 2^20 takes the one-launch form with
-        // 10 bits (1.83 -> 1.71 ms on one box; 11 bits 1.80, 12 bits 1.83); from 2^21 the forms are equal within 1 %.
-        static const int glv_bin_bits = [] { const char *e = ab_env("H2_GLV_BIN_BITS"); int v = e ? atoi(e) : 0; return v >= 8 && v <= 12 ? v : 0; }();
-        const int bin_bits = glv_bin_bits ? glv_bin_bits : (scalars_n <= ((size_t)1 << 19) ? 11 : scalars_n <= ((size_t)1 << 20) ? 10 : 9);
-        const int lowb = std::min(31 - lb, std::max(1, kb - bin_bits));
-        const u32 nh = (tb + (1u << lowb) - 1) >> lowb;
-        const u32 s1 = 1024;
-        const bool fits = ((size_t)nh * 3 + 1 + (size_t)s1 * 2 * sh.W) * 4 <= kLdsCap;
-        if (!force_old && lowb >= 1 && nh <= 4096 && fits) {
-            use_sort2 = true;
-            S2.m = (u32)scalars_n; S2.c = sh.c; S2.W = sh.W; S2.mont = a.form == H2_FORM_MONTGOMERY;
-            S2.stride = 0; S2.extra_col = 0xFFFFFFFFu;
-            S2.lowb = lowb; S2.lb = lb; S2.nh = nh;
-            S2.s1_scalars = s1;
-            S2.nb = sh.NB;
-            S2.B1 = (u32)((scalars_n + s1 - 1) / s1);
-            S2.K2 = kS2Chunk;
-            S2.B2 = (u32)((all_items + kS2Chunk - 1) / kS2Chunk);
-            S2.lds_window = std::min<u32>(tb, 32768u);
-        }
-    }
-    if (sh.c > kMaxC && !use_sort2) return H2_ERR_ARGS;   // choose_c only picks wide windows the two-pass sort can take
-    if (K > 1 && !use_sort2) return H2_ERR_BATCH_SHAPE;
-    const bool wide_reduce = sh.NB > 32768u;              // implies the registered path (one slice)
-    static const bool fold9_on = [] { const char *e = ab_env("H2_FOLD9"); return !(e && atoi(e) == 0); }();     // A/B switch
-    // the fold on the carry-free layer (fold9_* kernels: registered tables from 16-bit windows, paired commits, and the window
-    // slices of a large generic multiexp); a range of a chunked commit hands finished buckets on in the reference's form
-    // (add_into), so it keeps the 8 x 32 finisher
-    static const u32 fold9_min_nb = [] { const char *e = ab_env("H2_FOLD9_MIN_NB"); int v = e ? atoi(e) : 0; return (u32)(v >= 64 ? v : 128); }();
-    const bool fold9 = fold9_on && sh.NB >= fold9_min_nb && sh.slices <= 16 && m9 && !a.add_into && !fold_only;      // (16: arrival counters of fold9_planes)
-    if (K > 1 && !fold9) return H2_ERR_BATCH_SHAPE;
-    if (a.slice_sums_only && !(fold9 && glv)) return H2_ERR_BATCH_SHAPE;
-    // Slice split (round 5; generic multiexps from 2^19 points): the sorted list is ordered by (slice, bucket), so the upper slices
-    // [split_k, slices) and the lower ones [0, split_k) are two contiguous halves of it.  They are accumulated one after the other on
-    // `st`; as soon as the UPPER group is in its buckets its fold and its Horner chain -- (slices - 1) c ~ 128 dependent doublings, 0.25 ms
-    // on one quad of lanes, which used to follow the whole accumulate -- run on a side stream beside the lower group's accumulate and
-    // fold.  What is left behind the accumulate: the lower group's fold, (split_k - 1) c doublings and one addition.  The bases'
-    // conversion to M9 form runs on the side stream beside the sort.  H2_GENERIC_SPLIT=0: off (A/B); = k: force the lower group's size.
-    static const int split_env = [] { const char *e = ab_env("H2_GENERIC_SPLIT"); return e ? atoi(e) : -1; }();
-    // The grouped form (round 6, msm_generic.hip; generic multiexps beyond 2^18 points): the endomorphism split once, the window slices
-    // sorted / accumulated / folded in groups, upper slices first.  It answers H2_ERR_BATCH_SHAPE before enqueueing anything when the shape
-    // is not its own; round 5's slice split below then still applies (and is the A/B arm, H2_GENERIC_GROUPED=0 in the laboratory build).
-    if (glv && fold9 && m9 && a.phase == 0 && !a.slice_sums_only && K == 1 && !prof_enabled() && !timeline_on()) {
-        rc = msm_generic_grouped<FB, FS>(cx, a, sh, scalars_n, lanes, st);
-        if (rc != H2_ERR_BATCH_SHAPE) return rc;
-    }
-    int split_k = 0;
-    if (glv && fold9 && m9 && a.phase == 0 && !a.slice_sums_only && K == 1 && sh.slices >= 6 && split_env != 0 && !prof_enabled() && !timeline_on()) {
-        if (split_env > 0) split_k = std::min<int>(split_env, (int)sh.slices - 2);
-        else if (scalars_n >= ((size_t)1 << 19)) split_k = 3;
-    }
-    if (split_k) head_slots = 2 * (size_t)T;               // each group's T range heads
-    if (!a.table && a.phase == 0 && !fold_only && !a.add_into && !a.slice_sums_only) {      // a whole generic multiexp (h2_msm_last_path)
-        cx.last.path = split_k ? H2_MSM_PATH_SLICE_SPLIT : use_sort2 ? H2_MSM_PATH_TWO_PASS : H2_MSM_PATH_ONE_PASS;
-        cx.last.groups = split_k ? 2 : 1;
-        cx.last.acc_lanes = T;
-        cx.last.c = sh.c;
-    }
-    // pass 2 of the two-pass sort in its one-launch form (a workgroup per pass-1 bin)?  Decided here, before anything is launched,
-    // because a column-batched commit exists in that form only.
-    bool s2_bins_form = false;
-    size_t s2_cap_entries = 0;
-    if (use_sort2) {
-        static const bool bins_on = [] { const char *e = ab_env("H2_S2_BINS"); return !(e && atoi(e) == 0); }();
-        const size_t nbk = (size_t)1 << S2.lowb;
-        // LDS stage: the average bin + 25 % (two workgroups per CU where that fits: 2^20 scalars at 17 bits, 15 K-entry bins), at
-        // most what one workgroup can have; a bin beyond its stage takes the direct-scatter branch.  H2_S2_CAP: sweeps only.
-        const size_t cap_max = nbk * 8 + 64 < kLdsCap ? (kLdsCap - nbk * 8) / 4 : 0;
-        static const size_t cap_env = [] { const char *e = ab_env("H2_S2_CAP"); return e ? (size_t)atol(e) : (size_t)0; }();
-        s2_cap_entries = std::min(cap_max, cap_env ? cap_env : std::max<size_t>(4096, all_items / S2.nh * 5 / 4 + 1024));
-        const size_t nbins = ((size_t)tb + nbk - 1) >> S2.lowb;
-        s2_bins_form = bins_on && S2.lowb <= 12 && nbins == S2.nh && s2_cap_entries && all_items / S2.nh <= s2_cap_entries * 9 / 10;
-    }
-    if (K > 1 && !s2_bins_form) return H2_ERR_BATCH_SHAPE;
-    u32 wideS = 0, wideNR = 0;
-    if (wide_reduce || fold9) {
-        const int bb = sh.c - 1;
-        wideS = 1u << (bb / 2);
-        wideNR = sh.NB / wideS;
-    }
-    size_t plan_words = 0;
-    if (use_sort2) {
-        if (!cx.attr2_set) {
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s2_count, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s2_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s1_scatter<FP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s1_scatter<FQ, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s1_scatter<FP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            H2_HIP(hipFuncSetAttribute((const void *)msm_s1_scatter<FQ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-            cx.attr2_set = true;
-        }
+    *lanes_out = lanes;
+    return H2_OK;
+}
+// Every workspace of the call, in front of its first launch: a reservation that grows frees and synchronises (and invalidates the graphs
+// msm_host.hip captured).  The sizes follow from the plan alone, so a phase-2 / 3 / 4 call finds what its phase-1 call reserved.
+static int msm_reserve(MsmContext &cx, const MsmPlan &p, hipStream_t st) {
+    const MsmShape &sh = p.sh;
+    const Sort2 &S2 = p.S2;
+    const u32 K = p.K, tb = p.tb;
+    const size_t groups = p.split_k ? 2 : K;                 // heavy-bucket lists: one per column, or one per group of a slice split
+    int rc;
+    if (p.use_sort2) {
         if ((rc = cx.hist.reserve((size_t)K * S2.B1 * S2.nh * 4)) != H2_OK) return rc;
-        if ((rc = cx.tagged.reserve((size_t)K * all_items * 4)) != H2_OK) return rc;
-        if (S2.side && (rc = cx.tagged_low.reserve((size_t)K * all_items * 2 + 64)) != H2_OK) return rc;
-        plan_words = (size_t)S2.nh * 2 + 1 + (size_t)S2.B2 * 2 + 1 +
-                     std::max<size_t>(((size_t)S2.nh + S2.B2 + 1) << S2.lowb, 64 + (((size_t)kMaxBig * (kBigChunks + 1)) << S2.lowb));
-        plan_words = (plan_words + 3) & ~(size_t)3;
-        if ((rc = cx.plan.reserve((size_t)K * plan_words * 4)) != H2_OK) return rc;
+        if ((rc = cx.tagged.reserve((size_t)K * p.all_items * 4)) != H2_OK) return rc;
+        if (S2.side && (rc = cx.tagged_low.reserve((size_t)K * p.all_items * 2 + 64)) != H2_OK) return rc;
+        if ((rc = cx.plan.reserve((size_t)K * p.plan_words * 4)) != H2_OK) return rc;
     } else {
-        if ((rc = cx.digits.reserve(all_items * 2)) != H2_OK) return rc;
+        if ((rc = cx.digits.reserve(p.all_items * 2)) != H2_OK) return rc;
         if ((rc = cx.hist.reserve((size_t)sh.slices * sh.B * sh.NB * 4)) != H2_OK) return rc;
     }
     if ((rc = cx.counts.reserve((size_t)tb * 4)) != H2_OK) return rc;
     if ((rc = cx.starts.reserve((size_t)K * (tb + 2) * 4)) != H2_OK) return rc;
-    if ((rc = cx.bsums.reserve((size_t)(nblocks + 4) * 4)) != H2_OK) return rc;
-    if ((rc = cx.entries.reserve((size_t)K * all_items * 4)) != H2_OK) return rc;
-    if ((rc = cx.heads.reserve((size_t)std::max<size_t>(T, (size_t)sh.slices * 32) * 128)) != H2_OK) return rc;
-    if ((rc = cx.heavy.reserve((size_t)(split_k ? 2 : K) * (max_heavy + 2) * 4)) != H2_OK) return rc;
-    if ((rc = cx.hscratch.reserve((size_t)(split_k ? 2 : K) * max_heavy * kHeavyBlocks * 144)) != H2_OK) return rc;
+    if ((rc = cx.bsums.reserve((size_t)(p.nblocks + 4) * 4)) != H2_OK) return rc;
+    if ((rc = cx.entries.reserve((size_t)K * p.all_items * 4)) != H2_OK) return rc;
+    if ((rc = cx.heads.reserve((size_t)std::max<size_t>(p.T, (size_t)sh.slices * 32) * 128)) != H2_OK) return rc;
+    if ((rc = cx.heavy.reserve(groups * (kMaxHeavy + 2) * 4)) != H2_OK) return rc;
+    if ((rc = cx.hscratch.reserve(groups * kMaxHeavy * kHeavyBlocks * 144)) != H2_OK) return rc;
     if ((rc = cx.buckets.reserve((size_t)tb * 128)) != H2_OK) return rc;
-    if ((rc = cx.partial.reserve(std::max(wide_reduce ? ((size_t)2 * wideNR / kSeg + 2 * wideNR) * 128 : (size_t)segs * 128,
-                                          fold9 ? (size_t)K * sh.slices * (wideS + wideNR + 32) * 144 : (size_t)0))) != H2_OK) return rc;
-    if (fold9 && cx.fold_ctr.cap < (size_t)K * 64) {      // fold9_planes' arrival counters (16 words per column): zero once, every launch leaves them at zero
+    if ((rc = cx.partial.reserve(std::max(p.wide_reduce ? ((size_t)2 * p.wideNR / kSeg + 2 * p.wideNR) * 128 : (size_t)(tb / kSeg) * 128,
+                                          p.fold9 ? (size_t)K * sh.slices * (p.wideS + p.wideNR + 32) * 144 : (size_t)0))) != H2_OK) return rc;
+    if (p.fold9 && cx.fold_ctr.cap < (size_t)K * 64) {      // fold9_planes' arrival counters (16 words per column): zero once, every launch leaves them at zero
         if ((rc = cx.fold_ctr.reserve((size_t)kMaxCols * 64)) != H2_OK) return rc;
         H2_HIP(hipMemsetAsync(cx.fold_ctr.ptr, 0, (size_t)kMaxCols * 64, st));
     }
-    // column-batched commit: the per-column pointers and the distances between the per-column work areas (32-bit words)
-    ColIn ci;
-    ColOut co;
-    ColStride cs;
-    memset(&ci, 0, sizeof ci);
-    memset(&co, 0, sizeof co);
-    memset(&cs, 0, sizeof cs);
-    if (K > 1) {
-        for (u32 k = 0; k < K; ++k) {
-            ci.scalars[k] = (const u32 *)a.col_scalars[k];
-            ci.blinds[k] = a.col_blinds ? (const u32 *)a.col_blinds[k] : nullptr;
-            co.out[k] = (u32 *)a.col_outs[k];
-            if (!ci.scalars[k] || !co.out[k] || (a.d_extra_scalar && !ci.blinds[k])) return H2_ERR_ARGS;
-        }
-        cs.hist = (u32)((size_t)S2.B1 * S2.nh);
-        cs.plan = (u32)plan_words;
-        cs.items = (u32)all_items;
-        cs.entries = joined ? 0u : (u32)all_items;
-        cs.joined = joined ? S2.nh : 0u;
-        cs.starts = joined ? tb : tb + 2;
-        cs.heavy = max_heavy + 2;
-        cs.hscratch = max_heavy * kHeavyBlocks * 36;
-        cs.heads = T * 36;
-        cs.buckets = tb * 36;
-        cs.lines = sh.slices * (wideS + wideNR) * 36;
-        cs.planes = sh.slices * 32 * 36;
-        cs.ctr = 16;
-    }
     if ((rc = cx.ssums.reserve((size_t)(std::max<u32>(sh.slices, 2) + 1) * 128)) != H2_OK) return rc;      // (+ 1: the upper group's weighted sum of a slice split)
-    if (split_k && !cx.side) {
+    if (p.m9 && !p.fold_only) {
+        if (p.glv && (rc = cx.bases9.reserve((size_t)p.scalars_n * 128 + 64)) != H2_OK) return rc;
+        // raw M9 segments: the heads of the T ranges of every column, then the bucket slots of every column
+        if ((rc = cx.seg9.reserve((p.head_slots + (size_t)K * tb) * 144)) != H2_OK) return rc;
+    }
+    if (p.split_k && !cx.side) {
         H2_HIP(hipStreamCreateWithFlags(&cx.side, hipStreamNonBlocking));
         for (hipEvent_t *e : {&cx.ev_fork, &cx.ev_conv, &cx.ev_acc_a, &cx.ev_join}) H2_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    const u32 m32 = (u32)m;
+    return H2_OK;
+}
+// ---- the stages.  Each enqueues on `st` what the plan says; msm_launch decides which of them a call (or a phase of one) runs.
+// nothing to sum: the identity in the form the caller asked for
+template <int FB> static int msm_empty(MsmContext &cx, const MsmArgs &a, hipStream_t st) {
+    int rc;
+    if ((rc = cx.ssums.reserve(128)) != H2_OK) return rc;
+    H2_HIP(hipMemsetAsync(cx.ssums.ptr, 0, 128, st));
+    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), 1, 0, (u32 *)a.d_out, a.out_kind, a.form == H2_FORM_MONTGOMERY);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}
+// where the two-pass sort keeps its tables inside cx.plan: bin counts, bin starts, then the chunked pass 2's plan and histograms
+struct Sort2Areas { u32 *bin_count, *bin_start, *hlo, *woff, *hist2; };
+static Sort2Areas sort2_areas(MsmContext &cx, const Sort2 &S2) {
+    u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + S2.nh, *hlo = bin_start + S2.nh + 1, *woff = hlo + S2.B2;
+    return {bin_count, bin_start, hlo, woff, woff + S2.B2 + 1};
+}
+// bucket counts (cx.counts) -> bucket starts (cx.starts): the three-kernel exclusive scan both sorts end their counting with
+static void scan_bucket_starts(MsmContext &cx, const MsmPlan &p, hipStream_t st) {
+    const u32 tb = p.tb, nblocks = p.nblocks;
     u32 *grand = cx.bsums.as<u32>() + nblocks;
-    const u32 tl_id = (u32)(((uintptr_t)st >> 4) & 0xFFFF) << 8;
-    // the one-launch pass 2 also clears the raw bucket slots (its workgroups own disjoint bucket ranges), so the slots must exist
-    // before the sort is enqueued; a reservation that grows frees and synchronises, which is harmless here, in front of everything
-    const bool zero_in_sort = m9 && use_sort2 && s2_bins_form && !fold_only;
-    if (zero_in_sort && (rc = cx.seg9.reserve((head_slots + (size_t)K * tb) * 144)) != H2_OK) return rc;
-    // oversized pass-2 bins (degenerate columns) go to the chunked msm_s2_big_* kernels only where a bin can be large enough for
-    // that to matter: below 3 * 2^20 entries per column (2^18 scalars) the bin's own workgroup streams it (<= 2^17 entries: tens of
-    // microseconds, and only for such columns), and every commit saves three launches that would find an empty list
-    const u32 max_big = all_items >= ((size_t)3 << 20) ? kMaxBig : 0u;
-    if (!fold_only) {
-    TL_STAMP(tl_id | 1);
-    if (split_k) {          // the bases' conversion (it reads nothing the sort writes) on the side stream, beside the sort
-        if ((rc = cx.bases9.reserve((size_t)scalars_n * 128 + 64)) != H2_OK) return rc;
-        H2_HIP(hipEventRecord(cx.ev_fork, st));
-        H2_HIP(hipStreamWaitEvent(cx.side, cx.ev_fork, 0));
-        hipLaunchKernelGGL((msm_bases_to_m9_glv<FB>), dim3(((u32)scalars_n + 255) / 256), dim3(256), 0, cx.side, (const u32 *)a.d_bases,
-                           cx.bases9.as<u32>(), (u32)scalars_n);
-        H2_HIP(hipEventRecord(cx.ev_conv, cx.side));
+    hipLaunchKernelGGL(msm_scan_blocksums, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), tb);
+    hipLaunchKernelGGL(msm_scan_top, dim3(1), dim3(kScanBlock), 0, st, cx.bsums.as<u32>(), nblocks, grand);
+    hipLaunchKernelGGL(msm_scan_apply, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), grand, cx.starts.as<u32>(), tb);
+}
+// two-pass sort, pass 1: partition by the top bucket bits into the tagged list (generic: the endomorphism split on the fly; registered / batched:
+// a launch set over the K columns)
+template <int FS> static void sort2_pass1(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const Sort2 &S2 = p.S2;
+    const u32 K = p.K, tb = p.tb;
+    const Sort2Areas w = sort2_areas(cx, S2);
+    u32 *hist1 = cx.hist.as<u32>();
+    const size_t lds1 = ((size_t)S2.nh * 3 + 1 + (size_t)S2.s1_scalars * (p.glv ? 2 : 1) * p.sh.W) * 4;
+    // 512 lanes per pass-1 workgroup: msm_s1_scatter takes 72 registers a lane, and 16 waves of it do not fit beside the two
+    // msm_accumulate waves a SIMD already holds (2 x 168 of 512 registers) -- with 1024 lanes the sort of the NEXT commit on
+    // another stream sat out the whole accumulate (416 us on average in a 3-stream trace against 57 us alone); LDS is free
+    // there, the accumulate uses none.
+    const u32 s1_threads = 512;
+    if (p.glv) {
+        hipLaunchKernelGGL((msm_s1_count<FS, true>), dim3(S2.B1), dim3(s1_threads), S2.nh * 4, st, (const u32 *)a.d_scalars, (const u32 *)nullptr, S2, hist1, p.ci, p.cs);
+        hipLaunchKernelGGL(msm_s1_prefix, dim3((S2.nh + 15) / 16), dim3(1024), 0, st, hist1, w.bin_count, S2.B1, S2.nh, cx.heavy.as<u32>(), w.hist2, cx.starts.as<u32>() + tb + 1, p.cs);
+        hipLaunchKernelGGL((msm_s1_scatter<FS, true>), dim3(S2.B1), dim3(s1_threads), lds1, st, (const u32 *)a.d_scalars,
+                           (const u32 *)nullptr, S2, hist1, w.bin_count, w.bin_start, cx.tagged.as<u32>(), (uint16_t *)nullptr, p.ci, p.cs);
+    } else {
+        hipLaunchKernelGGL((msm_s1_count<FS, false>), dim3(S2.B1, 1, K), dim3(s1_threads), S2.nh * 4, st, (const u32 *)a.d_scalars,
+                           (const u32 *)a.d_extra_scalar, S2, hist1, p.ci, p.cs);
+        ColStride cs1 = p.cs;                 // joined columns: one heavy-bucket list and one sentinel, behind the K x tb boundaries
+        if (p.joined) cs1.heavy = cs1.starts = 0;
+        hipLaunchKernelGGL(msm_s1_prefix, dim3((S2.nh + 15) / 16, 1, K), dim3(1024), 0, st, hist1, w.bin_count, S2.B1, S2.nh, cx.heavy.as<u32>(), w.hist2,
+                           cx.starts.as<u32>() + (p.joined ? (size_t)K * tb : (size_t)tb) + 1, cs1);
+        hipLaunchKernelGGL((msm_s1_scatter<FS, false>), dim3(S2.B1, 1, K), dim3(s1_threads), lds1, st, (const u32 *)a.d_scalars,
+                           (const u32 *)a.d_extra_scalar, S2, hist1, w.bin_count, w.bin_start, cx.tagged.as<u32>(), cx.tagged_low.as<uint16_t>(), p.ci, p.cs);
     }
-    if (a.phase < 2) prof_begin(PROF_MSM_SORT, st);          // (phases >= 2 resume behind a sort the phase-1 call enqueued and timed)
+}
+// two-pass sort, pass 2 in its chunked form: chunks of 16 K tagged entries, counting sort inside the one or two bins a chunk spans
+static int sort2_pass2_chunked(MsmContext &cx, const MsmPlan &p, hipStream_t st) {
+    const Sort2 &S2 = p.S2;
+    const u32 tb = p.tb;
+    const Sort2Areas w = sort2_areas(cx, S2);
+    const u32 *tagged = cx.tagged.as<u32>();
+    const uint16_t *tagged_low = cx.tagged_low.as<uint16_t>();
+    hipLaunchKernelGGL(msm_s2_plan, dim3(1), dim3(kScanBlock), 0, st, w.bin_start, S2, w.hlo, w.woff);
+    const size_t hist2_words = ((size_t)S2.nh + S2.B2 + 1) << S2.lowb;
+    if (tb > S2.lds_window) H2_HIP(hipMemsetAsync(w.hist2, 0, hist2_words * 4, st));   // the HBM-counted windows start from zero
+    const size_t lds2 = ((size_t)S2.lds_window + S2.nh + 1) * 4;
+    hipLaunchKernelGGL(msm_s2_count, dim3(S2.B2), dim3(1024), lds2, st, tagged, tagged_low, w.bin_start, w.hlo, w.woff, S2, w.hist2);
+    hipLaunchKernelGGL(msm_s2_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, w.hist2, w.bin_start, w.hlo, w.woff, S2, cx.counts.as<u32>(), tb);
+    scan_bucket_starts(cx, p, st);
+    const size_t lds2s = std::max<size_t>(lds2, ((size_t)kS2StageWindow * 3 + 1 + S2.nh + kS2Chunk) * 4 + (size_t)kS2Chunk * 2);
+    hipLaunchKernelGGL(msm_s2_scatter, dim3(S2.B2), dim3(1024), lds2s, st, tagged, tagged_low, w.bin_start, w.hlo, w.woff, S2, w.hist2,
+                       cx.starts.as<u32>(), cx.entries.as<u32>());
+    return H2_OK;
+}
+// the two-pass sort.  Pass 2: one launch, a workgroup per bin, when an average bin fits LDS with room to spare (registered tables; the
+// 9-slice generic sort from 2^21 scalars has bins of ~64 K entries and keeps the chunked form)
+template <int FS> static int sort_two_pass(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    sort2_pass1<FS>(cx, p, a, st);
+    if (!p.s2_bins_form) return sort2_pass2_chunked(cx, p, st);
+    const Sort2Areas w = sort2_areas(cx, p.S2);
+    // (the chunked form's histogram area is free here: it holds the list of oversized bins; msm_s1_prefix zeroed its head)
+    sort2_pass2_bins(st, cx.tagged.as<u32>(), cx.tagged_low.as<uint16_t>(), w.bin_start, p.S2, p.tb, p.s2_cap_entries, cx.starts.as<u32>(), cx.entries.as<u32>(),
+                     w.hist2, p.max_big, p.zero_in_sort ? cx.seg9.as<u32>() + 36 * p.head_slots : (u32 *)nullptr, p.K, p.cs);
+    return H2_OK;
+}
+// the one-pass sort: 16-bit digit codes, per-chunk histograms in LDS, one scatter
+template <int FS> static void sort_one_pass(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const MsmShape &sh = p.sh;
+    const u32 tb = p.tb, m32 = (u32)p.m;
     const u32 extra_col = a.d_extra_scalar ? (a.table ? a.extra_col : (u32)a.n_used) : 0xFFFFFFFFu;
-    if (a.phase >= 2) {
-        // the sort was enqueued by the phase-1 call
-    } else if (use_sort2) {
-        u32 *hist1 = cx.hist.as<u32>(), *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + S2.nh, *hlo = bin_start + S2.nh + 1,
-            *woff = hlo + S2.B2, *hist2 = woff + S2.B2 + 1;
-        const size_t lds1 = ((size_t)S2.nh * 3 + 1 + (size_t)S2.s1_scalars * (glv ? 2 : 1) * sh.W) * 4;
-        // 512 lanes per pass-1 workgroup: msm_s1_scatter takes 72 registers a lane, and 16 waves of it do not fit beside the two
-        // msm_accumulate waves a SIMD already holds (2 x 168 of 512 registers) -- with 1024 lanes the sort of the NEXT commit on
-        // another stream sat out the whole accumulate (416 us on average in a 3-stream trace against 57 us alone); LDS is free
-        // there, the accumulate uses none.  H2_S1_THREADS: sweeps only.
-        static const u32 s1_threads = [] { const char *e = ab_env("H2_S1_THREADS"); int v = e ? atoi(e) : 0; return (u32)(v == 256 || v == 512 || v == 1024 ? v : 512); }();
-        if (glv) {
-            hipLaunchKernelGGL((msm_s1_count<FS, true>), dim3(S2.B1), dim3(s1_threads), S2.nh * 4, st, (const u32 *)a.d_scalars,
-                               (const u32 *)nullptr, S2, hist1, ci, cs);
-            hipLaunchKernelGGL(msm_s1_prefix, dim3((S2.nh + 15) / 16), dim3(1024), 0, st, hist1, bin_count, S2.B1, S2.nh, cx.heavy.as<u32>(), hist2, cx.starts.as<u32>() + tb + 1, cs);
-            hipLaunchKernelGGL((msm_s1_scatter<FS, true>), dim3(S2.B1), dim3(s1_threads), lds1, st, (const u32 *)a.d_scalars,
-                               (const u32 *)nullptr, S2, hist1, bin_count, bin_start, cx.tagged.as<u32>(), (uint16_t *)nullptr, ci, cs);
-        } else {
-            hipLaunchKernelGGL((msm_s1_count<FS, false>), dim3(S2.B1, 1, K), dim3(s1_threads), S2.nh * 4, st, (const u32 *)a.d_scalars,
-                               (const u32 *)a.d_extra_scalar, S2, hist1, ci, cs);
-            ColStride cs1 = cs;                   // joined columns: one heavy-bucket list and one sentinel, behind the K x tb boundaries
-            if (joined) cs1.heavy = cs1.starts = 0;
-            hipLaunchKernelGGL(msm_s1_prefix, dim3((S2.nh + 15) / 16, 1, K), dim3(1024), 0, st, hist1, bin_count, S2.B1, S2.nh, cx.heavy.as<u32>(), hist2,
-                               cx.starts.as<u32>() + (joined ? (size_t)K * tb : (size_t)tb) + 1, cs1);
-            hipLaunchKernelGGL((msm_s1_scatter<FS, false>), dim3(S2.B1, 1, K), dim3(s1_threads), lds1, st, (const u32 *)a.d_scalars,
-                               (const u32 *)a.d_extra_scalar, S2, hist1, bin_count, bin_start, cx.tagged.as<u32>(), cx.tagged_low.as<uint16_t>(), ci, cs);
-        }
-        // pass 2: one launch, a workgroup per bin, when an average bin fits LDS with room to spare (registered tables; the 9-slice
-        // generic sort has bins of ~64 K entries and keeps the chunked form); H2_S2_BINS=0: the chunked form (A/B)
-        const size_t nbk = (size_t)1 << S2.lowb;
-        const size_t cap_entries = s2_cap_entries;
-        if (s2_bins_form) {
-            if (!cx.attr_bins_set) {                              // per (device, stream) context: the attribute is per device
-                H2_HIP(hipFuncSetAttribute((const void *)msm_s2_bins, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-                cx.attr_bins_set = true;
-            }
-            u32 *big = hist2, *gcnt = hist2 + 64;                 // the chunked form's histogram area is free here; msm_s1_prefix zeroed *big
-            // the oversized-bin kernels return at once when the list is empty (the common case).  256-lane workgroups: a 1024-lane
-            // workgroup of an EMPTY launch still needs four wave slots on every SIMD of one CU, and sat behind other streams'
-            // accumulate for 10-160 us (profiles/r03_kernel_stats_3streams.csv) before it could find out that it had nothing to do
-            static const u32 big_threads = [] { const char *e = ab_env("H2_S2_BIG_THREADS"); int v = e ? atoi(e) : 0; return (u32)(v == 256 || v == 512 || v == 1024 ? v : 256); }();
-            hipLaunchKernelGGL(msm_s2_bins, dim3(S2.nh, 1, K), dim3(1024), (nbk * 2 + cap_entries) * 4, st, cx.tagged.as<u32>(),
-                               (const uint16_t *)cx.tagged_low.as<uint16_t>(), bin_start, S2, tb, (u32)cap_entries, cx.starts.as<u32>(), cx.entries.as<u32>(), big, max_big,
-                               zero_in_sort ? cx.seg9.as<u32>() + 36 * head_slots : (u32 *)nullptr, cs);
-            if (max_big) {
-            hipLaunchKernelGGL(msm_s2_big_count, dim3(kBigChunks, kMaxBig, K), dim3(big_threads), nbk * 4, st, cx.tagged.as<u32>(),
-                               (const uint16_t *)cx.tagged_low.as<uint16_t>(), bin_start, S2, (const u32 *)big, gcnt, cs);
-            hipLaunchKernelGGL(msm_s2_big_prefix, dim3(kMaxBig, 1, K), dim3(big_threads), nbk * 4, st, bin_start, S2, tb, (const u32 *)big, gcnt, cx.starts.as<u32>(), cs);
-            hipLaunchKernelGGL(msm_s2_big_scatter, dim3(kBigChunks, kMaxBig, K), dim3(big_threads), nbk * 4, st, cx.tagged.as<u32>(),
-                               (const uint16_t *)cx.tagged_low.as<uint16_t>(), bin_start, S2, (const u32 *)big, (const u32 *)gcnt, cx.entries.as<u32>(), cs);
-            }
-        } else {
-        hipLaunchKernelGGL(msm_s2_plan, dim3(1), dim3(kScanBlock), 0, st, bin_start, S2, hlo, woff);
-        const size_t hist2_words = ((size_t)S2.nh + S2.B2 + 1) << S2.lowb;
-        if (tb > S2.lds_window) H2_HIP(hipMemsetAsync(hist2, 0, hist2_words * 4, st));   // the HBM-counted windows start from zero
-        const size_t lds2 = ((size_t)S2.lds_window + S2.nh + 1) * 4;
-        hipLaunchKernelGGL(msm_s2_count, dim3(S2.B2), dim3(1024), lds2, st, cx.tagged.as<u32>(), (const uint16_t *)cx.tagged_low.as<uint16_t>(), bin_start, hlo, woff, S2, hist2);
-        hipLaunchKernelGGL(msm_s2_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, hist2, bin_start, hlo, woff, S2, cx.counts.as<u32>(),
-                           tb);
-        hipLaunchKernelGGL(msm_scan_blocksums, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), tb);
-        hipLaunchKernelGGL(msm_scan_top, dim3(1), dim3(kScanBlock), 0, st, cx.bsums.as<u32>(), nblocks, grand);
-        hipLaunchKernelGGL(msm_scan_apply, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), grand,
-                           cx.starts.as<u32>(), tb);
-        const size_t lds2s = std::max<size_t>(lds2, ((size_t)kS2StageWindow * 3 + 1 + S2.nh + kS2Chunk) * 4 + (size_t)kS2Chunk * 2);
-        hipLaunchKernelGGL(msm_s2_scatter, dim3(S2.B2), dim3(1024), lds2s, st, cx.tagged.as<u32>(), (const uint16_t *)cx.tagged_low.as<uint16_t>(), bin_start, hlo, woff, S2, hist2,
-                           cx.starts.as<u32>(), cx.entries.as<u32>());
-        }
-    } else {
-        if (glv)
-            hipLaunchKernelGGL((msm_recode_glv<FS>), dim3(((u32)scalars_n + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_scalars,
-                               cx.digits.as<uint16_t>(), (u32)scalars_n, sh.c, sh.W, a.form == H2_FORM_MONTGOMERY);
-        else
-            hipLaunchKernelGGL((msm_recode<FS>), dim3((m32 + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_scalars,
-                               (const u32 *)a.d_extra_scalar, cx.digits.as<uint16_t>(), m32, sh.c, sh.W,
-                               a.form == H2_FORM_MONTGOMERY);
-        hipLaunchKernelGGL(msm_count, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(),
-                           cx.hist.as<u32>(), sh.items, sh.chunk, sh.NB);
-        hipLaunchKernelGGL(msm_chunk_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, cx.hist.as<u32>(), cx.counts.as<u32>(),
-                           sh.NB, sh.B, tb);
-        hipLaunchKernelGGL(msm_scan_blocksums, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), tb);
-        hipLaunchKernelGGL(msm_scan_top, dim3(1), dim3(kScanBlock), 0, st, cx.bsums.as<u32>(), nblocks, grand);
-        hipLaunchKernelGGL(msm_scan_apply, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), grand,
-                           cx.starts.as<u32>(), tb);
-        hipLaunchKernelGGL(msm_scatter, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(),
-                           cx.hist.as<u32>(), cx.starts.as<u32>(), cx.entries.as<u32>(), sh.items, sh.chunk, sh.NB, m32,
-                           a.table ? a.stride : 0u, extra_col, a.table ? 1 : 0, a.table ? a.col0 : 0u);
-    }
-#ifdef H2_SORT_DEBUG
-    if (use_sort2 && sh.c <= kMaxC && a.table) {
-        std::vector<u32> sa(tb + 1), ea(all_items), sb(tb + 1), eb(all_items);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(sa.data(), cx.starts.ptr, (tb + 1) * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(ea.data(), cx.entries.ptr, (size_t)sa[tb] * 4, hipMemcpyDeviceToHost);
-        (void)cx.digits.reserve(all_items * 2);
-        DevBuf h2b;
-        (void)h2b.reserve((size_t)sh.slices * sh.B * sh.NB * 4);
+    if (p.glv)
+        hipLaunchKernelGGL((msm_recode_glv<FS>), dim3(((u32)p.scalars_n + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_scalars,
+                           cx.digits.as<uint16_t>(), (u32)p.scalars_n, sh.c, sh.W, a.form == H2_FORM_MONTGOMERY);
+    else
         hipLaunchKernelGGL((msm_recode<FS>), dim3((m32 + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_scalars,
-                           (const u32 *)a.d_extra_scalar, cx.digits.as<uint16_t>(), m32, sh.c, sh.W, a.form == H2_FORM_MONTGOMERY);
-        hipLaunchKernelGGL(msm_count, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(), h2b.as<u32>(), sh.items, sh.chunk, sh.NB);
-        hipLaunchKernelGGL(msm_chunk_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, h2b.as<u32>(), cx.counts.as<u32>(), sh.NB, sh.B, tb);
-        hipLaunchKernelGGL(msm_scan_blocksums, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), tb);
-        hipLaunchKernelGGL(msm_scan_top, dim3(1), dim3(kScanBlock), 0, st, cx.bsums.as<u32>(), nblocks, grand);
-        hipLaunchKernelGGL(msm_scan_apply, dim3(nblocks), dim3(kScanBlock), 0, st, cx.counts.as<u32>(), cx.bsums.as<u32>(), grand, cx.starts.as<u32>(), tb);
-        hipLaunchKernelGGL(msm_scatter, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(), h2b.as<u32>(), cx.starts.as<u32>(),
-                           cx.entries.as<u32>(), sh.items, sh.chunk, sh.NB, m32, a.table ? a.stride : 0u, extra_col, a.table ? 1 : 0, a.table ? a.col0 : 0u);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(sb.data(), cx.starts.ptr, (tb + 1) * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(eb.data(), cx.entries.ptr, (size_t)sb[tb] * 4, hipMemcpyDeviceToHost);
-        h2b.release();
-        size_t bad_s = 0, bad_e = 0, first_s = (size_t)-1, first_e = (size_t)-1;
-        for (u32 j = 0; j <= tb; ++j) if (sa[j] != sb[j]) { if (!bad_s) first_s = j; ++bad_s; }
-        if (!bad_s)
-            for (u32 j = 0; j < tb; ++j) {
-                std::sort(ea.begin() + sa[j], ea.begin() + sa[j + 1]);
-                std::sort(eb.begin() + sb[j], eb.begin() + sb[j + 1]);
-                if (!std::equal(ea.begin() + sa[j], ea.begin() + sa[j + 1], eb.begin() + sb[j])) { if (!bad_e) first_e = j; ++bad_e; }
-            }
-        fprintf(stderr, "[sort-debug] m=%zu NB=%u nh=%u lowb=%d lb=%d M=%u/%u starts mismatches %zu (first %zu: %u vs %u) bucket-content mismatches %zu (first %zu)\n",
-                m, sh.NB, S2.nh, S2.lowb, S2.lb, sa[tb], sb[tb], bad_s, first_s, first_s != (size_t)-1 ? sa[first_s] : 0,
-                first_s != (size_t)-1 ? sb[first_s] : 0, bad_e, first_e);
-    }
-#endif
-    if (a.phase == 1) {
-        // every workspace the rest needs is reserved NOW: a reservation that grows frees and synchronises, which the phase-2 call must
-        // not do under the sort's feet
-        if (m9) {
-            if (glv && (rc = cx.bases9.reserve((size_t)scalars_n * 128 + 64)) != H2_OK) return rc;
-            if ((rc = cx.seg9.reserve((head_slots + (size_t)K * tb) * 144)) != H2_OK) return rc;
-        }
-        prof_end(PROF_MSM_SORT, st);
-        H2_HIP(hipGetLastError());
-        return H2_OK;
-    }
-    if (split_k) {
-        if ((rc = cx.seg9.reserve((head_slots + (size_t)tb) * 144)) != H2_OK) return rc;
-        u32 *heads_b = cx.seg9.as<u32>(), *heads_a = heads_b + 36 * (size_t)T, *buckets9 = cx.seg9.as<u32>() + 36 * head_slots;
-        if (!zero_in_sort) H2_HIP(hipMemsetAsync(buckets9, 0, (size_t)tb * 144, st));
-        const u32 kb = (u32)split_k * sh.NB, tb_a = tb - kb, ns_a = sh.slices - (u32)split_k;       // buckets of the lower group; buckets / slices of the upper one
-        u32 *heavy_b = cx.heavy.as<u32>(), *heavy_a = heavy_b + (max_heavy + 2);
-        u32 *hscr_b = cx.hscratch.as<u32>(), *hscr_a = hscr_b + (size_t)max_heavy * kHeavyBlocks * 36;
-        if (!use_sort2) H2_HIP(hipMemsetAsync(heavy_b, 0, 8, st));
-        H2_HIP(hipMemsetAsync(heavy_a, 0, 8, st));
-        H2_HIP(hipStreamWaitEvent(st, cx.ev_conv, 0));
-        const u32 *pts = cx.bases9.as<u32>(), *starts = cx.starts.as<u32>();
-        u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)sh.slices * (wideS + wideNR), *ssums = cx.ssums.as<u32>();
-        int cb = 0;
-        while ((1u << cb) < wideS) ++cb;
-        const bool mont = a.form == H2_FORM_MONTGOMERY;
-        // the upper slices first, then the lower ones
-        hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(),
-                           starts + kb, heads_a, buckets9 + 36 * (size_t)kb, tb_a, T, lane_div, cs);
-        H2_HIP(hipEventRecord(cx.ev_acc_a, st));
-        hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(),
-                           starts, heads_b, buckets9, kb, T, lane_div, cs);
-        // a group's fold down to its slice sums: finish (range heads into their buckets), the heavy buckets, line sums, planes
-        auto fold_group = [&](hipStream_t s_, const u32 *heads9, const u32 *gstarts, u32 *gbuckets, u32 *heavy, u32 *hscr, u32 gtb, u32 slice0, u32 nslices) {
-            hipLaunchKernelGGL((fold9_finish<FB>), dim3((gtb + 255) / 256), dim3(256), 0, s_, heads9, gstarts, gbuckets, heavy, gtb, T, lane_div, cs);
-            hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows), dim3(256), 0, s_, heads9, gstarts, hscr, (const u32 *)heavy, gtb, T, lane_div, cs);
-            hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows), dim3(64), 0, s_, (const u32 *)hscr, gbuckets, (const u32 *)heavy, cs);
-            hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(wideS + wideNR - 1, nslices), dim3(256), 0, s_, (const u32 *)gbuckets, lines9 + 36 * (size_t)slice0 * (wideS + wideNR),
-                               wideS, wideNR, cs);
-            hipLaunchKernelGGL((fold9_planes<FB>), dim3(sh.c - 1, nslices), dim3(256), 0, s_, (const u32 *)(lines9 + 36 * (size_t)slice0 * (wideS + wideNR)),
-                               planes9 + 36 * (size_t)slice0 * 32, cx.fold_ctr.as<u32>() + slice0, wideS, wideNR, cb, ssums + 32 * (size_t)slice0, kOutSliceSum, mont, co, cs);
-        };
-        // upper group on the side stream: fold, Horner over its slices, split_k c more doublings -> one weighted point behind the slice sums
-        H2_HIP(hipStreamWaitEvent(cx.side, cx.ev_acc_a, 0));
-        fold_group(cx.side, heads_a, starts + kb, buckets9 + 36 * (size_t)kb, heavy_a, hscr_a, tb_a, (u32)split_k, ns_a);
-        hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, cx.side, (const u32 *)(ssums + 32 * (size_t)split_k), (int)ns_a, sh.c, ssums + 32 * (size_t)sh.slices,
-                           kOutSliceSum, 1, split_k * sh.c, (const u32 *)nullptr);
-        H2_HIP(hipEventRecord(cx.ev_join, cx.side));
-        // lower group behind its accumulate, then the two halves meet
-        fold_group(st, heads_b, starts, buckets9, heavy_b, hscr_b, kb, 0u, (u32)split_k);
-        H2_HIP(hipStreamWaitEvent(st, cx.ev_join, 0));
-        hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)ssums, split_k, sh.c, (u32 *)a.d_out, a.out_kind, mont ? 1 : 0, 0,
-                           (const u32 *)(ssums + 32 * (size_t)sh.slices));
-        H2_HIP(hipGetLastError());
-        return H2_OK;
-    }
-    if (a.phase != 4) {              // (phase 4: the accumulate ran in a phase-3 call)
-    if (m9) {
-        if (glv && (rc = cx.bases9.reserve((size_t)scalars_n * 128 + 64)) != H2_OK) return rc;
-        // raw M9 segments: the heads of the T ranges of every column, then the bucket slots of every column (zeroed in one go)
-        if ((rc = cx.seg9.reserve((head_slots + (size_t)K * tb) * 144)) != H2_OK) return rc;
-        if (!zero_in_sort) H2_HIP(hipMemsetAsync(cx.seg9.as<u32>() + 36 * head_slots, 0, (size_t)K * tb * 144, st));
+                           (const u32 *)a.d_extra_scalar, cx.digits.as<uint16_t>(), m32, sh.c, sh.W,
+                           a.form == H2_FORM_MONTGOMERY);
+    hipLaunchKernelGGL(msm_count, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(), cx.hist.as<u32>(), sh.items, sh.chunk, sh.NB);
+    hipLaunchKernelGGL(msm_chunk_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, cx.hist.as<u32>(), cx.counts.as<u32>(), sh.NB, sh.B, tb);
+    scan_bucket_starts(cx, p, st);
+    hipLaunchKernelGGL(msm_scatter, dim3(sh.B, sh.slices), dim3(1024), sh.NB * 4, st, cx.digits.as<uint16_t>(),
+                       cx.hist.as<u32>(), cx.starts.as<u32>(), cx.entries.as<u32>(), sh.items, sh.chunk, sh.NB, m32,
+                       a.table ? a.stride : 0u, extra_col, a.table ? 1 : 0, a.table ? a.col0 : 0u);
+}
+// what the accumulate adds into starts from zero: the bucket slots (unless the sort cleared them) and the heavy-bucket list
+static int clear_buckets(MsmContext &cx, const MsmPlan &p, hipStream_t st) {
+    if (p.m9) {
+        // the bucket slots of every column, zeroed in one go
+        if (!p.zero_in_sort) H2_HIP(hipMemsetAsync(cx.seg9.as<u32>() + 36 * p.head_slots, 0, (size_t)p.K * p.tb * 144, st));
     } else {
-        H2_HIP(hipMemsetAsync(cx.buckets.ptr, 0, (size_t)tb * 128, st));
+        H2_HIP(hipMemsetAsync(cx.buckets.ptr, 0, (size_t)p.tb * 128, st));
     }
-    if (!use_sort2) H2_HIP(hipMemsetAsync(cx.heavy.ptr, 0, 8, st));          // (the two-pass sort's msm_s1_prefix zeroed it)
-    if (a.phase < 2) prof_end(PROF_MSM_SORT, st);
-    TL_STAMP(tl_id | 2);
-    prof_begin(PROF_MSM_ACCUMULATE, st);
-    if (glv && !m9)
-        hipLaunchKernelGGL((msm_accumulate<FB, true>), dim3(T / 256), dim3(256), 0, st, (const u32 *)a.d_bases, (const u32 *)nullptr,
-                           (u32)scalars_n, cx.entries.as<u32>(), cx.starts.as<u32>(), cx.heads.as<u32>(), cx.buckets.as<u32>(), tb, T, lane_div, cs);
-    else if (m9) {
+    if (!p.use_sort2) H2_HIP(hipMemsetAsync(cx.heavy.ptr, 0, 8, st));          // (the two-pass sort's msm_s1_prefix zeroed it)
+    return H2_OK;
+}
+// the accumulate: registered tables on the carry-free layer (one launch over the joined columns of a batch, or a column per grid z), the
+// generic path likewise after converting its bases (+ phi(P)) to M9 form, and a generic call with a blind term on the 8 x 32 layer
+template <int FB> static void accumulate(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const u32 K = p.K, tb = p.tb, T = p.T;
+    if (p.m9) {
         const u32 *pts = (const u32 *)a.d_bases;
-        if (glv) {
-            hipLaunchKernelGGL((msm_bases_to_m9_glv<FB>), dim3(((u32)scalars_n + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_bases,
-                               cx.bases9.as<u32>(), (u32)scalars_n);
+        if (p.glv) {
+            hipLaunchKernelGGL((msm_bases_to_m9_glv<FB>), dim3(((u32)p.scalars_n + 255) / 256), dim3(256), 0, st, (const u32 *)a.d_bases,
+                               cx.bases9.as<u32>(), (u32)p.scalars_n);
             pts = cx.bases9.as<u32>();
         }
-        hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256, 1, joined ? 1 : K), dim3(256), 0, st, pts,
+        hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256, 1, p.joined ? 1 : K), dim3(256), 0, st, pts,
                            (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(), cx.starts.as<u32>(), cx.seg9.as<u32>(),
-                           cx.seg9.as<u32>() + 36 * head_slots, joined ? K * tb : tb, T, lane_div, cs);
-        if (!fold9)
-            hipLaunchKernelGGL((msm_segments_to_r256<FB>), dim3((T + tb + 255) / 256), dim3(256), 0, st, cx.seg9.as<u32>(),
-                               cx.heads.as<u32>(), cx.buckets.as<u32>(), T, tb);
-    }
-    else
+                           cx.seg9.as<u32>() + 36 * p.head_slots, p.joined ? K * tb : tb, T, p.lane_div, p.cs);
+        if (!p.fold9)
+            hipLaunchKernelGGL((msm_segments_to_r256<FB>), dim3((T + tb + 255) / 256), dim3(256), 0, st, cx.seg9.as<u32>(), cx.heads.as<u32>(), cx.buckets.as<u32>(), T, tb);
+    } else {
         hipLaunchKernelGGL((msm_accumulate<FB, false>), dim3(T / 256), dim3(256), 0, st, (const u32 *)a.d_bases,
                            (const u32 *)a.d_extra_base, (!a.table && a.d_extra_base) ? (u32)a.n_used : 0xFFFFFFFFu,
-                           cx.entries.as<u32>(), cx.starts.as<u32>(), cx.heads.as<u32>(), cx.buckets.as<u32>(), tb, T, lane_div, cs);
-    prof_end(PROF_MSM_ACCUMULATE, st);
-    TL_STAMP(tl_id | 3);
-    if (a.phase == 3) {
-        H2_HIP(hipGetLastError());
-        return H2_OK;
+                           cx.entries.as<u32>(), cx.starts.as<u32>(), cx.heads.as<u32>(), cx.buckets.as<u32>(), tb, T, p.lane_div, p.cs);
     }
+}
+// the carry-free fold: finish on the raw M9 segments, one lane per bucket; the buckets stay in cx.seg9.  Window slices (generic path) meet in
+// msm_combine's Horner step, unless the caller wants the slice sums (slice_sums_only)
+template <int FB> static void fold_carry_free(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const MsmShape &sh = p.sh;
+    const bool mont = a.form == H2_FORM_MONTGOMERY, windows = p.glv;
+    u32 *heads9 = cx.seg9.as<u32>(), *buckets9 = heads9 + 36 * p.head_slots;
+    u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)p.K * sh.slices * (p.wideS + p.wideNR);
+    fold9_group<FB>(st, heads9, cx.starts.as<u32>(), buckets9, cx.heavy.as<u32>(), cx.hscratch.as<u32>(), lines9, planes9, cx.fold_ctr.as<u32>(),
+                    windows ? cx.ssums.as<u32>() : (u32 *)a.d_out, windows ? kOutSliceSum : a.out_kind, mont, p.tb, p.T, p.lane_div, sh.c, p.wideS, p.wideNR,
+                    0u, sh.slices, p.K, p.co, p.cs);
+    if (windows && !a.slice_sums_only)
+        hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)sh.slices, sh.c, (u32 *)a.d_out, a.out_kind, mont);
+}
+// the 8 x 32 finisher and fold.  A range of a chunked commit stops at its finished buckets (added into add_into); the fold-only call
+// starts from buckets summed that way.
+template <int FB> static int fold_r256(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const MsmShape &sh = p.sh;
+    const u32 tb = p.tb, T = p.T;
+    if (!p.fold_only) {
+        hipLaunchKernelGGL((msm_finish_buckets<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, cx.heads.as<u32>(),
+                           cx.starts.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
+        hipLaunchKernelGGL((msm_finish_heavy<FB>), dim3(kHeavyBlocks, kMaxHeavy), dim3(256), (256 / kGroup) * 128, st,
+                           cx.heads.as<u32>(), cx.starts.as<u32>(), cx.hscratch.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
+        hipLaunchKernelGGL((msm_finish_heavy2<FB>), dim3(kMaxHeavy), dim3(64), 0, st, cx.hscratch.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>());
     }
-    prof_begin(PROF_MSM_REDUCE, st);
-    if (fold9) {
-        // wide slice: finish on the raw M9 segments, one lane per bucket (fold9_* above); the buckets stay in cx.seg9
-        u32 *heads9 = cx.seg9.as<u32>(), *buckets9 = cx.seg9.as<u32>() + 36 * head_slots;
-        const u32 fz = joined ? 1 : K, ftb = joined ? K * tb : tb;       // joined columns: one pass over the K x tb buckets
-        hipLaunchKernelGGL((fold9_finish<FB>), dim3((ftb + 255) / 256, 1, fz), dim3(256), 0, st, (const u32 *)heads9, cx.starts.as<u32>(), buckets9,
-                           cx.heavy.as<u32>(), ftb, T, lane_div, cs);
-        hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows, fz), dim3(256), 0, st, (const u32 *)heads9, cx.starts.as<u32>(),
-                           cx.hscratch.as<u32>(), cx.heavy.as<u32>(), ftb, T, lane_div, cs);
-        hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows, 1, fz), dim3(64), 0, st, cx.hscratch.as<u32>(), buckets9, cx.heavy.as<u32>(), cs);
-    } else {
-    hipLaunchKernelGGL((msm_finish_buckets<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, cx.heads.as<u32>(),
-                       cx.starts.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>(), tb, T, lane_div);
-    hipLaunchKernelGGL((msm_finish_heavy<FB>), dim3(kHeavyBlocks, max_heavy), dim3(256), (256 / kGroup) * 128, st,
-                       cx.heads.as<u32>(), cx.starts.as<u32>(), cx.hscratch.as<u32>(), cx.heavy.as<u32>(), tb, T, lane_div);
-    hipLaunchKernelGGL((msm_finish_heavy2<FB>), dim3(max_heavy), dim3(64), 0, st, cx.hscratch.as<u32>(), cx.buckets.as<u32>(),
-                       cx.heavy.as<u32>());
-    }
-    if (a.add_into) {
+    if (p.add_only) {
         hipLaunchKernelGGL((msm_bucket_add<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, a.add_into, cx.buckets.as<u32>(), tb);
-        prof_end(PROF_MSM_REDUCE, st);
+        return H2_OK;
+    }
+    // what the fold runs over: the bucket slices themselves, or (wide slices) the row / column sums as two slices
+    const u32 *fold_src = p.fold_only ? a.fold_from : cx.buckets.as<u32>();
+    u32 fold_nb = sh.NB, fold_slices = sh.slices;
+    int fold_c = sh.c;
+    if (p.wide_reduce) {
+        u32 *wide = cx.partial.as<u32>() + 32 * (size_t)(2 * p.wideNR / kSeg);     // after the fold's own partials
+        H2_HIP(hipMemsetAsync(wide, 0, (size_t)2 * p.wideNR * 128, st));
+        hipLaunchKernelGGL((msm_rowcol_sums<FB>), dim3(p.wideS + p.wideNR - 1), dim3(256), (256 / kGroup) * 128, st, fold_src, wide, p.wideS, p.wideNR);
+        fold_src = wide;
+        fold_nb = p.wideNR;
+        fold_slices = 2;
+        fold_c = (sh.c - 1) / 2;      // log2 S
+    }
+    // A segment is 2 seg running-sum additions + a small-scalar multiple (~23 more dependent operations) on one quad of lanes:
+    // 4 buckets while the segments fit the chip a few times over (the fold is their latency: one commit 0.235 -> 0.218 ms,
+    // small commits 5-8 %), 8 when there are many slices (generic multiexps of 2^20 points: the multiples are throughput)
+    const int seg = (size_t)fold_slices * fold_nb / kSeg <= 32768 ? kSeg : 2 * kSeg;
+    const u32 fold_segs = fold_slices * fold_nb / seg;
+    hipLaunchKernelGGL((msm_reduce_segments<FB>), dim3((fold_segs * kGroup + 255) / 256), dim3(256), 0, st, fold_src, cx.partial.as<u32>(), fold_nb, fold_segs, seg);
+    // 64 logical lanes per workgroup; first level leaves <= 32 block sums per slice
+    const u32 per_slice = fold_nb / seg, nl = 256 / kGroup;
+    const u32 bps = std::max(1u, std::min(32u, per_slice / (2 * nl)));
+    const u32 share = (per_slice + bps - 1) / bps;
+    if (bps > 1) {
+        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(bps, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(),
+                           cx.heads.as<u32>(), per_slice, share);     // heads[] is free again: reuse as level-1 output
+        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.heads.as<u32>(), cx.ssums.as<u32>(), bps, bps);
+    } else {
+        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(), cx.ssums.as<u32>(), per_slice, per_slice);
+    }
+    hipLaunchKernelGGL((msm_combine<FB>), dim3(p.pair ? 2 : 1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)fold_slices, fold_c, (u32 *)a.d_out,
+                       a.out_kind, a.form == H2_FORM_MONTGOMERY);
+    return H2_OK;
+}
+// the slice split, in front of the sort: the bases' conversion (it reads nothing the sort writes) on the side stream, beside the sort
+template <int FB> static int slice_split_convert(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    H2_HIP(hipEventRecord(cx.ev_fork, st));
+    H2_HIP(hipStreamWaitEvent(cx.side, cx.ev_fork, 0));
+    hipLaunchKernelGGL((msm_bases_to_m9_glv<FB>), dim3(((u32)p.scalars_n + 255) / 256), dim3(256), 0, cx.side, (const u32 *)a.d_bases, cx.bases9.as<u32>(), (u32)p.scalars_n);
+    H2_HIP(hipEventRecord(cx.ev_conv, cx.side));
+    return H2_OK;
+}
+// the slice split, behind the sort: both groups' accumulates on `st`, the upper group's fold and Horner chain on the side stream
+template <int FB> static int slice_split_accumulate_fold(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const MsmShape &sh = p.sh;
+    const u32 tb = p.tb, T = p.T, split_k = (u32)p.split_k;
+    u32 *heads_b = cx.seg9.as<u32>(), *heads_a = heads_b + 36 * (size_t)T, *buckets9 = cx.seg9.as<u32>() + 36 * p.head_slots;
+    if (!p.zero_in_sort) H2_HIP(hipMemsetAsync(buckets9, 0, (size_t)tb * 144, st));
+    const u32 kb = split_k * sh.NB, tb_a = tb - kb, ns_a = sh.slices - split_k;       // buckets of the lower group; buckets / slices of the upper one
+    u32 *heavy_b = cx.heavy.as<u32>(), *heavy_a = heavy_b + (kMaxHeavy + 2);
+    u32 *hscr_b = cx.hscratch.as<u32>(), *hscr_a = hscr_b + (size_t)kMaxHeavy * kHeavyBlocks * 36;
+    if (!p.use_sort2) H2_HIP(hipMemsetAsync(heavy_b, 0, 8, st));
+    H2_HIP(hipMemsetAsync(heavy_a, 0, 8, st));
+    H2_HIP(hipStreamWaitEvent(st, cx.ev_conv, 0));
+    const u32 *pts = cx.bases9.as<u32>(), *starts = cx.starts.as<u32>();
+    u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)sh.slices * (p.wideS + p.wideNR), *ssums = cx.ssums.as<u32>();
+    const bool mont = a.form == H2_FORM_MONTGOMERY;
+    // the upper slices first, then the lower ones
+    hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(),
+                       starts + kb, heads_a, buckets9 + 36 * (size_t)kb, tb_a, T, p.lane_div, p.cs);
+    H2_HIP(hipEventRecord(cx.ev_acc_a, st));
+    hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(),
+                       starts, heads_b, buckets9, kb, T, p.lane_div, p.cs);
+    // upper group on the side stream: fold, Horner over its slices, split_k c more doublings -> one weighted point behind the slice sums
+    H2_HIP(hipStreamWaitEvent(cx.side, cx.ev_acc_a, 0));
+    fold9_group<FB>(cx.side, heads_a, starts + kb, buckets9 + 36 * (size_t)kb, heavy_a, hscr_a, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
+                    tb_a, T, p.lane_div, sh.c, p.wideS, p.wideNR, split_k, ns_a, 1u, p.co, p.cs);
+    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, cx.side, (const u32 *)(ssums + 32 * (size_t)split_k), (int)ns_a, sh.c, ssums + 32 * (size_t)sh.slices,
+                       kOutSliceSum, 1, p.split_k * sh.c, (const u32 *)nullptr);
+    H2_HIP(hipEventRecord(cx.ev_join, cx.side));
+    // lower group behind its accumulate, then the two halves meet
+    fold9_group<FB>(st, heads_b, starts, buckets9, heavy_b, hscr_b, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
+                    kb, T, p.lane_div, sh.c, p.wideS, p.wideNR, 0u, split_k, 1u, p.co, p.cs);
+    H2_HIP(hipStreamWaitEvent(st, cx.ev_join, 0));
+    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)ssums, p.split_k, sh.c, (u32 *)a.d_out, a.out_kind, mont ? 1 : 0, 0,
+                       (const u32 *)(ssums + 32 * (size_t)sh.slices));
+    return H2_OK;
+}
+// One multiexp, or one phase of it (MsmArgs::phase): 1 = the sort; 2 = accumulate + fold behind a phase-1 sort; 3 = the accumulate; 4 = the fold.
+// The fold-only call (fold_from) is the 8 x 32 fold alone.
+template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a, hipStream_t st) {
+    const bool empty = a.n_used + (a.d_extra_scalar ? 1 : 0) == 0;
+    if (empty && a.add_into) return H2_OK;           // an empty range adds nothing
+    if (empty && !a.fold_from) return msm_empty<FB>(cx, a, st);
+    int rc;
+    u32 lanes = 0;
+    if ((rc = msm_context_setup<FB>(cx, msm_m9(a), &lanes)) != H2_OK) return rc;
+    MsmPlan p;
+    if ((rc = msm_plan(a, lanes, prof_enabled() || timeline_on(), &p)) != H2_OK) return rc;
+    if (p.try_grouped) {
+        rc = msm_generic_grouped<FB, FS>(cx, a, p.sh, p.scalars_n, lanes, st);
+        if (rc != H2_ERR_BATCH_SHAPE) return rc;
+    }
+    if (!a.table && a.phase == 0 && !p.fold_only && !a.add_into && !a.slice_sums_only) {      // a whole generic multiexp (h2_msm_last_path)
+        cx.last.path = p.split_k ? H2_MSM_PATH_SLICE_SPLIT : p.use_sort2 ? H2_MSM_PATH_TWO_PASS : H2_MSM_PATH_ONE_PASS;
+        cx.last.groups = p.split_k ? 2 : 1;
+        cx.last.acc_lanes = p.T;
+        cx.last.c = p.sh.c;
+    }
+    if ((rc = msm_reserve(cx, p, st)) != H2_OK) return rc;
+    // which stages this call runs (phases >= 2 resume behind a sort the phase-1 call enqueued and timed)
+    const bool sorts = !p.fold_only && a.phase < 2, accumulates = !p.fold_only && a.phase != 1 && a.phase != 4, folds = a.phase != 1 && a.phase != 3;
+    const u32 tl_id = (u32)(((uintptr_t)st >> 4) & 0xFFFF) << 8;
+    if (!p.fold_only) TL_STAMP(tl_id | 1);
+    if (p.split_k && (rc = slice_split_convert<FB>(cx, p, a, st)) != H2_OK) return rc;
+    if (sorts) {
+        prof_begin(PROF_MSM_SORT, st);
+        if (!p.use_sort2) sort_one_pass<FS>(cx, p, a, st);
+        else if ((rc = sort_two_pass<FS>(cx, p, a, st)) != H2_OK) return rc;
+    }
+    if (p.split_k) {
+        if ((rc = slice_split_accumulate_fold<FB>(cx, p, a, st)) != H2_OK) return rc;
         H2_HIP(hipGetLastError());
         return H2_OK;
     }
-    } else {
+    if (accumulates && (rc = clear_buckets(cx, p, st)) != H2_OK) return rc;
+    if (sorts) prof_end(PROF_MSM_SORT, st);
+    if (accumulates) {
+        TL_STAMP(tl_id | 2);
+        prof_begin(PROF_MSM_ACCUMULATE, st);
+        accumulate<FB>(cx, p, a, st);
+        prof_end(PROF_MSM_ACCUMULATE, st);
+        TL_STAMP(tl_id | 3);
+    }
+    if (folds) {
         prof_begin(PROF_MSM_REDUCE, st);
+        if (p.fold9) fold_carry_free<FB>(cx, p, a, st);
+        else if ((rc = fold_r256<FB>(cx, p, a, st)) != H2_OK) return rc;
+        prof_end(PROF_MSM_REDUCE, st);
+        if (!p.add_only) TL_STAMP(tl_id | 4);
     }
-    {
-        // what the fold runs over: the bucket slices themselves, or (wide slices) the row / column sums as two slices
-        const u32 *fold_src = fold_only ? a.fold_from : cx.buckets.as<u32>();
-        u32 fold_nb = sh.NB, fold_slices = sh.slices;
-        int fold_c = sh.c;
-        if (fold9) {
-            // line sums, then the bit planes of the line weights and their combination in one launch (fold9_planes)
-            u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)K * sh.slices * (wideS + wideNR);
-            int cb = 0;
-            while ((1u << cb) < wideS) ++cb;
-            hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(wideS + wideNR - 1, sh.slices, K), dim3(256), 0, st,
-                               (const u32 *)(cx.seg9.as<u32>() + 36 * head_slots), lines9, wideS, wideNR, cs);
-            const bool windows = glv;                // the slices are window slices: their sums meet in msm_combine's Horner step
-            hipLaunchKernelGGL((fold9_planes<FB>), dim3(sh.c - 1, sh.slices, K), dim3(256), 0, st, (const u32 *)lines9, planes9, cx.fold_ctr.as<u32>(),
-                               wideS, wideNR, cb, windows ? cx.ssums.as<u32>() : (u32 *)a.d_out, windows ? kOutSliceSum : a.out_kind,
-                               a.form == H2_FORM_MONTGOMERY, co, cs);
-            if (windows && !a.slice_sums_only)
-                hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)sh.slices, sh.c, (u32 *)a.d_out, a.out_kind,
-                                   a.form == H2_FORM_MONTGOMERY);
-            prof_end(PROF_MSM_REDUCE, st);
-            TL_STAMP(tl_id | 4);
-            H2_HIP(hipGetLastError());
-            return H2_OK;
-        }
-        if (wide_reduce) {
-            u32 *wide = cx.partial.as<u32>() + 32 * (size_t)(2 * wideNR / kSeg);     // after the fold's own partials
-            H2_HIP(hipMemsetAsync(wide, 0, (size_t)2 * wideNR * 128, st));
-            hipLaunchKernelGGL((msm_rowcol_sums<FB>), dim3(wideS + wideNR - 1), dim3(256), (256 / kGroup) * 128, st, fold_src,
-                               wide, wideS, wideNR);
-            fold_src = wide;
-            fold_nb = wideNR;
-            fold_slices = 2;
-            fold_c = (sh.c - 1) / 2;      // log2 S
-        }
-        // A segment is 2 seg running-sum additions + a small-scalar multiple (~23 more dependent operations) on one quad of lanes:
-        // 4 buckets while the segments fit the chip a few times over (the fold is their latency: one commit 0.235 -> 0.218 ms,
-        // small commits 5-8 %), 8 when there are many slices (generic multiexps of 2^20 points: the multiples are throughput)
-        const int seg = (size_t)fold_slices * fold_nb / kSeg <= 32768 ? kSeg : 2 * kSeg;
-        const u32 fold_segs = fold_slices * fold_nb / seg;
-        hipLaunchKernelGGL((msm_reduce_segments<FB>), dim3((fold_segs * kGroup + 255) / 256), dim3(256), 0, st, fold_src,
-                           cx.partial.as<u32>(), fold_nb, fold_segs, seg);
-        // 64 logical lanes per workgroup; first level leaves <= 32 block sums per slice
-        const u32 per_slice = fold_nb / seg, nl = 256 / kGroup;
-        const u32 bps = std::max(1u, std::min(32u, per_slice / (2 * nl)));
-        const u32 share = (per_slice + bps - 1) / bps;
-        if (bps > 1) {
-            hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(bps, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(),
-                               cx.heads.as<u32>(), per_slice, share);     // heads[] is free again: reuse as level-1 output
-            hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.heads.as<u32>(),
-                               cx.ssums.as<u32>(), bps, bps);
-        } else {
-            hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(),
-                               cx.ssums.as<u32>(), per_slice, per_slice);
-        }
-        hipLaunchKernelGGL((msm_combine<FB>), dim3(pair ? 2 : 1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)fold_slices, fold_c, (u32 *)a.d_out,
-                           a.out_kind, a.form == H2_FORM_MONTGOMERY);
-    }
-    prof_end(PROF_MSM_REDUCE, st);
-    TL_STAMP(tl_id | 4);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }

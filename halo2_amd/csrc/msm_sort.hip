@@ -1013,4 +1013,22 @@ template __global__ void msm_s1_scatter<FQ, true>(const u32 *__restrict__ scalar
 template __global__ void msm_glv_digits<FP>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
 template __global__ void msm_glv_digits<FQ>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
 
+// ---- host: the one-launch pass 2 and its oversized-bin followers, for every caller (declared in msm_internal.cuh)
+void sort2_pass2_bins(hipStream_t st, const u32 *tagged, const uint16_t *tagged_low, const u32 *bin_start, const Sort2 &S2, u32 tb, size_t cap_entries,
+                      u32 *starts, u32 *entries, u32 *big, u32 max_big, u32 *zero9, u32 cols, const ColStride &cs) {
+    const size_t nbk = (size_t)1 << S2.lowb;
+    u32 *gcnt = big + 64;
+    hipLaunchKernelGGL(msm_s2_bins, dim3(S2.nh, 1, cols), dim3(1024), (nbk * 2 + cap_entries) * 4, st, tagged, tagged_low, bin_start, S2, tb, (u32)cap_entries, starts,
+                       entries, big, max_big, zero9, cs);
+    if (!max_big) return;
+    // the oversized-bin kernels return at once when the list is empty (the common case).  256-lane workgroups: a 1024-lane
+    // workgroup of an EMPTY launch still needs four wave slots on every SIMD of one CU, and sat behind other streams'
+    // accumulate for 10-160 us (profiles/r03_kernel_stats_3streams.csv) before it could find out that it had nothing to do
+    const u32 big_threads = 256;
+    hipLaunchKernelGGL(msm_s2_big_count, dim3(kBigChunks, kMaxBig, cols), dim3(big_threads), nbk * 4, st, tagged, tagged_low, bin_start, S2, (const u32 *)big, gcnt, cs);
+    hipLaunchKernelGGL(msm_s2_big_prefix, dim3(kMaxBig, 1, cols), dim3(big_threads), nbk * 4, st, bin_start, S2, tb, (const u32 *)big, gcnt, starts, cs);
+    hipLaunchKernelGGL(msm_s2_big_scatter, dim3(kBigChunks, kMaxBig, cols), dim3(big_threads), nbk * 4, st, tagged, tagged_low, bin_start, S2, (const u32 *)big,
+                       (const u32 *)gcnt, entries, cs);
+}
+
 }  // namespace h2

@@ -272,7 +272,7 @@ static int pair_subdigit_launch(MsmContext &cx, const Bases &b, const void *d_sc
     const u32 nblk = (u32)((n + sub_block - 1) / sub_block), tb = kSubSlots, nsl = 4;
     const int glv = b.glv ? 1 : 0;
     const size_t max_entries = n * (glv ? 40 : 32);             // two sub-digits per table digit: 16 digits; over an endomorphism table 2 x (7 x 2 + 4 + 2) at most
-    u32 &lanes = cx.lanes[FB][2];
+    u32 &lanes = cx.lanes[FB][1];
     if (!lanes) {            // how many lanes of the M9 accumulate the chip holds at once (as msm_launch sizes it)
         int dev = 0, cus = 0, per_cu = 0;
         H2_HIP(hipGetDevice(&dev));

@@ -106,7 +106,10 @@ def test_shipped_library_reads_no_algorithm_switch():
         names |= set(re.findall(r'ab_env\("(H2_\w+)"\)', src))
         direct += re.findall(r'[^_]getenv\("(H2_\w+)"\)', src)
     assert direct == ["H2_TIMELINE"], direct
-    assert len(names) >= 30 and "H2_TIMELINE" not in names, sorted(names)
+    # (the scan is not vacuous: the multiexp's ten switches that a test or a tool sets are among the names it finds)
+    kept = {"H2_MSM_C", "H2_MSM_DIV", "H2_ACC_WAVES", "H2_BATCH_JOIN", "H2_BATCH_COLS", "H2_GENERIC_GROUPED", "H2_GENERIC_GROUPS", "H2_GENERIC_SPLIT",
+            "H2_GG_FORM", "H2_GG_SPARE"}
+    assert kept <= names and len(names) >= 28 and "H2_TIMELINE" not in names, sorted(names)
     blob = open(os.path.join(ROOT, "halo2_amd", "libhalo2_mi355x.so"), "rb").read()
     leaked = [n for n in sorted(names) if (n + "\0").encode() in blob]
     assert not leaked, leaked
