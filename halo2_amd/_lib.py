@@ -113,6 +113,12 @@ SIGNATURES = {
                             u64p, vp, vp], C.c_int),
     "h2_sort_device": ([C.c_int, vp, C.c_size_t, C.c_int, vp], C.c_int),
     "h2_permute_expression_pair_device": ([C.c_int, vp, vp, C.c_size_t, C.c_int, vp, vp, vp], C.c_int),
+    "h2_check_expressions_device": ([C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_size_t, C.POINTER(vp),
+                                     C.POINTER(C.c_uint8), C.c_size_t, C.c_uint, C.c_size_t, vp, vp, vp, C.POINTER(vp), vp], C.c_int),
+    "h2_lookup_check_device": ([C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.c_size_t, C.c_size_t,
+                                C.c_int, vp, vp, vp], C.c_int),
+    "h2_permutation_check_device": ([C.c_int, C.POINTER(vp), C.POINTER(C.c_uint8), C.c_size_t, vp, C.c_uint, C.c_size_t, C.c_int, vp, vp, vp],
+                                    C.c_int),
     "h2_points_compress": ([C.c_int, u64p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8)], C.c_int),
     "h2_points_compress_device": ([C.c_int, vp, C.c_size_t, C.c_int, vp, vp], C.c_int),
     "h2_points_decompress": ([C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, u64p], C.c_int),

@@ -195,5 +195,6 @@ extern "C" int h2_trim(void) {
     h2::verify_release_workspaces();
     h2::eval_release_workspaces();
     h2::lookup_release_workspaces();
+    h2::mock_release_workspaces();
     return H2_OK;
 }

@@ -116,6 +116,12 @@ void ipa_release_workspaces();
 void verify_release_workspaces();
 void eval_release_workspaces();
 void lookup_release_workspaces();
+void mock_release_workspaces();
+
+// The field-element sort of lookup.hip for other translation units (mock_prover.hip): `n` elements of d_src as canonical keys into
+// `keys`, padded to the next power of two with all-ones keys and sorted ascending; and the sort alone of 2^log_n keys already in place.
+int lookup_prepare_and_sort(int field, const void *d_src, size_t n, int form, DevBuf &keys, hipStream_t st);
+int lookup_sort_padded(uint32_t *keys, int log_n, hipStream_t st);
 
 // Confirms a usable gfx950 device exists; every entry point calls this first so a missing GPU or
 // runtime fails loudly (H2_ERR_NODEV) instead of silently doing nothing.

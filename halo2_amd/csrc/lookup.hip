@@ -17,6 +17,7 @@
 #include "common.h"
 #include "field.cuh"
 #include "host_field.h"
+#include "lookup_keys.cuh"
 
 namespace h2 {
 
@@ -25,35 +26,6 @@ namespace {
 constexpr int kTileLog = 11;                 // 2048 keys x 32 B = 64 KiB of LDS per workgroup
 constexpr u32 kTile = 1u << kTileLog;
 constexpr u32 kSortThreads = kTile / 2;      // one compare-exchange per lane per stage
-
-struct key256 {
-    u32 v[8];
-};
-
-__device__ __forceinline__ bool key_less(const key256 &a, const key256 &b) {
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        if (a.v[i] != b.v[i]) return a.v[i] < b.v[i];
-    }
-    return false;
-}
-
-__device__ __forceinline__ bool key_eq(const key256 &a, const key256 &b) {
-    u32 d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d |= a.v[i] ^ b.v[i];
-    return d == 0;
-}
-
-__device__ __forceinline__ key256 key_load(const u32 *p) {
-    const uint4 lo = reinterpret_cast<const uint4 *>(p)[0], hi = reinterpret_cast<const uint4 *>(p)[1];
-    return key256{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
-}
-
-__device__ __forceinline__ void key_store(u32 *p, const key256 &k) {
-    reinterpret_cast<uint4 *>(p)[0] = make_uint4(k.v[0], k.v[1], k.v[2], k.v[3]);
-    reinterpret_cast<uint4 *>(p)[1] = make_uint4(k.v[4], k.v[5], k.v[6], k.v[7]);
-}
 
 // copy n elements into the padded sort buffer as canonical keys; the padding sorts last (all ones > any field element)
 template <int F>
@@ -162,17 +134,6 @@ __global__ void __launch_bounds__(256) lk_sort_global2(u32 *__restrict__ a, size
     key_store(a + 8 * (i | j2), e1);
     key_store(a + 8 * (i | j1), e2);
     key_store(a + 8 * (i | j1 | j2), e3);
-}
-
-// lower bound of `key` in the ascending array s[0..n): first index whose element is not less than key
-__device__ __forceinline__ u32 lower_bound(const u32 *__restrict__ s, u32 n, const key256 &key) {
-    u32 lo = 0, hi = n;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (key_less(key_load(s + 8 * (size_t)mid), key)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // rep[i] = 1 where A[i] repeats A[i-1]; keep[i] = 0 for the head of a table run whose value occurs in A (that instance is the
@@ -319,6 +280,10 @@ int prepare_and_sort(int field, const void *d_src, size_t n, int form, DevBuf &k
 }  // namespace
 
 void lookup_release_workspaces() { g_lookup_ctxs.release_current_device(); }
+int lookup_prepare_and_sort(int field, const void *d_src, size_t n, int form, DevBuf &keys, hipStream_t st) {
+    return prepare_and_sort(field, d_src, n, form, keys, st);
+}
+int lookup_sort_padded(uint32_t *keys, int log_n, hipStream_t st) { return sort_padded(keys, log_n, st); }
 
 }  // namespace h2
 

@@ -1,0 +1,450 @@
+// `dev::MockProver::verify` over device-resident columns (halo2_proofs/src/dev.rs:576-904): which constraints does a witness break?
+// Three checks, each leaving one bit per row in a bit plane (a 64-bit wave ballot per wave, written by one lane) and exact counts:
+//   * h2_check_expressions_device  the gate polynomials at every row with the Real / Poison algebra of dev.rs:104-156: the bytecode of
+//                                  evaluator.hip (Lagrange basis), several programs per launch, a poison bit beside every stack slot;
+//   * h2_lookup_check_device       exact membership of input tuples among table tuples (dev.rs:709-833): every component is replaced
+//                                  by its rank in the sorted table column, up to seven ranks pack into one 224-bit key whose order
+//                                  is the tuples' lexicographic order, the packed table keys are sorted (lookup.hip's bitonic
+//                                  network) and the packed input keys binary-searched;
+//   * h2_permutation_check_device  one gather and one 256-bit compare per cell of the copy-constraint mapping (dev.rs:835-881).
+// A satisfied circuit costs the caller one read of the counts; the planes are fetched only for what failed.  Nothing here
+// synchronises or allocates per call beyond the grow-only workspaces of its (device, stream) context.
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+#include "field.cuh"
+#include "host_field.h"
+#include "lookup_keys.cuh"
+
+namespace h2 {
+
+namespace {
+
+enum : u32 { MP_POLY = 1, MP_CONST = 2, MP_LINEAR = 3, MP_ADD = 4, MP_MUL = 5, MP_SCALE = 6, MP_MULADD = 7 };   // = H2_EV_*
+constexpr int kMpDepth = 8;        // stack slots below the register-resident top (as evaluator.hip)
+constexpr int kMpThreads = 256;
+constexpr u32 kAbsent = 0xFFFFFFFFu;   // rank of an input value (or packed key) that its table column does not hold
+
+__device__ __forceinline__ void mp_spill(u32 *lds, int level, const fe &v) {
+#pragma unroll
+    for (int w = 0; w < 8; ++w) lds[(level * 8 + w) * kMpThreads + threadIdx.x] = v.v[w];
+}
+__device__ __forceinline__ fe mp_fill(const u32 *lds, int level) {
+    fe v;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) v.v[w] = lds[(level * 8 + w) * kMpThreads + threadIdx.x];
+    return v;
+}
+
+// adds a wave's ballot to the workgroup's counter (lane 0 of every wave), the workgroup's sum to the global one (thread 0)
+__device__ __forceinline__ void mp_count_wave(u32 *s_cnt, unsigned long long ballot) {
+    if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(s_cnt, (u32)__popcll(ballot));
+}
+
+// One lane per row, every program in turn.  fe_mulx and fe_add return fully reduced values and the columns hold values below p,
+// so `fe_is_zero` (all limbs zero) is exact for a Montgomery value: x R = 0 mod p iff x = 0.
+template <int F>
+__global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ programs, const u32 *__restrict__ offsets, u32 n_programs,
+                                                       const u32 *__restrict__ consts, const u32 *const *__restrict__ polys,
+                                                       const unsigned char *__restrict__ is_advice, unsigned log_len, u32 usable,
+                                                       unsigned long long *__restrict__ nz_bits, unsigned long long *__restrict__ po_bits,
+                                                       u32 *__restrict__ counts, u32 *const *__restrict__ values) {
+    extern __shared__ __attribute__((aligned(16))) u32 lds[];
+    const size_t len = (size_t)1 << log_len, i = (size_t)blockIdx.x * kMpThreads + threadIdx.x;
+    const size_t words = (len + 63) >> 6;
+    const bool active = i < len;          // 2^log_len < 64: the rest of the wave votes 0 (no early return: ballots and barriers below)
+    for (u32 p = 0; p < n_programs; ++p) {
+        fe top = fe_zero();
+        bool ptop = false;                // the top of the stack is Poison
+        u32 pbits = 0;                    // bit l: stack level l (spilled to LDS) is Poison
+        if (active) {
+            int depth = 0;
+            const u32 end = offsets[p + 1];
+            for (u32 pc = offsets[p]; pc < end; ++pc) {
+                const u32 word = programs[pc], op = word & 0xFFu, arg = word >> 8;
+                if (op == MP_POLY || op == MP_CONST) {
+                    if (depth > 0) {
+                        mp_spill(lds, depth - 1, top);
+                        pbits = (pbits & ~(1u << (depth - 1))) | ((ptop ? 1u : 0u) << (depth - 1));
+                    }
+                    ++depth;
+                    if (op == MP_POLY) {
+                        const int shift = (int)programs[++pc];
+                        const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| < len
+                        top = fe_load(polys[arg] + 8 * j);
+                        ptop = is_advice[arg] && j >= usable;                                             // dev.rs:529-533
+                    } else {
+                        top = fe_load(consts + 8 * (size_t)arg);
+                        ptop = false;
+                    }
+                } else if (op == MP_SCALE) {                                                              // Mul<F>, dev.rs:144-156
+                    const fe c = fe_load(consts + 8 * (size_t)arg);
+                    if (ptop && fe_is_zero(c)) {
+                        top = fe_zero();
+                        ptop = false;
+                    } else if (!ptop) {
+                        top = fe_mulx<F>(top, c);
+                    }
+                } else {
+                    fe below = mp_fill(lds, depth - 2);
+                    bool pbelow = (pbits >> (depth - 2)) & 1u;
+                    --depth;
+                    if (op == MP_MULADD) {                                                                // SCALE of the accumulator, then ADD
+                        const fe c = fe_load(consts + 8 * (size_t)arg);
+                        if (pbelow && fe_is_zero(c)) {
+                            below = fe_zero();
+                            pbelow = false;
+                        } else if (!pbelow) {
+                            below = fe_mulx<F>(below, c);
+                        }
+                    }
+                    if (op == MP_MUL) {                                                                   // dev.rs:126-142
+                        if (!pbelow && !ptop) {
+                            top = fe_mulx<F>(below, top);
+                        } else if ((!pbelow && fe_is_zero(below)) || (!ptop && fe_is_zero(top))) {
+                            top = fe_zero();
+                            ptop = false;
+                        } else {
+                            ptop = true;
+                        }
+                    } else {                                                                              // dev.rs:115-124
+                        ptop = ptop || pbelow;
+                        if (!ptop) top = fe_add<F>(below, top);
+                    }
+                }
+            }
+        }
+        const bool nz = active && !ptop && !fe_is_zero(top), po = active && ptop;
+        const unsigned long long bn = __ballot(nz), bp = __ballot(po);
+        if ((threadIdx.x & 63) == 0 && (i >> 6) < words) {
+            nz_bits[(size_t)p * words + (i >> 6)] = bn;
+            po_bits[(size_t)p * words + (i >> 6)] = bp;
+        }
+        if (values && active) fe_store(values[p] + 8 * i, ptop ? fe_zero() : top);
+        // counts: the stack's LDS is dead once every lane is through the program, so its first two words hold the workgroup's sums
+        // (the kernel's 64 KiB stay 64 KiB).  A workgroup with no bit set -- every one of a satisfied circuit -- pays one barrier.
+        if (!__syncthreads_or((bn | bp) != 0)) continue;
+        if (threadIdx.x == 0) lds[0] = lds[1] = 0;
+        __syncthreads();
+        mp_count_wave(&lds[0], bn);
+        mp_count_wave(&lds[1], bp);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (lds[0]) atomicAdd(&counts[2 * p], lds[0]);
+            if (lds[1]) atomicAdd(&counts[2 * p + 1], lds[1]);
+        }
+        __syncthreads();
+    }
+}
+
+// Slot `slot` of the packed keys of `rows` rows <- the rank of src[r] in the sorted table column S (n_s entries): its lower bound.
+// Equal values share a rank and the order of ranks is the order of values.  Poison ranks one past the largest (n_s).  An INPUT value
+// the column does not hold would share the rank of the next larger one: it gets kAbsent instead, which no table key carries.
+// init: the key is created ({rank, 0 ...}); the table's rows in [rows, padded) become the all-ones padding the sort wants.
+template <int F>
+__global__ void __launch_bounds__(256) mp_rank_column(const u32 *__restrict__ S, u32 n_s, const u32 *__restrict__ src,
+                                                      const unsigned long long *__restrict__ poison, int from_mont, u32 rows, u32 padded,
+                                                      u32 *__restrict__ packed, int slot, int init, int is_input) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) {
+        if (init && r < padded) key_store(packed + 8 * (size_t)r, key256{{~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u}});
+        return;
+    }
+    u32 rank;
+    if (poison && ((poison[r >> 6] >> (r & 63)) & 1ull)) {
+        rank = n_s;
+    } else {
+        fe v = fe_load(src + 8 * (size_t)r);
+        if (from_mont) v = fe_from_mont<F>(v);
+        key256 key;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) key.v[q] = v.v[q];
+        rank = lower_bound(S, n_s, key);
+        if (is_input && (rank >= n_s || !key_eq(key_load(S + 8 * (size_t)rank), key))) rank = kAbsent;
+    }
+    if (init) {
+        key256 k{{0, 0, 0, 0, 0, 0, 0, 0}};
+        k.v[6 - slot] = rank;
+        key_store(packed + 8 * (size_t)r, k);
+    } else {
+        packed[8 * (size_t)r + (6 - slot)] = rank;
+    }
+}
+
+// seven ranks are one key: the key's own rank among the sorted packed table keys becomes slot 0 of the next group
+__global__ void __launch_bounds__(256) mp_rank_packed(const u32 *__restrict__ S, u32 n_s, u32 rows, u32 *__restrict__ packed, int is_input) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const key256 key = key_load(packed + 8 * (size_t)r);
+    u32 rank = lower_bound(S, n_s, key);
+    if (is_input && (rank >= n_s || !key_eq(key_load(S + 8 * (size_t)rank), key))) rank = kAbsent;
+    key256 k{{0, 0, 0, 0, 0, 0, 0, 0}};
+    k.v[6] = rank;
+    key_store(packed + 8 * (size_t)r, k);
+}
+
+// fail bit of row r < rows: its packed key is not among the sorted packed table keys.  Covers ceil(n / 64) words.
+__global__ void __launch_bounds__(256) mp_member(const u32 *__restrict__ S, u32 n_s, const u32 *__restrict__ packed, u32 rows, u32 n,
+                                                 unsigned long long *__restrict__ fail_bits, u32 *__restrict__ count) {
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    bool fail = false;
+    if (r < rows) {
+        const key256 key = key_load(packed + 8 * (size_t)r);
+        const u32 p = lower_bound(S, n_s, key);
+        fail = p >= n_s || !key_eq(key_load(S + 8 * (size_t)p), key);
+    }
+    const unsigned long long b = __ballot(fail);
+    if ((threadIdx.x & 63) == 0 && (r >> 6) < (n + 63) / 64) fail_bits[r >> 6] = b;
+    mp_count_wave(&s_cnt, b);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(count, s_cnt);
+}
+
+// cell (c, r) against the cell its mapping entry names; blockIdx.y = c
+__global__ void __launch_bounds__(256) mp_permutation(const u32 *const *__restrict__ cols, const unsigned char *__restrict__ is_advice, u32 n_cols,
+                                                      const long long *__restrict__ mapping, unsigned log_len, u32 usable,
+                                                      unsigned long long *__restrict__ fail_bits, u32 *__restrict__ counts) {
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const size_t len = (size_t)1 << log_len, words = (len + 63) >> 6;
+    const u32 c = blockIdx.y;
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool fail = false;
+    if (r < len) {
+        const long long m = mapping[(size_t)c * len + r];
+        const unsigned long long c2 = (unsigned long long)m >> log_len;
+        const size_t r2 = (size_t)m & (len - 1);
+        if (m < 0 || c2 >= n_cols) {
+            fail = true;
+        } else {
+            const bool pa = is_advice[c] && r >= usable, pb = is_advice[c2] && r2 >= usable;
+            if (pa || pb) fail = !(pa && pb && cols[c] == cols[c2] && r == r2);       // CellValue::Poison(usize): equal to itself only
+            else fail = !fe_eq(fe_load(cols[c] + 8 * r), fe_load(cols[c2] + 8 * r2));
+        }
+    }
+    const unsigned long long b = __ballot(fail);
+    if ((threadIdx.x & 63) == 0 && (r >> 6) < words) fail_bits[(size_t)c * words + (r >> 6)] = b;
+    mp_count_wave(&s_cnt, b);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&counts[c], s_cnt);
+}
+
+struct MockContext {
+    std::mutex mu;
+    DevBuf prog, offsets, consts, ptrs, flags, vals;      // staging of the expression / permutation checks
+    std::vector<u32> offs;                                // program offsets as the kernel reads them
+    DevBuf sorted, pack_t, pack_i;                        // lookup check: a sorted column or sorted packed keys; packed table / input keys
+    void release_all() {
+        prog.release();
+        offsets.release();
+        consts.release();
+        ptrs.release();
+        flags.release();
+        vals.release();
+        sorted.release();
+        pack_t.release();
+        pack_i.release();
+    }
+};
+StreamContexts<MockContext> g_mock_ctxs;
+
+int ceil_log2(size_t n) {
+    int l = 0;
+    while (((size_t)1 << l) < n) ++l;
+    return l;
+}
+
+// what h2_evaluate_device asks of a Lagrange-basis program, minus LINEAR
+bool program_ok(const uint32_t *prog, size_t begin, size_t end, size_t n_consts, const void *const *d_polys, size_t n_polys, size_t len) {
+    if (begin >= end) return false;
+    int depth = 0, max_depth = 0;
+    for (size_t pc = begin; pc < end; ++pc) {
+        const uint32_t op = prog[pc] & 0xFFu, arg = prog[pc] >> 8;
+        switch (op) {
+            case MP_POLY: {
+                if (arg >= n_polys || pc + 1 >= end || !d_polys[arg]) return false;
+                const long long shift = (int)prog[++pc];
+                if (shift <= -(long long)len || shift >= (long long)len) return false;
+                ++depth;
+                break;
+            }
+            case MP_CONST:
+                if (arg >= n_consts) return false;
+                ++depth;
+                break;
+            case MP_SCALE:
+                if (arg >= n_consts || depth < 1) return false;
+                break;
+            case MP_MUL:
+            case MP_ADD:
+                if (depth < 2) return false;
+                --depth;
+                break;
+            case MP_MULADD:
+                if (arg >= n_consts || depth < 2) return false;
+                --depth;
+                break;
+            default:                      // MP_LINEAR included
+                return false;
+        }
+        max_depth = std::max(max_depth, depth);
+    }
+    return depth == 1 && max_depth <= kMpDepth + 1;
+}
+
+}  // namespace
+
+void mock_release_workspaces() { g_mock_ctxs.release_current_device(); }
+
+}  // namespace h2
+
+using namespace h2;
+
+extern "C" int h2_check_expressions_device(int field, const uint32_t *programs, const size_t *prog_offsets, size_t n_programs,
+                                           const uint64_t *consts, size_t n_consts, const void *const *d_polys, const uint8_t *poly_is_advice,
+                                           size_t n_polys, unsigned log_len, size_t usable_rows, void *d_nonzero_bits, void *d_poison_bits,
+                                           void *d_counts, void *const *d_values, void *stream) {
+    if ((field != H2_FP && field != H2_FQ) || !programs || !prog_offsets || n_programs == 0 || n_programs > 4096 || log_len > 30 ||
+        (n_consts && !consts) || (n_polys && (!d_polys || !poly_is_advice)) || !d_nonzero_bits || !d_poison_bits || !d_counts)
+        return H2_ERR_ARGS;
+    const size_t len = (size_t)1 << log_len;
+    if (usable_rows > len) return H2_ERR_ARGS;
+    const size_t n_words = prog_offsets[n_programs];
+    if (n_words == 0 || n_words > ((size_t)1 << 20)) return H2_ERR_ARGS;
+    for (size_t p = 0; p <= n_programs; ++p) {
+        if (prog_offsets[p] > n_words || (p && prog_offsets[p] <= prog_offsets[p - 1])) return H2_ERR_ARGS;
+    }
+    for (size_t p = 0; p < n_programs; ++p) {
+        if (!program_ok(programs, prog_offsets[p], prog_offsets[p + 1], n_consts, d_polys, n_polys, len)) return H2_ERR_ARGS;
+        if (d_values && !d_values[p]) return H2_ERR_ARGS;
+    }
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MockContext &cx = g_mock_ctxs.get(st);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    if ((rc = cx.prog.reserve(n_words * 4)) != H2_OK || (rc = cx.offsets.reserve((n_programs + 1) * 4)) != H2_OK ||
+        (rc = cx.consts.reserve(n_consts * 32 + 32)) != H2_OK || (rc = cx.ptrs.reserve(n_polys * 8 + 8)) != H2_OK ||
+        (rc = cx.flags.reserve(n_polys + 8)) != H2_OK || (rc = cx.vals.reserve(n_programs * 8)) != H2_OK)
+        return rc;
+    // the staging buffers belong to this (device, stream): the copies are stream-ordered after the kernel that last read them
+    H2_HIP(hipMemcpyAsync(cx.prog.ptr, programs + prog_offsets[0], (n_words - prog_offsets[0]) * 4, hipMemcpyHostToDevice, st));
+    cx.offs.resize(n_programs + 1);                  // lives in the context: the copy below may outlast this call
+    for (size_t p = 0; p <= n_programs; ++p) cx.offs[p] = (u32)(prog_offsets[p] - prog_offsets[0]);
+    H2_HIP(hipMemcpyAsync(cx.offsets.ptr, cx.offs.data(), cx.offs.size() * 4, hipMemcpyHostToDevice, st));
+    if (n_consts) H2_HIP(hipMemcpyAsync(cx.consts.ptr, consts, n_consts * 32, hipMemcpyHostToDevice, st));
+    if (n_polys) {
+        H2_HIP(hipMemcpyAsync(cx.ptrs.ptr, d_polys, n_polys * 8, hipMemcpyHostToDevice, st));
+        H2_HIP(hipMemcpyAsync(cx.flags.ptr, poly_is_advice, n_polys, hipMemcpyHostToDevice, st));
+    }
+    if (d_values) H2_HIP(hipMemcpyAsync(cx.vals.ptr, d_values, n_programs * 8, hipMemcpyHostToDevice, st));
+    H2_HIP(hipMemsetAsync(d_counts, 0, n_programs * 8, st));
+    const dim3 grid((unsigned)((len + kMpThreads - 1) / kMpThreads)), block(kMpThreads);
+    const size_t lds = (size_t)kMpDepth * 8 * kMpThreads * 4;
+    u32 *const *vals = d_values ? (u32 *const *)cx.vals.ptr : nullptr;
+    if (field == H2_FP)
+        hipLaunchKernelGGL((mp_check<FP>), grid, block, lds, st, cx.prog.as<u32>(), cx.offsets.as<u32>(), (u32)n_programs, cx.consts.as<u32>(),
+                           (const u32 *const *)cx.ptrs.ptr, cx.flags.as<unsigned char>(), log_len, (u32)usable_rows,
+                           (unsigned long long *)d_nonzero_bits, (unsigned long long *)d_poison_bits, (u32 *)d_counts, vals);
+    else
+        hipLaunchKernelGGL((mp_check<FQ>), grid, block, lds, st, cx.prog.as<u32>(), cx.offsets.as<u32>(), (u32)n_programs, cx.consts.as<u32>(),
+                           (const u32 *const *)cx.ptrs.ptr, cx.flags.as<unsigned char>(), log_len, (u32)usable_rows,
+                           (unsigned long long *)d_nonzero_bits, (unsigned long long *)d_poison_bits, (u32 *)d_counts, vals);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}
+
+extern "C" int h2_lookup_check_device(int field, const void *const *d_inputs, const void *const *d_input_poison, const void *const *d_tables,
+                                      const void *const *d_table_poison, size_t w, size_t n, size_t usable_rows, int form, void *d_fail_bits,
+                                      void *d_count, void *stream) {
+    if ((field != H2_FP && field != H2_FQ) || (form != H2_FORM_CANONICAL && form != H2_FORM_MONTGOMERY) || !d_inputs || !d_tables || w == 0 ||
+        w > 4096 || n == 0 || n > ((size_t)1 << 30) || usable_rows > n || !d_fail_bits || !d_count)
+        return H2_ERR_ARGS;
+    for (size_t c = 0; c < w; ++c) {
+        if (!d_inputs[c] || !d_tables[c]) return H2_ERR_ARGS;
+    }
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    H2_HIP(hipMemsetAsync(d_count, 0, 4, st));
+    const u32 rows = (u32)usable_rows, un = (u32)n;
+    const int log_p = ceil_log2(rows ? rows : 1);
+    const u32 padded = 1u << log_p;
+    MockContext &cx = g_mock_ctxs.get(st);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    if ((rc = cx.sorted.reserve((size_t)padded * 32)) != H2_OK || (rc = cx.pack_t.reserve((size_t)padded * 32)) != H2_OK ||
+        (rc = cx.pack_i.reserve((size_t)padded * 32)) != H2_OK)
+        return rc;
+    const dim3 block(256), grid_t((padded + 255) / 256), grid_i((rows + 255) / 256 + (rows ? 0 : 1));
+    const int from_mont = form == H2_FORM_MONTGOMERY;
+    u32 *S = nullptr;
+    // the packed table keys, sorted: what a full group's keys are ranked in and what the input keys are searched in at the end
+    auto sort_packed = [&]() -> int {
+        H2_HIP(hipMemcpyAsync(cx.sorted.ptr, cx.pack_t.ptr, (size_t)padded * 32, hipMemcpyDeviceToDevice, st));
+        return lookup_sort_padded(cx.sorted.as<u32>(), log_p, st);
+    };
+    int slot = 0;
+    for (size_t c = 0; rows && c < w; ++c) {
+        if (slot == 7) {
+            if ((rc = sort_packed()) != H2_OK) return rc;
+            S = cx.sorted.as<u32>();
+            hipLaunchKernelGGL(mp_rank_packed, grid_i, block, 0, st, (const u32 *)S, rows, rows, cx.pack_t.as<u32>(), 0);
+            hipLaunchKernelGGL(mp_rank_packed, grid_i, block, 0, st, (const u32 *)S, rows, rows, cx.pack_i.as<u32>(), 1);
+            slot = 1;
+        }
+        if ((rc = lookup_prepare_and_sort(field, d_tables[c], rows, form, cx.sorted, st)) != H2_OK) return rc;
+        S = cx.sorted.as<u32>();
+        const unsigned long long *pt = d_table_poison ? (const unsigned long long *)d_table_poison[c] : nullptr;
+        const unsigned long long *pi = d_input_poison ? (const unsigned long long *)d_input_poison[c] : nullptr;
+        const int init = c == 0;
+        if (field == H2_FP) {
+            hipLaunchKernelGGL((mp_rank_column<FP>), grid_t, block, 0, st, (const u32 *)S, rows, (const u32 *)d_tables[c], pt, from_mont, rows, padded,
+                               cx.pack_t.as<u32>(), slot, init, 0);
+            hipLaunchKernelGGL((mp_rank_column<FP>), grid_i, block, 0, st, (const u32 *)S, rows, (const u32 *)d_inputs[c], pi, from_mont, rows, 0u,
+                               cx.pack_i.as<u32>(), slot, init, 1);
+        } else {
+            hipLaunchKernelGGL((mp_rank_column<FQ>), grid_t, block, 0, st, (const u32 *)S, rows, (const u32 *)d_tables[c], pt, from_mont, rows, padded,
+                               cx.pack_t.as<u32>(), slot, init, 0);
+            hipLaunchKernelGGL((mp_rank_column<FQ>), grid_i, block, 0, st, (const u32 *)S, rows, (const u32 *)d_inputs[c], pi, from_mont, rows, 0u,
+                               cx.pack_i.as<u32>(), slot, init, 1);
+        }
+        ++slot;
+    }
+    if (rows && (rc = sort_packed()) != H2_OK) return rc;
+    const u32 lanes = ((un + 63) / 64) * 64;
+    hipLaunchKernelGGL(mp_member, dim3((lanes + 255) / 256), block, 0, st, (const u32 *)cx.sorted.ptr, rows, (const u32 *)cx.pack_i.ptr, rows, un,
+                       (unsigned long long *)d_fail_bits, (u32 *)d_count);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}
+
+extern "C" int h2_permutation_check_device(int field, const void *const *d_columns, const uint8_t *column_is_advice, size_t n_columns,
+                                           const void *d_mapping, unsigned log_len, size_t usable_rows, int form, void *d_fail_bits,
+                                           void *d_counts, void *stream) {
+    if ((field != H2_FP && field != H2_FQ) || (form != H2_FORM_CANONICAL && form != H2_FORM_MONTGOMERY) || !d_columns || !column_is_advice ||
+        n_columns == 0 || n_columns > 65535 || !d_mapping || log_len > 30 || usable_rows > ((size_t)1 << log_len) || !d_fail_bits || !d_counts)
+        return H2_ERR_ARGS;
+    for (size_t c = 0; c < n_columns; ++c) {
+        if (!d_columns[c]) return H2_ERR_ARGS;
+    }
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MockContext &cx = g_mock_ctxs.get(st);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    if ((rc = cx.ptrs.reserve(n_columns * 8)) != H2_OK || (rc = cx.flags.reserve(n_columns)) != H2_OK) return rc;
+    H2_HIP(hipMemcpyAsync(cx.ptrs.ptr, d_columns, n_columns * 8, hipMemcpyHostToDevice, st));
+    H2_HIP(hipMemcpyAsync(cx.flags.ptr, column_is_advice, n_columns, hipMemcpyHostToDevice, st));
+    H2_HIP(hipMemsetAsync(d_counts, 0, n_columns * 4, st));
+    const size_t len = (size_t)1 << log_len, lanes = ((len + 63) / 64) * 64;
+    hipLaunchKernelGGL(mp_permutation, dim3((unsigned)((lanes + 255) / 256), (unsigned)n_columns), dim3(256), 0, st, (const u32 *const *)cx.ptrs.ptr,
+                       cx.flags.as<unsigned char>(), (u32)n_columns, (const long long *)d_mapping, log_len, (u32)usable_rows,
+                       (unsigned long long *)d_fail_bits, (u32 *)d_counts);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}

@@ -450,6 +450,41 @@ int h2_sort_device(int field, void *d_a, size_t n, int form, void *stream);
 int h2_permute_expression_pair_device(int field, const void *d_input, const void *d_table, size_t n, int form,
                                       void *d_permuted_input, void *d_permuted_table, void *stream);
 
+/* ---- dev::MockProver::verify over device columns (halo2_proofs/src/dev.rs:576-904) ------------------------------- */
+/* Finding failures is the RESULT of these three calls, not an error: they return H2_OK and leave bit planes (one bit per row,
+ * row r = bit r % 64 of 64-bit word r / 64, ceil(2^log_len / 64) words per plane) and exact counts (uint32) in device memory.
+ * None of them synchronises `stream`: the caller reads the counts back (one small copy) and fetches a plane only when its count
+ * is not zero.  Planes and counts are overwritten, not accumulated.
+ *
+ * h2_check_expressions_device: n_programs programs in the bytecode of h2_evaluate_device (Lagrange basis; program p is the words
+ * [prog_offsets[p], prog_offsets[p + 1]) of `programs`, all sharing `consts`), each evaluated at every one of the 2^log_len rows
+ * with the poison tracking of dev.rs:104-156.  poly_is_advice[i] != 0 marks a registered vector as an advice column: its cell is
+ * Poison where the row it is read at (after rotation, modulo the length) is >= usable_rows.  Negation (a SCALE) and ADD propagate
+ * poison; MUL and SCALE turn Poison into Real(0) when the other factor is Real(0) / the constant 0.  H2_EV_MULADD b is
+ * SCALE b of the accumulator, then ADD.  H2_EV_LINEAR is refused (a lowered gate has no such term).
+ *   d_nonzero_bits, d_poison_bits: n_programs planes each; bit set where the program gives Real(x != 0) / Poison
+ *   d_counts: 2 * n_programs uint32: set bits of program p's non-zero plane at [2p], of its poison plane at [2p + 1]
+ *   d_values: null, or n_programs device vectors of 2^log_len elements that receive program p's value (Montgomery; 0 where poisoned) */
+int h2_check_expressions_device(int field, const uint32_t *programs, const size_t *prog_offsets, size_t n_programs, const uint64_t *consts,
+                                size_t n_consts, const void *const *d_polys, const uint8_t *poly_is_advice, size_t n_polys, unsigned log_len,
+                                size_t usable_rows, void *d_nonzero_bits, void *d_poison_bits, void *d_counts, void *const *d_values,
+                                void *stream);
+/* Exact tuple membership (dev.rs:709-833): input row r < usable_rows fails iff (inputs[0][r], ..., inputs[w-1][r]) does not occur
+ * among the tuples (tables[0][t], ..., tables[w-1][t]), t < usable_rows.  Tuples of canonical values are compared exactly; a
+ * component whose bit is set in its poison plane (d_*_poison[c], layout above; a null plane = never poisoned) is one more value,
+ * equal only to itself.  Vectors hold n >= usable_rows elements in `form`; any w >= 1.
+ *   d_fail_bits: one plane of ceil(n / 64) words (rows >= usable_rows clear);  d_count: one uint32 */
+int h2_lookup_check_device(int field, const void *const *d_inputs, const void *const *d_input_poison, const void *const *d_tables,
+                           const void *const *d_table_poison, size_t w, size_t n, size_t usable_rows, int form, void *d_fail_bits,
+                           void *d_count, void *stream);
+/* Copy constraints (dev.rs:835-881): cell (c, r) of n_columns vectors of 2^log_len elements must equal the cell
+ * d_mapping[c * 2^log_len + r] = c' * 2^log_len + r' (int64).  A cell of a column with column_is_advice[c] != 0 in a row
+ * >= usable_rows is poisoned: equal to itself only.  A mapping entry outside the table fails its cell.
+ *   d_fail_bits: n_columns planes;  d_counts: n_columns uint32 */
+int h2_permutation_check_device(int field, const void *const *d_columns, const uint8_t *column_is_advice, size_t n_columns,
+                                const void *d_mapping, unsigned log_len, size_t usable_rows, int form, void *d_fail_bits, void *d_counts,
+                                void *stream);
+
 /* ---- compressed points: the URS file and proof encoding --------------------------------------- */
 /* pasta_curves `to_bytes` as Params::write uses it (halo2_proofs/src/poly/commitment.rs:169-181) and write_point
  * (transcript.rs:183-187): out[32 i ..] = x little-endian with the parity of y in bit 255; identity = 32 zero bytes.
