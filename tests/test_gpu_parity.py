@@ -731,6 +731,8 @@ def test_best_multiexp_host_slices_range_pipeline(curve, canonical, affine):
 @pytest.mark.parametrize("env,args", [
     ({"H2_NTT_MAXR": "11"}, ["ntt", "5,11,13,21,22", "0", "1"]),          # 11-stage passes: 2^21 = 11 + 10, 2^22 = 11 + 11 (odd stage counts open with a radix-2 round)
     ({"H2_NTT_MAXR": "12"}, ["ntt", "12,23,24", "1", "1"]),               # 12-stage passes on Fq: 2^24 = 12 + 12, one 4096-row column per tile
+    ({"H2_NTT_FE9": "0"}, ["ntt", "1,2,5,10,11,13", "0", "1"]),             # the 8 x 32 kernel (the product's beyond 2^28): single passes, two passes of odd and even stage counts
+    ({"H2_NTT_FE9": "0", "H2_NTT_MAXR": "4"}, ["ntt", "12,13", "1", "1"]),  # the same on Fq in three and four passes: 4 + 4 + 4, 4 + 4 + 2 + 3
     # (H2_GENERIC_GROUPED=0: at 2^19 the grouped form runs first and returns, so without it the split switches are never read)
     ({"H2_GENERIC_GROUPED": "0", "H2_GENERIC_SPLIT": "0", "H2_MSM_HOST_CHUNKS": "1"}, ["msm", "19", "0"]),      # round 4's forms: one accumulate, one piece from host slices
     ({"H2_GENERIC_GROUPED": "0", "H2_GENERIC_SPLIT": "5"}, ["msm", "19", "1"]),                      # another cut of the window slices
@@ -743,6 +745,7 @@ def test_switched_forms_keep_parity(env, args):
     """The A/B arms left behind switches (live only in the laboratory build, build/ab/libhalo2_mi355x_ab.so, which the native driver loads here;
     read once per process): every one of them is the same
     mathematics and must stay bit-exact against the C oracle -- the 11- and 12-stage NTT passes that the default plan does not use, the
+    8 x 32 NTT kernel that the product reaches only beyond 2^28, the
     generic multiexp without its slice split or with another cut, the host-slice multiexp in one piece, in ragged ranges with plain
     launches, and with the runtime calls made by a helper thread."""
     import os
