@@ -107,6 +107,10 @@ SIGNATURES = {
     "h2_scale_add_device": ([C.c_int, vp, u64p, vp, C.c_size_t, C.c_int, vp], C.c_int),
     "h2_batch_invert": ([C.c_int, u64p, C.c_size_t, C.c_int], C.c_int),
     "h2_batch_invert_device": ([C.c_int, vp, C.c_size_t, C.c_int, vp], C.c_int),
+    "h2_assigned_to_field": ([C.c_int, u64p, u64p, u64p, C.c_size_t, C.c_int], C.c_int),
+    "h2_assigned_to_field_device": ([C.c_int, vp, vp, vp, C.c_size_t, C.c_int, vp], C.c_int),
+    "h2_selector_conflicts_device": ([vp, C.c_size_t, C.c_size_t, vp, vp], C.c_int),
+    "h2_selector_combine_device": ([C.c_int, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp], C.c_int),
     "h2_grand_product": ([C.c_int, u64p, C.c_size_t, u64p, C.c_int, u64p], C.c_int),
     "h2_grand_product_device": ([C.c_int, vp, C.c_size_t, u64p, C.c_int, vp, vp], C.c_int),
     "h2_evaluate_device": ([C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_uint,

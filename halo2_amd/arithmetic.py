@@ -329,3 +329,56 @@ def grand_product(m, n: int, init, field: int, form: int = FORM_MONTGOMERY):
     z = np.zeros((n, 4), dtype=np.uint64)
     check(lib().h2_grand_product(field, _p(m), n, _p(init), form, _p(z)), "h2_grand_product")
     return z
+
+
+def assigned_to_field(num, den, field: int, form: int = FORM_MONTGOMERY, out=None):
+    """`batch_invert_assigned` (poly.rs:135-180): num[i] / den[i] element-wise with x / 0 = 0, for every column of a proof concatenated
+    into one vector; den=None means every value is trivial.  torch: `out` (default: in place on `num`) may alias `num`."""
+    if den is not None and den.shape[0] != num.shape[0]:
+        raise ValueError("assigned_to_field: numerators and denominators differ in length")
+    if _is_torch(num):
+        out = num if out is None else out
+        if out.shape[0] != num.shape[0]:
+            raise ValueError("assigned_to_field: the output has another length")
+        check(lib().h2_assigned_to_field_device(field, _dev_vec(num).data_ptr(), None if den is None else _dev_vec(den).data_ptr(),
+                                                _dev_vec(out).data_ptr(), num.shape[0], form, _stream_ptr()), "h2_assigned_to_field_device")
+        return out
+    num = _np(num, 4)
+    den = None if den is None else _np(den, 4)
+    res = np.zeros_like(num)
+    check(lib().h2_assigned_to_field(field, _p(num), None if den is None else _p(den), _p(res), num.shape[0], form), "h2_assigned_to_field")
+    return res
+
+
+def _dev_words(t, dtype):
+    assert t.is_cuda and t.is_contiguous() and t.dtype == dtype
+    return t
+
+
+def selector_conflicts(bits):
+    """The exclusion matrix of selector compression (compress_selectors.rs:103-124).  bits: an (S, ceil(n / 32)) int32 CUDA tensor,
+    row r of selector s is bit r % 32 of word r / 32.  Returns the symmetric (S, S) uint8 device matrix, zero on the diagonal."""
+    import torch
+    _dev_words(bits, torch.int32)
+    s = bits.shape[0]
+    out = torch.empty((s, s), dtype=torch.uint8, device=bits.device)
+    check(lib().h2_selector_conflicts_device(bits.data_ptr() if bits.numel() else None, s, bits.shape[1], out.data_ptr() if s else None,
+                                             _stream_ptr()), "h2_selector_conflicts_device")
+    return out
+
+
+def selector_combine(bits, roots, columns, n: int, n_columns: int, field: int):
+    """The combination assignments (compress_selectors.rs:180-213): an (n_columns, n, 4) Montgomery device tensor whose [c][r] is
+    roots[s] for the selector s with columns[s] == c that is enabled on row r, else 0.  bits as `selector_conflicts` takes them."""
+    import torch
+    _dev_words(bits, torch.int32)
+    s = bits.shape[0]
+    if len(roots) != s or len(columns) != s or bits.shape[1] != (n + 31) // 32:
+        raise ValueError("selector_combine: one root and one column per selector, ceil(n / 32) words each")
+    up = lambda v: torch.tensor([int(x) for x in v], dtype=torch.int32, device=bits.device)
+    d_roots, d_columns = up(roots), up(columns)
+    out = torch.empty((n_columns, n, 4), dtype=torch.int64, device=bits.device)
+    check(lib().h2_selector_combine_device(field, bits.data_ptr() if s else None, d_roots.data_ptr() if s else None,
+                                           d_columns.data_ptr() if s else None, s, n, out.data_ptr() if out.numel() else None, n_columns,
+                                           _stream_ptr()), "h2_selector_combine_device")
+    return out

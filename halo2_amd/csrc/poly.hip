@@ -193,6 +193,73 @@ template <int F> __global__ void __launch_bounds__(kPT) poly_batch_invert(u32 *_
     tile_store(sh, a, base, 0, n, 0);
 }
 
+// out[i] = num[i] / den[i], x / 0 = 0: `batch_invert_assigned` (poly.rs:135-180) over every column of a proof at once.  The sibling of
+// poly_batch_invert: the same tile and the same two-level trick over the DENOMINATORS, which are read once into LDS and never written
+// back; a denominator of zero or of one stays out of the inversion product (the reference skips its Zero / Trivial values the same way).
+// The inverses stay in LDS (Montgomery form, 0 for a zero and R for a one) and the numerator multiply runs in the coalesced store
+// loop: each lane reads num[i] and writes out[i] of the same i, so `out` may alias `num`.
+template <int F> __global__ void __launch_bounds__(kPT) poly_assigned_to_field(const u32 *num, const u32 *__restrict__ den, u32 *out, size_t n,
+                                                                                int canonical) {
+    extern __shared__ __attribute__((aligned(16))) u32 lds[];
+    u32 *sh = lds, *sc = lds + kPT * kPitch;
+    const size_t base = (size_t)blockIdx.x * kTile;
+    tile_load(sh, den, base, n, 0);
+    __syncthreads();
+    u32 *row = sh + threadIdx.x * kPitch;
+    const fe raw_one = canonical ? fe{{1, 0, 0, 0, 0, 0, 0, 0}} : fe_one<F>();
+    fe pre[kPC];
+    fe run = fe_one<F>();
+    u32 skip = 0;                                             // bit e: element e is 0 or 1 and takes no part in the inversion
+#pragma unroll
+    for (int e = 0; e < kPC; ++e) {
+        fe v = lds_get(row + 8 * e);
+        pre[e] = run;
+        if (fe_is_zero(v)) { skip |= 1u << e; continue; }
+        if (fe_eq(v, raw_one)) {
+            skip |= 1u << e;
+            if (canonical) lds_put(row + 8 * e, fe_one<F>());
+            continue;
+        }
+        if (canonical) { v = fe_to_mont<F>(v); lds_put(row + 8 * e, v); }
+        run = fe_mulx<F>(run, v);
+    }
+    lds_put(sc + threadIdx.x * kSPitch, run);
+    __syncthreads();
+    const u32 g0 = threadIdx.x & ~(u32)(kInvGroup - 1), gl = threadIdx.x & (kInvGroup - 1);
+    fe before = fe_one<F>(), after = fe_one<F>();
+#pragma unroll
+    for (int q = 0; q < kInvGroup; ++q) {
+        const fe rq = lds_get(sc + (g0 + q) * kSPitch);
+        if (q < (int)gl) before = fe_mulx<F>(before, rq);
+        if (q > (int)gl) after = fe_mulx<F>(after, rq);
+    }
+    const fe others = fe_mulx<F>(before, after);
+    fe total = fe_one<F>();
+    if (threadIdx.x < kPT / kInvGroup) {
+#pragma unroll
+        for (int q = 0; q < kInvGroup; ++q) total = fe_mulx<F>(total, lds_get(sc + (threadIdx.x * kInvGroup + q) * kSPitch));
+    }
+    __syncthreads();
+    if (threadIdx.x < kPT / kInvGroup) lds_put(sc + threadIdx.x * kSPitch, fe_inv<F>(total));
+    __syncthreads();
+    fe inv = fe_mulx<F>(lds_get(sc + (threadIdx.x / kInvGroup) * kSPitch), others);       // = 1 / run
+#pragma unroll
+    for (int e = kPC - 1; e >= 0; --e) {
+        if ((skip >> e) & 1) continue;
+        const fe v = lds_get(row + 8 * e);
+        lds_put(row + 8 * e, fe_mulx<F>(inv, pre[e]));
+        inv = fe_mulx<F>(inv, v);
+    }
+    __syncthreads();
+    for (int it = 0; it < kPC; ++it) {
+        const u32 j = it * kPT + threadIdx.x;
+        const size_t gi = base + j;
+        if (gi >= n) continue;
+        const fe d = lds_get(sh + (j / kPC) * kPitch + (j % kPC) * 8);
+        fe_store(out + 8 * gi, fe_mulx<F>(fe_load(num + 8 * gi), d));       // Montgomery inverse: the product keeps the form of num
+    }
+}
+
 // ---- kate division: suffix Horner scan H_i = a_i + b H_{i+1};  quotient q_{i-1} = H_i for i = 1 .. n-1 -------------
 // pw[k] = b^(kPC * 2^k) for k = 0..7.  FINAL = false: agg[blk] = H at the tile's first element assuming nothing above.
 template <int F, bool FINAL>
@@ -402,6 +469,8 @@ int poly_kernel_attrs() {
     H2_LDS_ATTR((poly_product_tile<FQ, true>), kScanLds);
     H2_LDS_ATTR((poly_batch_invert<FP>), kScanLds);
     H2_LDS_ATTR((poly_batch_invert<FQ>), kScanLds);
+    H2_LDS_ATTR((poly_assigned_to_field<FP>), kScanLds);
+    H2_LDS_ATTR((poly_assigned_to_field<FQ>), kScanLds);
     H2_LDS_ATTR((poly_powers<FP>), kTileLds);
     H2_LDS_ATTR((poly_powers<FQ>), kTileLds);
 #undef H2_LDS_ATTR
@@ -662,6 +731,35 @@ extern "C" int h2_batch_invert(int field, uint64_t *a, size_t n, int form) {
     if ((rc = s.up(a, n * 32, &d_a)) != H2_OK) return rc;
     if ((rc = h2_batch_invert_device(field, d_a, n, form, nullptr)) != H2_OK) return rc;
     H2_HIP(hipMemcpy(a, d_a, n * 32, hipMemcpyDeviceToHost));
+    return H2_OK;
+}
+
+extern "C" int h2_assigned_to_field_device(int field, const void *d_num, const void *d_den, void *d_out, size_t n_total, int form, void *stream) {
+    if (bad_field_form(field, form) || (n_total && (!d_num || !d_out)) || n_total > kMaxLen) return H2_ERR_ARGS;
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    if (!n_total) return H2_OK;
+    if (!d_den) {                                                  // every value is trivial
+        if (d_out != d_num) H2_HIP(hipMemcpyAsync(d_out, d_num, n_total * 32, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return H2_OK;
+    }
+    if ((rc = poly_kernel_attrs()) != H2_OK) return rc;
+    H2_FIELD_LAUNCH(field, poly_assigned_to_field, dim3((unsigned)((n_total + kTile - 1) / kTile)), dim3(kPT), kScanLds, (hipStream_t)stream,
+                    (const u32 *)d_num, (const u32 *)d_den, (u32 *)d_out, n_total, form == H2_FORM_CANONICAL ? 1 : 0);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}
+
+extern "C" int h2_assigned_to_field(int field, const uint64_t *num, const uint64_t *den, uint64_t *out, size_t n_total, int form) {
+    if (bad_field_form(field, form) || (n_total && (!num || !out)) || n_total > kMaxLen) return H2_ERR_ARGS;
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    if (!n_total) return H2_OK;
+    Staged s;
+    void *d_num, *d_den = nullptr;
+    if ((rc = s.up(num, n_total * 32, &d_num)) != H2_OK || (den && (rc = s.up(den, n_total * 32, &d_den)) != H2_OK)) return rc;
+    if ((rc = h2_assigned_to_field_device(field, d_num, d_den, d_num, n_total, form, nullptr)) != H2_OK) return rc;
+    H2_HIP(hipMemcpy(out, d_num, n_total * 32, hipMemcpyDeviceToHost));
     return H2_OK;
 }
 

@@ -239,6 +239,17 @@ class MockProver:
         self._counts = None
         return self
 
+    @classmethod
+    def run_circuit(cls, k: int, circuit, instances, field: int, device=None) -> "MockProver":
+        """dev.rs:463-574 from a `halo2_amd.circuit.Circuit`: configure, synthesize with the witness (SimpleFloorPlanner), invert the
+        assigned cells' denominators, compress the selectors, lower, `run`.  instances: the instance columns, integer lists."""
+        from . import circuit as front
+        instances = [list(col) for col in instances]
+        cs, assembly, _ = front.synthesize(circuit, k, field, fixed=True, advice=True, instances=instances)
+        fixed = front.fixed_columns_of(assembly, cs, device)
+        advice = assembly.columns_to_field(assembly.advice, device)
+        return cls.run(k, front.lower(cs), fixed, advice, instances, assembly.permutation.flat(), field, device)
+
     # ---- the three device checks: enqueue only ---------------------------------------------------------------------------------------
     def _check_expressions(self, linked, n_programs: int, store: bool):
         import torch

@@ -2,8 +2,8 @@
 turns fixed columns and the copy-constraint mapping into the three bases (plonk/keygen.rs:296-380, permutation/keygen.rs:163-190),
 for circuit instances whose columns are already assigned (one or several per proof).  This module is orchestration: it sequences the device
 arguments (`halo2_amd.{permutation, lookup, vanishing, multiopen, opening}`), the column commits / iFFTs / coset FFTs and the
-transcript exactly in the reference's order.  What it does not do is run a `Circuit` (floor planning, region assignment,
-selector compression, `Expression<F>` construction): the caller hands over the constraint system in lowered form --
+transcript exactly in the reference's order.  Running a `Circuit` (floor planning, region assignment, selector compression,
+`Expression<F>` construction) is `halo2_amd.circuit`, which ends in the calls below; here the constraint system arrives in lowered form --
 
 * a gate polynomial or a lookup expression is a callable `cells -> value` using `cells.fixed(col, rot)`, `cells.advice(col, rot)`,
   `cells.instance(col, rot)` and `+ - *` (integers are constants).  The prover applies it to `Ast` leaves, a verifier to
@@ -11,7 +11,8 @@ selector compression, `Expression<F>` construction): the caller hands over the c
 * queries are (column, rotation) lists in the order the reference's `ConstraintSystem` would have recorded them.
 
 `vk_repr` stands in for `VerifyingKey::transcript_repr` (plonk.rs:94-101; a hash of the Rust Debug print of the pinned
-key, not reproducible without the reference's types).  torch is plumbing; all arithmetic goes through the C ABI."""
+key, which callables cannot produce: `halo2_amd.circuit.keygen_pk` can, from its expression trees).  torch is plumbing; all
+arithmetic goes through the C ABI."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

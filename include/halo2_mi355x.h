@@ -408,11 +408,28 @@ int h2_scale_add_device(int field, void *d_a, const uint64_t *x, const void *d_b
  * a[i] = 1 / a[i]; zeros are left zero. */
 int h2_batch_invert(int field, uint64_t *a, size_t n, int form);
 int h2_batch_invert_device(int field, void *d_a, size_t n, int form, void *stream);
+/* batch_invert_assigned (halo2_proofs/src/poly.rs:135-180; plonk/keygen.rs:221, plonk/prover.rs:291): out[i] = num[i] / den[i] with
+ * x / 0 = 0; a denominator equal to one stays out of the inversion, as the reference's Trivial values do.  den == NULL: every value is
+ * trivial, out = num.  All columns of a proof go concatenated into one call (n_total elements).  out may alias num. */
+int h2_assigned_to_field(int field, const uint64_t *num, const uint64_t *den, uint64_t *out, size_t n_total, int form);
+int h2_assigned_to_field_device(int field, const void *d_num, const void *d_den, void *d_out, size_t n_total, int form, void *stream);
 /* the running product of a permutation / lookup argument (plonk/permutation/prover.rs:147-153,
  * plonk/lookup/prover.rs:318-326): z[0] = init, z[i] = z[i-1] * m[i-1] for 0 < i < n.  m holds at least
  * n - 1 factors; z has n elements and must not alias m. */
 int h2_grand_product(int field, const uint64_t *m, size_t n, const uint64_t *init, int form, uint64_t *z);
 int h2_grand_product_device(int field, const void *d_m, size_t n, const uint64_t *init, int form, void *d_z, void *stream);
+
+/* ---- selector compression (plonk/circuit/compress_selectors.rs:51-227), the parts that scale with the circuit ---- */
+/* Activations are bit-packed: selector s owns the n_words = ceil(n / 32) words bits[s * n_words ...], row r is bit r % 32 of word
+ * r / 32, bits past n are zero.  All pointers are device pointers.
+ * h2_selector_conflicts_device: the exclusion matrix of `process` (:103-124) -- out[i * S + j] = 1 where selectors i and j are
+ * both enabled on some row, else 0; symmetric, zero diagonal; S = n_selectors bytes per row.
+ * h2_selector_combine_device: the combination assignments (:180-213) -- out_columns is n_columns vectors of n field elements
+ * (Montgomery form), out_columns[c][r] = root_of_selector[s] for the one selector s with column_of_selector[s] == c that is
+ * enabled on row r, else 0 (the conflict matrix guarantees there is at most one). */
+int h2_selector_conflicts_device(const uint32_t *bits, size_t n_selectors, size_t n_words, uint8_t *out, void *stream);
+int h2_selector_combine_device(int field, const uint32_t *bits, const uint32_t *root_of_selector, const uint32_t *column_of_selector,
+                               size_t n_selectors, size_t n, void *out_columns, size_t n_columns, void *stream);
 
 /* ---- expression evaluation between the coset FFTs and the quotient iFFT ----------------------- */
 /* poly::Evaluator::evaluate (halo2_proofs/src/poly/evaluator.rs:129-228): one expression tree over registered
