@@ -146,6 +146,9 @@ SIGNATURES = {
     "h2_profile_read": ([C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)], C.c_int),
     "h2_profile_read_busy": ([C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)], C.c_int),
     "h2_debug_timeline": ([C.POINTER(C.c_ulonglong), C.c_uint], C.c_int),
+    "h2_poseidon_permute_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_poseidon_hash_device": ([C.c_int, vp, C.c_size_t, C.c_size_t, vp, vp], C.c_int),
+    "h2_poseidon_trace_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
 }
 
 

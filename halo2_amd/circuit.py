@@ -15,7 +15,8 @@ synthesis is the existing prover.  A key made here prints as the reference's `Pi
 `vk_repr` is the reference's `transcript_repr` (plonk.rs:75-101).
 
 One extension: `Region.assign_advice_column` / `assign_fixed_column` assign a whole vector of rows in one call (a 2^20-row column
-is otherwise a million Python calls); they lay out exactly as that many single assignments would."""
+is otherwise a million Python calls) and `Region.enable_selector_rows` enables a selector on an array of offsets; they lay out
+exactly as that many single calls would."""
 from __future__ import annotations
 
 import hashlib
@@ -755,6 +756,12 @@ class Assembly:
             self._row(row)
             self.selectors[selector.index][row] = True
 
+    def enable_selector_rows(self, selector: Selector, rows: np.ndarray) -> None:
+        if self.collect_fixed and rows.size:
+            if int(rows.min()) < 0 or int(rows.max()) >= self.usable:
+                raise NotEnoughRowsAvailable(self.k)
+            self.selectors[selector.index][rows] = True
+
     def query_instance(self, column: Column, row: int) -> Value:
         self._row(row)
         if self.instances is None:
@@ -889,6 +896,16 @@ class Region:
         self._note(selector, offset)
         if self.layouter:
             self.layouter.cs.enable_selector(selector, self._start() + offset)
+
+    def enable_selector_rows(self, selector: Selector, offsets) -> None:
+        """`enable_selector` on every offset of an integer array in one call."""
+        offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size:
+            if int(offsets.min()) < 0:
+                raise ValueError("a negative offset")
+            self._note(selector, int(offsets.max()))
+            if self.layouter:
+                self.layouter.cs.enable_selector_rows(selector, self._start() + offsets)
 
     def _assign(self, column: Column, offset: int, to) -> AssignedCell:
         self._note(column, offset)

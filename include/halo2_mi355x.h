@@ -574,6 +574,27 @@ int h2_msm_last_path(void *stream, int *path, int *groups, unsigned *acc_lanes, 
  * 1 = sort, 2 = accumulate, 3 = reduce, 4 = done.  Returns the pair count, or -1 when the timeline is off. */
 int h2_debug_timeline(unsigned long long *out, unsigned cap);
 
+/* ---- Poseidon P128Pow5T3 (halo2_poseidon: width 3, rate 2, R_F = 8, R_P = 56, S-box x^5), batched ---- */
+/* All pointers are device pointers; every element is 4 x u64 Montgomery limbs; one lane per permutation / message.  The constants
+ * are those halo2_amd/poseidon_spec.py generates (csrc/poseidon_consts.inc).  Bad arguments -- an unknown field, a null pointer
+ * with a nonzero count, a count above 2^30 -- return H2_ERR_ARGS before anything touches the device; a count of 0 launches nothing.
+ *
+ * h2_poseidon_permute_device: d_states holds n states of 3 elements, d_out receives the n permuted states.  d_out may be d_states
+ * (in place); any other overlap is not allowed. */
+int h2_poseidon_permute_device(int field, const void *d_states, size_t n, void *d_out, void *stream);
+/* h2_poseidon_hash_device: the reference's Hash<_, P128Pow5T3, ConstantLength<len>, 3, 2> of n messages of `len` elements each
+ * (d_messages: n * len elements, message after message).  The state starts as (0, 0, len * 2^64); two elements are added to words 0
+ * and 1 per permutation, the last block zero-padded; d_out[i] is word 0 after the last permutation of message i.  len = 0,
+ * len >= 2^32 and n * len > 2^40 are H2_ERR_ARGS.  d_out must not overlap d_messages. */
+int h2_poseidon_hash_device(int field, const void *d_messages, size_t n, size_t len, void *d_out, void *stream);
+/* h2_poseidon_trace_device: the Pow5 chip's witness (halo2_gadgets poseidon/pow5.rs) of `count` permutations of the states in
+ * d_states (3 elements each).  d_columns is ONE buffer of 4 vectors of 37 * count elements, one after the other: state0, state1,
+ * state2, partial_sbox.  Rows 37 i .. 37 i + 36 of the state vectors belong to permutation i: row 0 the input, rows 1-4 the state
+ * after full rounds 0-3, rows 5-32 after each pair of partial rounds, rows 33-36 after full rounds 60-63 (row 36 is the output).
+ * Rows 37 i + 4 .. 37 i + 31 of partial_sbox hold (state0 + rc)^5 of the first round of that row's pair, before the MDS; its other
+ * rows are zero.  Every one of the 4 * 37 * count elements is written.  d_columns must not overlap d_states. */
+int h2_poseidon_trace_device(int field, const void *d_states, size_t count, void *d_columns, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
