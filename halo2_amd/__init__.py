@@ -9,6 +9,7 @@ from .arithmetic import (assigned_to_field, batch_invert, best_fft, best_fft_bat
 from .commitment import Blind, Params, hash_to_curve, lagrange_basis, points_from_bytes, points_to_bytes  # noqa: F401
 from .domain import EvaluationDomain  # noqa: F401
 from . import poseidon  # noqa: F401
+from . import sinsemilla  # noqa: F401
 from .poly import Coeff, ExtendedLagrangeCoeff, LagrangeCoeff, Polynomial  # noqa: F401
 from .circuit import (Assigned, Circuit, Column, ConstraintSystem, Expression, Rotation, Selector, SimpleFloorPlanner, TableColumn,  # noqa: F401
                       Value, create_proof, keygen_pk, keygen_vk, lower)

@@ -149,6 +149,9 @@ SIGNATURES = {
     "h2_poseidon_permute_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
     "h2_poseidon_hash_device": ([C.c_int, vp, C.c_size_t, C.c_size_t, vp, vp], C.c_int),
     "h2_poseidon_trace_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_sinsemilla_hash_device": ([vp, C.c_size_t, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_merkle_layer_device": ([C.c_uint, vp, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_trace_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
 }
 
 

@@ -1,0 +1,482 @@
+"""The Sinsemilla gadget of halo2_gadgets (src/sinsemilla.rs, sinsemilla/chip.rs, chip/hash_to_point.rs, chip/generator_table.rs,
+sinsemilla/merkle.rs, merkle/chip.rs) against `halo2_amd.circuit`: `SinsemillaChip`, `Message` / `MessagePiece`, `HashDomain`,
+`MerkleChip` and `MerklePath`, over the Pallas base field with public Q.
+
+The mirror assigns cell by cell with host `Assigned` rationals -- the same regions, offsets, gate and lookup shapes and copy
+constraints as the reference, one message word per row:
+
+    config = SinsemillaChip.configure(meta, advices[5], witness_pieces, fixed_y_q, lookup(3), range_check)
+    SinsemillaChip.load(config, layouter)
+    point, zs = SinsemillaChip(config).hash_to_point(layouter, Q, [piece, ...])
+
+What the reference does not have is the bulk path: `SinsemillaChip.hash_to_point_many` lays `count` hashes of one piece structure
+back to back in ONE region whose five advice columns come from the device (`halo2_amd.sinsemilla.trace`), with the q_sinsemilla2
+pattern tiled; cell for cell the layout of `count` calls of `hash_to_point`.
+
+The generator table is `halo2_amd.sinsemilla`'s, built on the device once per process; `table=` injects another (1024 (x, y) pairs)."""
+from __future__ import annotations
+
+import numpy as np
+
+from .. import fields
+from .. import sinsemilla as primitive
+from ..circuit import Assigned, AssignedCell, Cell, Column, ConstraintSystem, Expression, Rotation, Synthesis
+from .utilities import CondSwapChip, K, LookupRangeCheckConfig, RangeConstrained, i2lebsp, load_private, value_int
+
+FP = 0
+C_MAX = primitive.C_MAX
+PIECE_MAX_WORDS = 25                                                          # floor(CAPACITY / K) = floor(254 / 10)
+
+
+class GeneratorTableConfig:
+    def __init__(self, table_idx, table_x, table_y):
+        self.table_idx, self.table_x, self.table_y = table_idx, table_x, table_y
+
+
+class DoubleAndAdd:
+    """ecc/chip/mul/incomplete.rs:28-56: the columns of the merged double-and-add and its two derived expressions."""
+
+    def __init__(self, x_a, x_p, lambda_1, lambda_2):
+        self.x_a, self.x_p, self.lambda_1, self.lambda_2 = x_a, x_p, lambda_1, lambda_2
+
+    def x_r(self, cells, rotation) -> Expression:
+        x_a = cells.query_advice(self.x_a, rotation)
+        x_p = cells.query_advice(self.x_p, rotation)
+        lambda_1 = cells.query_advice(self.lambda_1, rotation)
+        return lambda_1.square() - x_a - x_p
+
+    def Y_A(self, cells, rotation) -> Expression:                             # noqa: N802 -- the reference's name; lacks the factor 1/2
+        x_a = cells.query_advice(self.x_a, rotation)
+        lambda_1 = cells.query_advice(self.lambda_1, rotation)
+        lambda_2 = cells.query_advice(self.lambda_2, rotation)
+        return (lambda_1 + lambda_2) * (x_a - self.x_r(cells, rotation))
+
+
+class SinsemillaConfig:
+    def __init__(self, modulus, q_sinsemilla1, q_sinsemilla2, q_sinsemilla4, fixed_y_q, double_and_add, bits, witness_pieces,
+                 generator_table, lookup_config, table, injected_table=None):
+        self.modulus = modulus
+        self.q_sinsemilla1, self.q_sinsemilla2, self.q_sinsemilla4, self.fixed_y_q = q_sinsemilla1, q_sinsemilla2, q_sinsemilla4, fixed_y_q
+        self.double_and_add, self.bits, self.witness_pieces = double_and_add, bits, witness_pieces
+        self.generator_table, self.lookup_config = generator_table, lookup_config
+        self.table, self.injected_table = table, injected_table              # 1024 (x, y) integers; what the caller passed, if anything
+
+    def advices(self) -> list:
+        d = self.double_and_add
+        return [d.x_a, d.x_p, self.bits, d.lambda_1, d.lambda_2]
+
+    def q_s3(self, cells) -> Expression:
+        """q_s3 = q_s2 (q_s2 - 1)"""
+        q_s2 = cells.query_fixed(self.q_sinsemilla2)
+        return q_s2 * (q_s2 - Expression.constant(1))
+
+
+class MessagePiece:
+    """sinsemilla/message.rs: a witnessed field element carrying num_words K-bit words."""
+
+    def __init__(self, cell_value: AssignedCell, num_words: int):
+        assert 1 <= num_words <= PIECE_MAX_WORDS
+        self.cell_value, self.num_words = cell_value, num_words
+
+    def field_elem(self, modulus: int):
+        return value_int(self.cell_value.value(), modulus)
+
+    @staticmethod
+    def from_field_elem(chip, layouter, field_elem, num_words: int) -> "MessagePiece":
+        return chip.witness_message_piece(layouter, field_elem, num_words)
+
+    @staticmethod
+    def from_subpieces(chip, layouter, subpieces) -> "MessagePiece":
+        """sinsemilla.rs:256-278: the subpieces (RangeConstrained integers) concatenated, low bits first; assigned, not constrained"""
+        elem, total_bits = 0, 0
+        for sub in subpieces:
+            assert total_bits < 64
+            elem = None if elem is None or sub.inner is None else elem + (sub.inner << total_bits)
+            total_bits += sub.num_bits
+        assert total_bits % K == 0
+        return MessagePiece.from_field_elem(chip, layouter, elem, total_bits // K)
+
+
+Message = list                                                                # sinsemilla/message.rs Message: the pieces in order
+
+
+class NonIdentityEccPoint:
+    def __init__(self, x: AssignedCell, y: AssignedCell):
+        self._x, self._y = x, y
+
+    def x(self) -> AssignedCell:
+        return self._x
+
+    def y(self) -> AssignedCell:
+        return self._y
+
+
+class HashMany:
+    """What `hash_to_point_many` returns: the cells of hash i by position.  outputs: (count, 2, 4) Montgomery x and y of the hashes
+    (None without a witness)."""
+
+    def __init__(self, region_index, config, count, num_words, outputs):
+        self.region_index, self.config, self.count, self.num_words, self.outputs = region_index, config, count, list(num_words), outputs
+        self.rows = sum(num_words) + 1
+        self.piece_offsets = [sum(num_words[:k]) for k in range(len(num_words))]
+
+    def x_a(self, i: int) -> Cell:
+        return Cell(self.region_index, self.rows * i + self.rows - 1, self.config.double_and_add.x_a)
+
+    def y_a(self, i: int) -> Cell:
+        return Cell(self.region_index, self.rows * i + self.rows - 1, self.config.double_and_add.lambda_1)
+
+    def z(self, i: int, piece: int, j: int) -> Cell:
+        """the running sum z_j of that piece of hash i (z_0 is the copy of the piece)"""
+        if not 0 <= j < self.num_words[piece]:
+            raise IndexError(j)
+        return Cell(self.region_index, self.rows * i + self.piece_offsets[piece] + j, self.config.bits)
+
+
+class SinsemillaChip:
+    def __init__(self, config: SinsemillaConfig):
+        self.config = config
+
+    @staticmethod
+    def load(config: SinsemillaConfig, layouter) -> None:
+        config.lookup_config.load(config.generator_table, layouter, config.table)
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, advices, witness_pieces: Column, fixed_y_q: Column, lookup, range_check: LookupRangeCheckConfig,
+                  table=None) -> SinsemillaConfig:
+        """chip.rs:170-288 with allow_init_from_private_point = false.  All five advice columns become equality-enabled."""
+        advices = list(advices)
+        assert len(advices) == 5
+        for advice in advices:
+            meta.enable_equality(advice)
+        injected = table
+        table = primitive.generator_table_ints(table)
+        config = SinsemillaConfig(
+            meta.modulus, q_sinsemilla1=meta.complex_selector(), q_sinsemilla2=meta.fixed_column(), q_sinsemilla4=meta.selector(),
+            fixed_y_q=fixed_y_q, double_and_add=DoubleAndAdd(advices[0], advices[1], advices[3], advices[4]), bits=advices[2],
+            witness_pieces=witness_pieces, generator_table=GeneratorTableConfig(*lookup), lookup_config=range_check, table=table,
+            injected_table=injected)
+        dna = config.double_and_add
+
+        def generator_lookup(cells):                                          # generator_table.rs:46-82
+            q_s1 = cells.query_selector(config.q_sinsemilla1)
+            q_s2 = cells.query_fixed(config.q_sinsemilla2)
+            q_s3 = config.q_s3(cells)
+            q_run = q_s2 - q_s3
+            z_cur = cells.query_advice(config.bits, Rotation.cur())
+            z_next = cells.query_advice(config.bits, Rotation.next())
+            word = z_cur - (q_run * z_next * (1 << K))                        # m_{i+1} = z_i - 2^K q_run z_{i+1}
+            x_p = cells.query_advice(dna.x_p, Rotation.cur())
+            lambda1 = cells.query_advice(dna.lambda_1, Rotation.cur())
+            x_a = cells.query_advice(dna.x_a, Rotation.cur())
+            y_a = dna.Y_A(cells, Rotation.cur())
+            y_p = (y_a * pow(2, -1, meta.modulus)) - (lambda1 * (x_a - x_p))  # y_p = Y_A / 2 - lambda_1 (x_a - x_p)
+            init_x, init_y = table[0]                                         # the lookup defaults to the first entry without q_s1
+            not_q_s1 = Expression.constant(1) - q_s1
+            m = q_s1 * word
+            x_p = q_s1 * x_p + not_q_s1 * init_x
+            y_p = q_s1 * y_p + not_q_s1 * init_y
+            return [(m, config.generator_table.table_idx), (x_p, config.generator_table.table_x), (y_p, config.generator_table.table_y)]
+        meta.lookup(generator_lookup)
+
+        def initial_y_q(cells):
+            q_s4 = cells.query_selector(config.q_sinsemilla4)
+            y_q = cells.query_fixed(config.fixed_y_q)
+            y_a_cur = dna.Y_A(cells, Rotation.cur())
+            return [("init_y_q_check", q_s4 * (y_q * 2 - y_a_cur))]           # 2 y_Q - Y_{A,0} = 0
+        meta.create_gate("Initial y_Q", initial_y_q)
+
+        def sinsemilla_gate(cells):
+            q_s1 = cells.query_selector(config.q_sinsemilla1)
+            q_s3 = config.q_s3(cells)
+            lambda_1_next = cells.query_advice(dna.lambda_1, Rotation.next())
+            lambda_2_cur = cells.query_advice(dna.lambda_2, Rotation.cur())
+            x_a_cur = cells.query_advice(dna.x_a, Rotation.cur())
+            x_a_next = cells.query_advice(dna.x_a, Rotation.next())
+            x_r = dna.x_r(cells, Rotation.cur())
+            y_a_cur = dna.Y_A(cells, Rotation.cur())
+            y_a_next = dna.Y_A(cells, Rotation.next())
+            secant_line = lambda_2_cur.square() - (x_a_next + x_r + x_a_cur)
+            lhs = lambda_2_cur * 4 * (x_a_cur - x_a_next)
+            y_a_final = lambda_1_next                                         # on the last row lambda_1 holds y_a
+            rhs = y_a_cur * 2 + (Expression.constant(2) - q_s3) * y_a_next + q_s3 * 2 * y_a_final
+            return [("Secant line", q_s1 * secant_line), ("y check", q_s1 * (lhs - rhs))]
+        meta.create_gate("Sinsemilla gate", sinsemilla_gate)
+        return config
+
+    # ---- SinsemillaInstructions (chip.rs:315-372) ---------------------------------------------------------------------------------------------
+    def witness_message_piece(self, layouter, field_elem, num_words: int) -> MessagePiece:
+        cell = layouter.assign_region("witness message piece",
+                                      lambda region: region.assign_advice(self.config.witness_pieces, 0, lambda: field_elem))
+        return MessagePiece(cell, num_words)
+
+    def hash_to_point(self, layouter, Q, message):                            # noqa: N803
+        """message: a list of MessagePiece.  -> (NonIdentityEccPoint, the running sums of every piece)"""
+        assert sum(p.num_words for p in message) <= C_MAX
+        return layouter.assign_region("hash_to_point", lambda region: self._hash_message(region, Q, message))
+
+    @staticmethod
+    def extract(point: NonIdentityEccPoint) -> AssignedCell:
+        return point.x()
+
+    # ---- hash_to_point.rs ------------------------------------------------------------------------------------------------------------------
+    def _hash_message(self, region, Q, message):                              # noqa: N803
+        c, m = self.config, self.config.modulus
+        x_q, y_q = int(Q[0]) % m, int(Q[1]) % m
+        # public Q: q_sinsemilla4 and y_Q (fixed) on the first row, x_Q constrained to the constant
+        c.q_sinsemilla4.enable(region, 0)
+        region.assign_fixed(c.fixed_y_q, 0, lambda: y_q)
+        x_a = region.assign_advice_from_constant(c.double_and_add.x_a, 0, x_q)
+        y_a = Assigned.trivial(y_q, m) if region.layouter and region.layouter.cs.collect_advice else None
+        offset, zs_sum = 0, []
+        for idx, piece in enumerate(message):
+            x_a, y_a, zs = self._hash_piece(region, offset, piece, x_a, y_a, idx == len(message) - 1)
+            offset += piece.num_words
+            zs_sum.append(zs)
+        y_a_cell = region.assign_advice(c.double_and_add.lambda_1, offset, lambda: y_a)
+        region.assign_advice(c.double_and_add.lambda_2, offset, lambda: 0)    # queried by the gate, multiplied by zero
+        region.assign_advice(c.double_and_add.x_p, offset, lambda: 0)
+        if y_a is not None:
+            x_val = x_a.value().inner
+            if x_val.is_zero_vartime() or y_a.is_zero_vartime():
+                raise Synthesis("Sinsemilla: the hash has no value (an exceptional addition)")
+        return NonIdentityEccPoint(x_a, y_a_cell), zs_sum
+
+    def _hash_piece(self, region, offset, piece: MessagePiece, x_a: AssignedCell, y_a, final_piece: bool):
+        c, m = self.config, self.config.modulus
+        dna = c.double_and_add
+        n = piece.num_words
+        for row in range(n):
+            c.q_sinsemilla1.enable(region, offset + row)
+        for row in range(n - 1):
+            region.assign_fixed(c.q_sinsemilla2, offset + row, lambda: 1)
+        region.assign_fixed(c.q_sinsemilla2, offset + n - 1, lambda: 2 if final_piece else 0)
+
+        elem = piece.field_elem(m)
+        words = [None] * n if elem is None else [(elem >> (K * j)) & ((1 << K) - 1) for j in range(n)]
+        # the running sum: z_0 is a copy of the piece, z_{i+1} = (z_i - m_{i+1}) / 2^K; z_n = 0 is not assigned
+        zs = [piece.cell_value.copy_advice(region, c.bits, offset)]
+        z, inv_2_k = elem, pow(1 << K, -1, m)
+        for idx in range(n - 1):
+            z = None if z is None else (z - words[idx]) * inv_2_k % m
+            zs.append(region.assign_advice(c.bits, offset + idx + 1, lambda v=z: v))
+
+        for row, word in enumerate(words):
+            if word is None or y_a is None:
+                for column in (dna.x_p, dna.lambda_1, dna.lambda_2):
+                    region.assign_advice(column, offset + row, lambda: None)
+                x_a = region.assign_advice(dna.x_a, offset + row + 1, lambda: None)
+                continue
+            x_p, y_p = c.table[word]
+            x_a_val = x_a.value().inner
+            region.assign_advice(dna.x_p, offset + row, lambda: x_p)
+            lambda_1 = (y_a - y_p) * (x_a_val - x_p).invert()
+            region.assign_advice(dna.lambda_1, offset + row, lambda: lambda_1)
+            x_r = lambda_1.square() - x_a_val - x_p
+            lambda_2 = y_a * 2 * (x_a_val - x_r).invert() - lambda_1
+            region.assign_advice(dna.lambda_2, offset + row, lambda: lambda_2)
+            x_a_new = lambda_2.square() - x_a_val - x_r
+            x_a = region.assign_advice(dna.x_a, offset + row + 1, lambda: x_a_new)
+            y_a = lambda_2 * (x_a_val - x_a_new) - y_a
+        return x_a, y_a, zs
+
+    # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def hash_to_point_many(self, layouter, Q, num_words, pieces, values=None, trace=None) -> HashMany:      # noqa: N803
+        """`count` hashes of one piece structure back to back in one region of (sum(num_words) + 1) * count rows; cell for cell what
+        `count` calls of `hash_to_point` lay out.
+
+        pieces: pieces[i][k] is the MessagePiece k of hash i (their cells are copied into z_0).  values: the (count, n_pieces, 4)
+        CANONICAL limbs of the pieces where the caller has them on the device already (else they are read from the cells); trace:
+        the (5, rows * count, 4) columns where the caller has them (else `sinsemilla.trace`, once).  Without a witness (keygen) the
+        same shape is laid out and nothing is launched."""
+        import torch
+        c, m = self.config, self.config.modulus
+        num_words = [int(w) for w in num_words]
+        count, n_pieces, rows = len(pieces), len(num_words), sum(num_words) + 1
+        if any(len(p) != n_pieces or any(q.num_words != w for q, w in zip(p, num_words)) for p in pieces):
+            raise ValueError("hash_to_point_many: every hash has the pieces of the one structure")
+        backend = layouter.cs
+        total = rows * count
+        if not backend.collect_advice:
+            trace = None
+        elif trace is None and count:
+            if values is None:
+                ints = [q.field_elem(m) for p in pieces for q in p]
+                if any(v is None for v in ints):
+                    raise Synthesis("hash_to_point_many: a witness is needed and there is none")
+                values = fields.to_limbs(ints, FP, montgomery=False).reshape(count, n_pieces, 4)
+            if not torch.is_tensor(values):
+                values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint64).view(np.int64)).to(fields.current_device())
+            trace = primitive.trace(values, num_words, Q, table=c.injected_table)
+        if trace is not None:
+            if not torch.is_tensor(trace):
+                trace = torch.from_numpy(np.ascontiguousarray(trace, dtype=np.uint64).view(np.int64))
+            if tuple(trace.shape) != (5, total, 4):
+                raise ValueError("hash_to_point_many: the trace is (5, rows * count, 4)")
+        blank = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (total, 4))
+        advice = [blank] * 5 if trace is None else [trace[j] for j in range(5)]
+        # q_sinsemilla2 of one hash: 1 on the rows of a piece but its last, 0 there, 2 on the last word row; nothing on the final row
+        # (a fixed cell nobody assigns is zero, so the tiled pattern carries a zero there)
+        pattern = []
+        for k, w in enumerate(num_words):
+            pattern += [1] * (w - 1) + [2 if k == n_pieces - 1 else 0]
+        q_s2 = blank
+        if backend.collect_fixed and count:
+            q_s2 = np.tile(fields.to_limbs(pattern + [0], FP), (count, 1))
+        base = rows * np.arange(count, dtype=np.int64)
+        word_rows = (base[:, None] + np.arange(rows - 1, dtype=np.int64)[None, :]).reshape(-1)
+        x_q, y_q = int(Q[0]) % m, int(Q[1]) % m
+        dna = c.double_and_add
+        result = HashMany(None, c, count, num_words, None)
+
+        def assign(region):
+            for column, values_ in zip((dna.x_a, dna.x_p, c.bits, dna.lambda_1, dna.lambda_2), advice):
+                region.assign_advice_column(column, 0, values_)
+            region.enable_selector_rows(c.q_sinsemilla1, word_rows)
+            region.enable_selector_rows(c.q_sinsemilla4, base)
+            region.assign_fixed_column(c.q_sinsemilla2, 0, q_s2)
+            for i in range(count):
+                region.assign_fixed(c.fixed_y_q, rows * i, lambda: y_q)
+                region.constrain_constant(Cell(region.region_index, rows * i, dna.x_a), x_q)
+                at = rows * i
+                for k, w in enumerate(num_words):
+                    region.constrain_equal(Cell(region.region_index, at, c.bits), pieces[i][k].cell_value.cell())
+                    at += w
+            return region.region_index
+        result.region_index = layouter.assign_region("hash_to_point many", assign)
+        if trace is not None and count:
+            last = torch.from_numpy(base + rows - 1).to(trace.device)
+            result.outputs = torch.stack([trace[0][last], trace[3][last]], dim=1)
+        return result
+
+
+class HashDomain:
+    """sinsemilla.rs HashDomain over a SinsemillaChip (or a MerkleChip) and a public Q."""
+
+    def __init__(self, chip, Q):                                              # noqa: N803
+        self.chip, self.Q = chip, (int(Q[0]), int(Q[1]))
+
+    def hash_to_point(self, layouter, message):
+        return self.chip.hash_to_point(layouter, self.Q, message)
+
+    def hash(self, layouter, message):                                        # noqa: A003
+        point, zs = self.hash_to_point(layouter, message)
+        return self.chip.extract(point), zs
+
+
+# ---- MerkleChip, MerklePath (merkle/chip.rs, merkle.rs) ------------------------------------------------------------------------------------
+class MerkleConfig:
+    def __init__(self, advices, q_decompose, cond_swap_config, sinsemilla_config):
+        self.advices, self.q_decompose = advices, q_decompose
+        self.cond_swap_config, self.sinsemilla_config = cond_swap_config, sinsemilla_config
+
+
+class MerkleChip:
+    """hash_layer = MerkleCRH: SinsemillaHash(Q, l (10 bits) || left (255 bits) || right (255 bits)); left and right are not
+    constrained to be canonical."""
+
+    def __init__(self, config: MerkleConfig):
+        self.config = config
+        self._sinsemilla = SinsemillaChip(config.sinsemilla_config)
+        self._cond_swap = CondSwapChip(config.cond_swap_config)
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, sinsemilla_config: SinsemillaConfig) -> MerkleConfig:
+        advices = sinsemilla_config.advices()
+        cond_swap_config = CondSwapChip.configure(meta, advices)
+        q_decompose = meta.selector()
+
+        # |  A_0  |  A_1  |  A_2  |  A_3  |  A_4  | q_decompose |
+        # |   a   |   b   |   c   |  left | right |      1      |
+        # |  z1_a |  z1_b |  b_1  |  b_2  |   l   |      0      |
+        def gate(cells):
+            q = cells.query_selector(q_decompose)
+            l_whole = cells.query_advice(advices[4], Rotation.next())
+            two_pow_5, two_pow_10 = 1 << 5, 1 << 10
+            a_whole = cells.query_advice(advices[0], Rotation.cur())
+            b_whole = cells.query_advice(advices[1], Rotation.cur())
+            c_whole = cells.query_advice(advices[2], Rotation.cur())
+            left_node = cells.query_advice(advices[3], Rotation.cur())
+            right_node = cells.query_advice(advices[4], Rotation.cur())
+            a_1 = cells.query_advice(advices[0], Rotation.next())             # z_1 of SinsemillaHash(a)
+            a_0 = a_whole - a_1 * two_pow_10
+            z1_b = cells.query_advice(advices[1], Rotation.next())
+            b_1 = cells.query_advice(advices[2], Rotation.next())
+            b_2 = cells.query_advice(advices[3], Rotation.next())
+            b1_b2_check = z1_b - (b_1 + b_2 * two_pow_5)
+            b_0 = b_whole - (z1_b * two_pow_10)
+            left_check = (a_1 + (b_0 + b_1 * two_pow_10) * (1 << 240)) - left_node
+            right_check = b_2 + c_whole * two_pow_5 - right_node
+            return [("l_check", q * (a_0 - l_whole)), ("left_check", q * left_check), ("right_check", q * right_check),
+                    ("b1_b2_check", q * b1_b2_check)]
+        meta.create_gate("Decomposition check", gate)
+        return MerkleConfig(advices, q_decompose, cond_swap_config, sinsemilla_config)
+
+    # what the chip forwards to its two parts
+    def witness_message_piece(self, layouter, value, num_words):
+        return self._sinsemilla.witness_message_piece(layouter, value, num_words)
+
+    def hash_to_point(self, layouter, Q, message):                            # noqa: N803
+        return self._sinsemilla.hash_to_point(layouter, Q, message)
+
+    extract = staticmethod(SinsemillaChip.extract)
+
+    def swap(self, layouter, pair, swap):
+        return self._cond_swap.swap(layouter, pair, swap)
+
+    def load_private(self, layouter, column, value):
+        return load_private(layouter, column, value)
+
+    def hash_layer(self, layouter, Q, l: int, left: AssignedCell, right: AssignedCell) -> AssignedCell:      # noqa: N803, E741
+        """a = l || bits 0..239 of left;  b = bits 240..249 of left || bits 250..254 of left || bits 0..4 of right;
+        c = bits 5..254 of right.  b_1 and b_2 are range-constrained to 5 bits, the pieces by the hash itself."""
+        config = self.config
+        m = config.sinsemilla_config.modulus
+        lookup_config = config.sinsemilla_config.lookup_config
+        left_v, right_v = value_int(left.value(), m), value_int(right.value(), m)
+        a = MessagePiece.from_subpieces(self, layouter, [RangeConstrained.bitrange_of(l, 0, 10), RangeConstrained.bitrange_of(left_v, 0, 240)])
+        b_0 = RangeConstrained.bitrange_of(left_v, 240, 250)
+        b_1 = RangeConstrained.witness_short(lookup_config, layouter, left_v, 250, 255)
+        b_2 = RangeConstrained.witness_short(lookup_config, layouter, right_v, 0, 5)
+        b = MessagePiece.from_subpieces(self, layouter, [b_0, b_1.value(m), b_2.value(m)])
+        c = MessagePiece.from_subpieces(self, layouter, [RangeConstrained.bitrange_of(right_v, 5, 255)])
+        point, zs = self.hash_to_point(layouter, Q, [a, b, c])
+        digest = self.extract(point)
+        z1_a, z1_b = zs[0][1], zs[1][1]
+
+        def assign(region):
+            config.q_decompose.enable(region, 0)
+            region.assign_advice_from_constant(config.advices[4], 1, l)
+            a.cell_value.copy_advice(region, config.advices[0], 0)
+            b.cell_value.copy_advice(region, config.advices[1], 0)
+            c.cell_value.copy_advice(region, config.advices[2], 0)
+            left.copy_advice(region, config.advices[3], 0)
+            right.copy_advice(region, config.advices[4], 0)
+            z1_a.copy_advice(region, config.advices[0], 1)
+            z1_b.copy_advice(region, config.advices[1], 1)
+            b_1.inner.copy_advice(region, config.advices[2], 1)
+            b_2.inner.copy_advice(region, config.advices[3], 1)
+        layouter.assign_region("Check piece decomposition", assign)
+        return digest
+
+
+class MerklePath:
+    """merkle.rs:46-171: the path from a leaf to the root, its layers shared out over the chips (ceil(len / chips) layers each)."""
+
+    def __init__(self, chips, Q, leaf_pos, path, path_length: int | None = None):      # noqa: N803
+        assert chips
+        self.chips, self.Q, self.leaf_pos = list(chips), Q, leaf_pos
+        self.path = None if path is None else list(path)
+        self.path_length = len(self.path) if path_length is None else path_length
+
+    def calculate_root(self, layouter, leaf: AssignedCell) -> AssignedCell:
+        n = self.path_length
+        layers_per_chip = (n + len(self.chips) - 1) // len(self.chips)
+        pos = [None] * n if self.leaf_pos is None else i2lebsp(self.leaf_pos, n)
+        path = [None] * n if self.path is None else self.path
+        node = leaf
+        for l in range(n):                                                    # noqa: E741 -- l counts from the leaf
+            chip = self.chips[l // layers_per_chip]
+            pair = chip.swap(layouter, (node, path[l]), pos[l])
+            node = chip.hash_layer(layouter, self.Q, l, pair[0], pair[1])
+        return node

@@ -1,0 +1,225 @@
+"""Sinsemilla over Pallas in bulk (halo2_amd/csrc/sinsemilla.hip): the hash of Orchard's note-commitment tree (MerkleCRH) and the
+witness of the Sinsemilla chip.  Zcash protocol specification 5.4.1.9: K = 10, C = 253,
+    S(j) = hash_to_curve("z.cash:SinsemillaS")(j as 4 bytes LE),   Q(D) = hash_to_curve("z.cash:SinsemillaQ")(D),
+    hash_to_point(m_1 .. m_n) = fold Acc <- (Acc + S(m_i)) + Acc from Q, with INCOMPLETE addition: a chain that meets equal or
+    opposite operands has no value (the reference's `None`), reported here per message.
+
+Field elements and points are arrays of uint64 Montgomery limbs ((..., 4) and (..., 8)): a CUDA int64 tensor is used in place and a
+CUDA tensor comes back; a numpy array is uploaded and a numpy array comes back.  The 1024-point table S is built once per process and
+device by h2_hash_to_curve_device and stays in HBM (64 KiB)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import fields
+from ._lib import FORM_MONTGOMERY, check, lib
+from .arithmetic import _is_torch, _p, _stream_ptr
+
+__all__ = ["K", "C_MAX", "HashDomain", "generator_table", "generator_table_ints", "q_point", "merkle_crh", "merkle_root", "trace",
+           "Bottom", "MERKLE_CRH_DOMAIN"]
+
+K = 10
+C_MAX = 253                                     # the specification's C: words per message
+S_PERSONALIZATION = "z.cash:SinsemillaS"
+Q_PERSONALIZATION = "z.cash:SinsemillaQ"
+MERKLE_CRH_DOMAIN = "z.cash:Orchard-MerkleCRH"
+PALLAS, FP = 0, 0
+
+_tables: dict = {}
+_table_ints: dict = {}
+
+
+class Bottom(ValueError):
+    """A Sinsemilla hash met an exceptional addition: the specification's bottom."""
+
+
+def generator_table():
+    """S(0) .. S(1023) as a (1024, 8) int64 CUDA tensor of Montgomery affine limbs on the current device; built on first use."""
+    import torch
+    dev = fields.current_device()
+    if dev.index not in _tables:
+        msgs = torch.from_numpy(np.arange(1 << K, dtype="<u4").view(np.uint8).reshape(1 << K, 4).copy()).to(dev)
+        out = torch.empty((1 << K, 8), dtype=torch.int64, device=dev)
+        check(lib().h2_hash_to_curve_device(PALLAS, S_PERSONALIZATION.encode(), msgs.data_ptr(), 4, 1 << K, FORM_MONTGOMERY,
+                                            out.data_ptr(), _stream_ptr()), "h2_hash_to_curve_device")
+        _tables[dev.index] = out
+    return _tables[dev.index]
+
+
+def _points_to_ints(limbs) -> list:
+    v = fields.from_limbs(np.asarray(limbs).reshape(-1, 4), FP)
+    return [(v[2 * i], v[2 * i + 1]) for i in range(len(v) // 2)]
+
+
+def generator_table_ints(table=None) -> list:
+    """The table as 1024 (x, y) pairs of Python integers: `table` if given (a list of pairs, or (1024, 8) Montgomery limbs), the device's
+    otherwise.  This is what the chip's synthesis reads."""
+    if table is None:
+        index = fields.current_device().index
+        if index not in _table_ints:
+            _table_ints[index] = _points_to_ints(generator_table().cpu().numpy().view(np.uint64))
+        return _table_ints[index]
+    if isinstance(table, np.ndarray):
+        return _points_to_ints(table)
+    table = [(int(x), int(y)) for x, y in table]
+    if len(table) != 1 << K:
+        raise ValueError("sinsemilla: the table has 2^10 points")
+    return table
+
+
+def _device_table(table):
+    """-> (1024, 8) int64 CUDA tensor from an injected table, or the process's own"""
+    import torch
+    if table is None:
+        return generator_table()
+    if _is_torch(table):
+        return table.contiguous()
+    if not isinstance(table, np.ndarray):
+        table = fields.to_limbs([c for pt in table for c in pt], FP).reshape(-1, 8)
+    if table.shape != (1 << K, 8):
+        raise ValueError("sinsemilla: the table has 2^10 points")
+    return torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint64).view(np.int64)).to(fields.current_device())
+
+
+def q_point(domain) -> tuple:
+    """Q(D) = hash_to_curve("z.cash:SinsemillaQ")(D) as (x, y) integers."""
+    from .commitment import hash_to_curve
+    d = domain.encode() if isinstance(domain, str) else bytes(domain)
+    return _points_to_ints(hash_to_curve(PALLAS, Q_PERSONALIZATION, [d]))[0]
+
+
+def _q_limbs(q) -> np.ndarray:
+    return np.ascontiguousarray(fields.to_limbs([q[0], q[1]], FP).reshape(8))
+
+
+def _ptr(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _raise_bottom(status, what):
+    bad = status.nonzero().flatten()
+    if bad.numel():
+        raise Bottom(f"{what}: message {int(bad[0])} meets an exceptional addition ({bad.numel()} of {status.numel()} do)")
+
+
+class HashDomain:
+    """`HashDomain::new(name)` (halo2_gadgets/src/sinsemilla.rs), or a domain with a caller's Q: `HashDomain((x, y))`.
+    `table=` replaces the generator table (host tests inject one computed on the CPU)."""
+
+    def __init__(self, name_or_q, table=None):
+        self.Q = q_point(name_or_q) if isinstance(name_or_q, (str, bytes)) else (int(name_or_q[0]), int(name_or_q[1]))
+        self.table = table
+
+    def hash_to_point(self, words, with_status: bool = False):
+        """n messages of `len` words (< 1024): an (n, len) integer array or CUDA int16 tensor -> (n, 8) affine points.  A message without
+        a value raises `Bottom`; with_status: returns (points, status) instead -- status[i] = 1 and a zero point for such a message."""
+        import torch
+        host = not _is_torch(words)
+        if host:
+            w = np.asarray(words)
+            if w.ndim != 2 or (w.size and (w.min() < 0 or w.max() >= 1 << K)):
+                raise ValueError("sinsemilla.hash_to_point: an (n, len) array of 10-bit words")
+            w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint16).view(np.int16)).to(fields.current_device())
+        else:
+            w = words.contiguous()
+            if w.dtype != torch.int16 or w.ndim != 2 or not w.is_cuda:
+                raise ValueError("sinsemilla.hash_to_point: an (n, len) CUDA int16 tensor of 10-bit words")
+        n, length = w.shape
+        if length > C_MAX:
+            raise ValueError("sinsemilla.hash_to_point: a message has at most 253 words")
+        tab = _device_table(self.table)
+        out = torch.empty((n, 8), dtype=torch.int64, device=w.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=w.device)
+        check(lib().h2_sinsemilla_hash_device(_ptr(w), n, length, _p(_q_limbs(self.Q)), tab.data_ptr(), _ptr(out), _ptr(status), _stream_ptr()),
+              "h2_sinsemilla_hash_device")
+        if with_status:
+            return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
+        _raise_bottom(status, "sinsemilla.hash_to_point")
+        return out.cpu().numpy().view(np.uint64) if host else out
+
+    def hash(self, words):                                                    # noqa: A003 -- the reference's name
+        """The x coordinates of hash_to_point: (n, len) -> (n, 4)."""
+        pts = self.hash_to_point(words)
+        return np.ascontiguousarray(pts[:, :4]) if isinstance(pts, np.ndarray) else pts[:, :4].contiguous()
+
+
+def _merkle_domain(domain):
+    if domain is None:
+        return HashDomain(MERKLE_CRH_DOMAIN)
+    return domain if isinstance(domain, HashDomain) else HashDomain(domain)
+
+
+def merkle_crh(layer: int, left, right, domain=None):
+    """MerkleCRH (specification 5.4.1.3) of n pairs: the hash of  layer (10 bits) || left (255 bits) || right (255 bits) = 52 words,
+    (n, 4) and (n, 4) -> (n, 4).  `domain`: a HashDomain, a name or None for Orchard's.  Raises `Bottom` where the specification's
+    hash has no value (Orchard maps that to 0; a caller who wants that catches it)."""
+    import torch
+    dom = _merkle_domain(domain)
+    host = not _is_torch(left)
+    dev = fields.current_device()
+    up = (lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)) if host else (lambda a: a)
+    l, r = up(left), up(right)
+    if l.shape != r.shape or l.ndim != 2 or l.shape[1] != 4 or l.dtype != torch.int64:
+        raise ValueError("sinsemilla.merkle_crh: left and right are (n, 4) arrays of Montgomery limbs")
+    out = _merkle_layer(dom, layer, torch.stack((l, r), dim=1).contiguous())
+    return out.cpu().numpy().view(np.uint64) if host else out
+
+
+def _merkle_layer(dom, layer, pairs):
+    """pairs: (n, 2, 4) int64 CUDA tensor -> (n, 4)"""
+    import torch
+    if not 0 <= layer < 1 << K:
+        raise ValueError("sinsemilla.merkle_crh: the layer is a 10-bit number")
+    n = pairs.shape[0]
+    tab = _device_table(dom.table)
+    out = torch.empty((n, 4), dtype=torch.int64, device=pairs.device)
+    status = torch.empty((n,), dtype=torch.uint8, device=pairs.device)
+    check(lib().h2_sinsemilla_merkle_layer_device(layer, _ptr(pairs), n, _p(_q_limbs(dom.Q)), tab.data_ptr(), _ptr(out), _ptr(status),
+                                                  _stream_ptr()), "h2_sinsemilla_merkle_layer_device")
+    _raise_bottom(status, "sinsemilla.merkle_crh")
+    return out
+
+
+def merkle_root(leaves, domain=None):
+    """The root of the binary tree over a power-of-two number of leaves, (n, 4) -> (4,): one launch per layer, every layer stays on
+    the device.  The tree has depth log2(n) and level l counted from the leaves is hashed with layer = depth - 1 - l, as Orchard
+    numbers them (the root's children meet at layer 0).  Any other number of leaves is rejected."""
+    import torch
+    dom = _merkle_domain(domain)
+    host = not _is_torch(leaves)
+    t = torch.from_numpy(np.ascontiguousarray(leaves, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else leaves.contiguous()
+    n = t.shape[0] if t.ndim == 2 else 0
+    if t.ndim != 2 or t.shape[1] != 4 or n < 1 or n & (n - 1):
+        raise ValueError("sinsemilla.merkle_root: a power-of-two number of leaves, (n, 4) Montgomery limbs")
+    depth = n.bit_length() - 1
+    for level in range(depth):
+        t = _merkle_layer(dom, depth - 1 - level, t.view(t.shape[0] // 2, 2, 4))
+    return t[0].cpu().numpy().view(np.uint64) if host else t[0]
+
+
+def trace(pieces, num_words, Q, table=None, with_status: bool = False):
+    """What SinsemillaChip.hash_to_point witnesses for `count` messages of one piece structure.  pieces: (count, n_pieces, 4) CANONICAL
+    limbs (piece k carries num_words[k] <= 25 words, low bits first); Q an (x, y) pair.  -> (5, rows * count, 4) Montgomery limbs, the
+    columns x_a, x_p, bits, lambda_1, lambda_2 with rows = sum(num_words) + 1 per message (see include/halo2_mi355x.h).  A message
+    without a value raises `Bottom`, or is flagged in the returned status with with_status."""
+    import torch
+    num_words = [int(w) for w in num_words]
+    host = not _is_torch(pieces)
+    p = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else pieces.contiguous()
+    if p.ndim != 3 or p.shape[1] != len(num_words) or p.shape[2] != 4 or p.dtype != torch.int64:
+        raise ValueError("sinsemilla.trace: pieces is a (count, n_pieces, 4) array of canonical limbs")
+    if not num_words or any(not 1 <= w <= 25 for w in num_words) or sum(num_words) > C_MAX:
+        raise ValueError("sinsemilla.trace: 1 .. 25 words per piece, 253 per message")
+    count, rows = p.shape[0], sum(num_words) + 1
+    tab = _device_table(table)
+    out = torch.empty((5, rows * count, 4), dtype=torch.int64, device=p.device)
+    status = torch.empty((count,), dtype=torch.uint8, device=p.device)
+    nw = (C.c_uint32 * len(num_words))(*num_words)
+    check(lib().h2_sinsemilla_trace_device(_ptr(p), count, nw, len(num_words), _p(_q_limbs(Q)), tab.data_ptr(), _ptr(out), _ptr(status),
+                                           _stream_ptr()), "h2_sinsemilla_trace_device")
+    if with_status:
+        return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
+    _raise_bottom(status, "sinsemilla.trace")
+    return out.cpu().numpy().view(np.uint64) if host else out

@@ -595,6 +595,36 @@ int h2_poseidon_hash_device(int field, const void *d_messages, size_t n, size_t 
  * rows are zero.  Every one of the 4 * 37 * count elements is written.  d_columns must not overlap d_states. */
 int h2_poseidon_trace_device(int field, const void *d_states, size_t count, void *d_columns, void *stream);
 
+/* ---- Sinsemilla over Pallas (Zcash protocol specification 5.4.1.9; K = 10, C = 253), batched ---- */
+/* One lane per message.  q_xy is the domain's Q in HOST memory; d_table the 1024 points S(j) = hash_to_curve("z.cash:SinsemillaS")
+ * (j as 4 bytes LE) in device memory; both Montgomery affine (8 limbs a point).  Every addition is the specification's INCOMPLETE
+ * addition: a message whose chain Acc <- (Acc + S(m_i)) + Acc meets equal or opposite operands (or starts from the identity) gets
+ * d_status[i] = 1 (one byte per message; the reference's bottom) where every other message gets 0.
+ *
+ * h2_sinsemilla_hash_device: d_words holds n messages of `words` uint16 each, message after message; only the low 10 bits of a word
+ * are read.  d_out_xy[i] is the Montgomery affine hash point of message i, zeros where d_status[i] = 1.  words = 0 returns Q;
+ * words > 253, n > 2^30 or a null pointer with n > 0 are H2_ERR_ARGS. */
+int h2_sinsemilla_hash_device(const void *d_words, size_t n, size_t words, const uint64_t *q_xy, const void *d_table, void *d_out_xy,
+                              void *d_status, void *stream);
+/* h2_sinsemilla_merkle_layer_device: MerkleCRH (specification 5.4.1.3) of n pairs: d_pairs holds n times (left, right), Montgomery
+ * elements; message i is the 52 words  layer (10 bits) || left (255 bits) || right (255 bits), low bits first, cut on the lane.
+ * d_out_x[i] is the x coordinate of its hash (Montgomery), zero where d_status[i] = 1.  layer >= 1024 is H2_ERR_ARGS.  d_out_x must
+ * not overlap d_pairs. */
+int h2_sinsemilla_merkle_layer_device(unsigned layer, const void *d_pairs, size_t n, const uint64_t *q_xy, const void *d_table,
+                                      void *d_out_x, void *d_status, void *stream);
+/* h2_sinsemilla_trace_device: the witness of SinsemillaChip::hash_message (halo2_gadgets sinsemilla/chip/hash_to_point.rs) for `count`
+ * messages of one piece structure.  d_pieces: count * n_pieces CANONICAL field elements, message after message; piece k supplies
+ * num_words[k] (1 .. 25, host memory) words, its low bits first; the sum of num_words is at most 253.  Each message takes
+ * rows = sum(num_words) + 1 rows.  d_columns is ONE buffer of 5 vectors of rows * count Montgomery elements, one after the other,
+ * in the order of the chip's advice columns: x_a, x_p, bits, lambda_1, lambda_2; rows i * rows .. (i + 1) * rows - 1 belong to
+ * message i.  A word row holds the accumulator's x before the round, the x of S(word), the running sum z = piece >> 10 j of the
+ * j-th word of its piece, and the two slopes; the last row holds the hash's x in x_a, its y in lambda_1, zeros elsewhere.  Every
+ * element is written.  The rows of a message with d_status[i] = 1 are not a witness (a vanished denominator inverts to 0, as the
+ * reference's Assigned does).  Scratch (32 bytes per row of at most 2^20 rows at a time) belongs to the (device, stream) context
+ * and goes back with h2_trim.  Bad arguments are H2_ERR_ARGS. */
+int h2_sinsemilla_trace_device(const void *d_pieces, size_t count, const uint32_t *num_words, size_t n_pieces, const uint64_t *q_xy,
+                               const void *d_table, void *d_columns, void *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
