@@ -24,6 +24,13 @@ namespace h2 {
         }                                                 \
     } while (0)
 
+// one launch of a kernel template on the field (kern<FP> / kern<FQ>, field.cuh) that `field` names: grid, block, LDS bytes, stream, then the arguments
+#define H2_FIELD_LAUNCH(field, kern, ...)                                      \
+    do {                                                                       \
+        if ((field) == H2_FP) hipLaunchKernelGGL((kern<FP>), __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kern<FQ>), __VA_ARGS__);                      \
+    } while (0)
+
 void set_last_hip_error(hipError_t e, const char *file, int line);
 void set_last_error_msg(const char *msg);   // what h2_last_error() returns on this thread
 

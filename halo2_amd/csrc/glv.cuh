@@ -1,7 +1,7 @@
 // The Pasta curves' endomorphism phi(x, y) = (zeta x, y) = [lambda](x, y) (zeta, lambda: cube roots of unity of the base
 // and scalar field) splits a 255-bit scalar k = k1 + k2 lambda with |k1|, |k2| < 2^128.  Used where a doubling chain is
 // the latency floor: the generic multiexp (its Horner over windows shrinks from 255 to 128 doublings) and the
-// opening argument's generator collapse (ipa.hip, split done once on the host there).
+// opening argument's generator collapse (ipa_kernels.cuh; the split is done once on the host, ipa_recode.h).
 //
 // Lattice basis (a1, b1), (a2, b2) with a + b lambda = 0 mod q (b1 < 0 for both fields) and g_i = floor(2^256 (b2, -b1) / q),
 // all from extended Euclid on (q, lambda) in big-integer arithmetic offline; c_i = (k g_i) >> 256 only has to be CLOSE to the

@@ -442,7 +442,10 @@ bool bad_common(int curve, int form, int out_kind);
 int table_fill(Bases &b, u32 first, u32 count, hipStream_t st, bool keep_tmp = false);
 int set_blind_base_host(Bases &b, const void *host_w_xy, int form);
 int override_blind_base_device(Bases &b, const void *d_w_xy, int form, hipStream_t st);
-bool pair_subdigits_apply(size_t n);                                                 // msm_subdigit.hip
+bool pair_subdigits_apply(size_t n);                                                 // does h2_commit_pair_device take the sub-digit form for n points?
+// the opening argument's table of collapsed generators (ipa.hip): refilled in place / registered, optionally as an endomorphism table
+int bases_refill_device(h2_bases_t handle, const void *d_bases_xy, size_t n, int form);
+int bases_register_device_internal(int curve, const void *d_bases_xy, size_t n, int form, h2_bases_t *handle, bool glv);
 
 // compile-time A/B knobs of the accumulate (a second build under build/ab/; the defaults are what ships)
 #ifndef H2_ACC_LOOP

@@ -326,7 +326,7 @@ extern "C" int h2_bases_register_device(int curve, const void *d_bases_xy, size_
     return bases_register_impl(curve, d_bases_xy, true, n, form, handle);
 }
 
-// Internal (ipa.hip): rebuild the table of an existing handle from n new points in HBM -- same n, same window width, the allocation
+// Internal (ipa.hip; declared in msm_internal.cuh): rebuild the table of an existing handle from n new points in HBM -- same n, same window width, the allocation
 // is kept.  The opening argument registers a table for its collapsed generators in every proof; from the second proof on this
 // saves the allocation and the release (~0.35 ms of hipMalloc / hipFree, which also synchronise the device).  The handle's blind
 // column is cleared with the table.  Nothing else may be using the handle (the caller owns it).
@@ -337,7 +337,7 @@ static long pair_subdigit_max() {
     return v;
 }
 bool pair_subdigits_apply(size_t n) { return pair_subdigit_max() > 0 && n >= 8 && n <= (size_t)pair_subdigit_max(); }
-// Internal (ipa.hip): the table of the opening argument's collapsed generators.  glv: an ENDOMORPHISM table (Bases::glv) -- nine rows by the doubling
+// Internal (ipa.hip; declared in msm_internal.cuh): the table of the opening argument's collapsed generators.  glv: an ENDOMORPHISM table (Bases::glv) -- nine rows by the doubling
 // chain instead of sixteen (128 dependent doublings instead of 240: the chain is the latency of the switch), nine more through phi; only the
 // sub-digit paired commit reads such a table.
 int bases_register_device_internal(int curve, const void *d_bases_xy, size_t n, int form, h2_bases_t *handle, bool glv) {

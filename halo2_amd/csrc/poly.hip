@@ -479,12 +479,6 @@ int poly_kernel_attrs() {
 }
 unsigned reduce_blocks(size_t n) { return (unsigned)std::min<size_t>(1024, (n + kPT - 1) / kPT); }
 
-#define H2_FIELD_LAUNCH(field, kern, ...)                                      \
-    do {                                                                       \
-        if ((field) == H2_FP) hipLaunchKernelGGL((kern<FP>), __VA_ARGS__);     \
-        else hipLaunchKernelGGL((kern<FQ>), __VA_ARGS__);                      \
-    } while (0)
-
 int eval_launch(int field, const void *d_a, size_t n, const u64 *point, int form, void *d_out, hipStream_t st) {
     PolyContext &cx = poly_ctx(st);
     std::lock_guard<std::mutex> lk(cx.mu);

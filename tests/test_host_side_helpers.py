@@ -1,5 +1,5 @@
 """Host-side pieces added in round 5 that need no GPU: the transcript wrapper that reads queued evaluations back together
-(halo2_amd.transcript.DeferredScalars), and the integer identity behind the S commitment by quarters (csrc/ipa.hip: ipa_fix_s0)."""
+(halo2_amd.transcript.DeferredScalars), and the integer identity behind the S commitment by quarters (csrc/ipa_kernels.cuh: ipa_fix_s0)."""
 import random
 
 import numpy as np
@@ -84,7 +84,7 @@ def test_deferred_scalars_keep_the_unwritten_tail_when_a_write_fails():
 
 
 def test_evaluation_from_the_quarters():
-    """ipa_fix_s0: s(x) = sum_r x^(r n / 4) ev_r with ev_r the evaluation of quarter r as a polynomial in its own index, and x^(n / 4) by k - 2 squarings;
+    """ipa_fix_s0 (csrc/ipa_kernels.cuh): s(x) = sum_r x^(r n / 4) ev_r with ev_r the evaluation of quarter r as a polynomial in its own index, and x^(n / 4) by k - 2 squarings;
     after s[0] -= s(x) the polynomial has its root at x (prover.rs:49-51)."""
     rng = random.Random(11)
     for k in (4, 7, 10):
