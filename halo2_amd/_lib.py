@@ -152,6 +152,8 @@ SIGNATURES = {
     "h2_sinsemilla_hash_device": ([vp, C.c_size_t, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
     "h2_sinsemilla_merkle_layer_device": ([C.c_uint, vp, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
     "h2_sinsemilla_trace_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
+    "h2_ecc_mul_device": ([vp, vp, C.c_size_t, vp, vp, vp], C.c_int),
+    "h2_ecc_mul_trace_device": ([vp, vp, C.c_size_t, vp, vp, vp, vp], C.c_int),
 }
 
 

@@ -625,6 +625,28 @@ int h2_sinsemilla_merkle_layer_device(unsigned layer, const void *d_pairs, size_
 int h2_sinsemilla_trace_device(const void *d_pieces, size_t count, const uint32_t *num_words, size_t n_pieces, const uint64_t *q_xy,
                                const void *d_table, void *d_columns, void *d_status, void *stream);
 
+/* ---- Variable-base scalar multiplication over Pallas (halo2_gadgets ecc/chip/mul.rs), batched ---- */
+/* One lane per multiplication.  Points are Montgomery affine (8 limbs), the identity is (0, 0).
+ *
+ * h2_ecc_mul_device: n independent products d_out_xy[i] = [k_i] P_i (nothing is summed).  d_scalars holds n CANONICAL integers of 4
+ * limbs, any value below 2^255 (bit 255 is ignored).  Complete: every scalar and base, the identity among them, gives the group's
+ * answer.  d_status[i] (one byte) is 1 where P_i is neither the identity nor on the curve (the product of such a base is not
+ * defined), 0 elsewhere.  n > 2^30 or a null pointer with n > 0 are H2_ERR_ARGS.
+ *
+ * h2_ecc_mul_trace_device: the witness of mul::Config::assign for `count` pairs (P_i, alpha_i), alpha a Montgomery element of Fp.
+ * d_columns is ONE buffer of 10 vectors of 137 * count Montgomery elements, the chip's advice columns 0 .. 9 one after the other; rows
+ * 137 i .. 137 i + 136 hold the region "variable-base scalar mul" of multiplication i: row 0 the complete addition P + P, rows 1 - 128
+ * the two incomplete halves side by side over the bits of k = alpha + t_q (not reduced, most significant first), rows 129 - 134 the
+ * three complete iterations, rows 135 - 136 the last bit; a cell the reference leaves unassigned is zero.  The product's coordinates
+ * are columns 2 and 3 of row 136.  d_aux holds 16 Montgomery elements per multiplication, the overflow check's witnesses:
+ * s = alpha + k_254 2^130, the 14 running sums s >> 10 j (j = 0 .. 13) of its range check, eta = inv0(z_130).  d_status[i] = 1 where a
+ * denominator of the incomplete range vanished or P_i is the identity (for a point of the curve neither happens): those rows are
+ * not a witness.  Scratch (32 bytes per element, 253 elements per multiplication, at most 2^23 elements at a time) belongs to the (device, stream) context and goes back
+ * with h2_trim.  Bad arguments are H2_ERR_ARGS. */
+int h2_ecc_mul_device(const void *d_bases_xy, const void *d_scalars, size_t n, void *d_out_xy, void *d_status, void *stream);
+int h2_ecc_mul_trace_device(const void *d_bases_xy, const void *d_alphas, size_t count, void *d_columns, void *d_aux, void *d_status,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
