@@ -7,7 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-H2_OK, H2_ERR_ARGS, H2_ERR_HIP, H2_ERR_NODEV, H2_ERR_HANDLE, H2_ERR_DECODE, H2_ERR_LOOKUP, H2_ERR_PEER = 0, 1, 2, 3, 4, 5, 6, 7
+H2_OK, H2_ERR_ARGS, H2_ERR_HIP, H2_ERR_NODEV, H2_ERR_HANDLE, H2_ERR_DECODE, H2_ERR_LOOKUP, H2_ERR_PEER, H2_ERR_NOTFOUND = 0, 1, 2, 3, 4, 5, 6, 7, 8
 FP, FQ = 0, 1
 PALLAS, VESTA = 0, 1
 FORM_CANONICAL, FORM_MONTGOMERY = 0, 1
@@ -154,6 +154,9 @@ SIGNATURES = {
     "h2_sinsemilla_trace_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
     "h2_ecc_mul_device": ([vp, vp, C.c_size_t, vp, vp, vp], C.c_int),
     "h2_ecc_mul_trace_device": ([vp, vp, C.c_size_t, vp, vp, vp, vp], C.c_int),
+    "h2_ecc_fixed_tables_device": ([u64p, C.c_uint, C.c_uint64, vp, vp, vp, vp, vp], C.c_int),
+    "h2_ecc_mul_fixed_device": ([vp, C.c_uint, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_ecc_mul_fixed_trace_device": ([vp, vp, C.c_uint, vp, C.c_size_t, vp, vp, vp], C.c_int),
 }
 
 
@@ -200,6 +203,10 @@ class ConstraintSystemFailure(ValueError):
     """plonk::Error::ConstraintSystemFailure (plonk/error.rs): the witness does not satisfy the circuit."""
 
 
+class NotFound(LookupError):
+    """A search over a bounded range found nothing (H2_ERR_NOTFOUND)."""
+
+
 def check(rc: int, what: str):
     if rc == H2_OK:
         return
@@ -208,6 +215,8 @@ def check(rc: int, what: str):
         raise ValueError(f"{what}: bad arguments")
     if rc == H2_ERR_LOOKUP:
         raise ConstraintSystemFailure(f"{what}: an input value does not occur in the table")    # lookup/prover.rs:609-611
+    if rc == H2_ERR_NOTFOUND:
+        raise NotFound(f"{what}: {lib().h2_last_error().decode()}")        # e.g. find_zs_and_us' None (ecc/chip/constants.rs:117-148)
     if rc == H2_ERR_DECODE:
         raise ValueError(f"{what}: invalid point encoding")      # the reference returns io::Error (commitment.rs:193-198)
     msg = lib().h2_last_error().decode()

@@ -16,10 +16,10 @@
 // more elements ride in the same batch: ZZ ZZZ of the last accumulator, and z_130 whose inverse is the overflow check's eta.
 // The 8 complete additions (row 0's [2]P, two per complete bit, one for the last bit) take their operands from the previous result
 // and run in a kernel of their own after pass B, which keeps the inversion's registers out of the chain's loop;
-// each forms the product of its nonzero denominators -- x_q - x_p (or y_q + y_p, or 2 y_p, when that vanishes), x_p, x_q -- inverts it
+// each (complete_add, ecc_add.cuh) forms the product of its nonzero denominators -- x_q - x_p (or y_q + y_p, or 2 y_p, when that vanishes), x_p, x_q -- inverts it
 // on the lane (field_inv.cuh) and splits it: 8 inversions against the 251 rounds of 32 products, measured in profiles/ecc.txt.
 #include "common.h"
-#include "curve.cuh"
+#include "ecc_add.cuh"
 
 namespace h2 {
 namespace {
@@ -55,13 +55,6 @@ __device__ __forceinline__ void double_and_add_round(xyzz<FP> &a, const affine<F
     a.zzz = fe_mulx<FP>(zzz_r, ddd);
 }
 
-__device__ __forceinline__ fe fe_select(bool c, const fe &a, const fe &b) {
-    fe r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = c ? a.v[i] : b.v[i];
-    return r;
-}
-
 // the top bit of a 256-bit word, which then moves up by one
 __device__ __forceinline__ u32 take_top_bit(u32 (&k)[8]) {
     const u32 bit = k[7] >> 31;
@@ -69,12 +62,6 @@ __device__ __forceinline__ u32 take_top_bit(u32 (&k)[8]) {
     for (int j = 7; j > 0; j--) k[j] = (k[j] << 1) | (k[j - 1] >> 31);
     k[0] <<= 1;
     return bit;
-}
-
-__device__ __forceinline__ bool on_curve(const affine<FP> &p) {          // y^2 = x^3 + 5
-    fe five = fe_one<FP>();
-    five = fe_add<FP>(fe_dbl<FP>(fe_dbl<FP>(five)), five);
-    return fe_eq(fe_sqr<FP>(p.y), fe_add<FP>(fe_mulx<FP>(fe_sqr<FP>(p.x), p.x), five));
 }
 
 __global__ void __launch_bounds__(kET) ecc_mul(const u32 *__restrict__ bases, const u32 *__restrict__ scalars, size_t n,
@@ -99,37 +86,6 @@ __global__ void __launch_bounds__(kET) ecc_mul(const u32 *__restrict__ bases, co
     fe_store(out_xy + 16 * i, res.x);
     fe_store(out_xy + 16 * i + 8, res.y);
     status[i] = aff_is_identity(p) || on_curve(p) ? 0 : 1;
-}
-
-// Complete addition as add.rs:213-295 assigns it: lambda, alpha = inv0(x_q - x_p), beta = inv0(x_p), gamma = inv0(x_q),
-// delta = inv0(y_q + y_p) where x_q = x_p, and the sum.  One inversion: of f0 f1 f2 with f0 the first nonzero of x_q - x_p, y_q + y_p,
-// 2 y_p (the tangent's denominator when the operands are opposite), f1 = x_p, f2 = x_q, a vanishing factor replaced by one.
-struct AddWitness {
-    fe lambda, alpha, beta, gamma, delta;
-};
-__device__ __forceinline__ affine<FP> complete_add(const affine<FP> &p, const affine<FP> &q, AddWitness &w) {
-    const fe a = fe_sub<FP>(q.x, p.x), d = fe_add<FP>(q.y, p.y), one = fe_one<FP>();
-    const bool az = fe_is_zero(a), dz = fe_is_zero(d), pz = fe_is_zero(p.x), qz = fe_is_zero(q.x), yz = fe_is_zero(p.y);
-    const fe f0 = fe_select(!az, a, fe_select(!dz, d, fe_select(!yz, fe_dbl<FP>(p.y), one)));
-    const fe f1 = fe_select(pz, one, p.x), f2 = fe_select(qz, one, q.x);
-    const fe f12 = fe_mulx<FP>(f1, f2);
-    const fe all = fe_inv<FP>(fe_mulx<FP>(f0, f12));
-    const fe i0 = fe_mulx<FP>(all, f12), t = fe_mulx<FP>(all, f0);
-    const fe zero = fe_zero();
-    w.alpha = fe_select(az, zero, i0);
-    w.beta = fe_select(pz, zero, fe_mulx<FP>(t, f2));
-    w.gamma = fe_select(qz, zero, fe_mulx<FP>(t, f1));
-    w.delta = fe_select(az && !dz, i0, zero);
-    const fe xx = fe_sqr<FP>(p.x);
-    const fe num = fe_select(az, fe_add<FP>(fe_dbl<FP>(xx), xx), fe_sub<FP>(q.y, p.y));   // 3 x_p^2 over 2 y_p, or the chord
-    w.lambda = fe_select(az && yz, zero, fe_mulx<FP>(num, i0));
-    affine<FP> r;
-    r.x = fe_sub<FP>(fe_sub<FP>(fe_sqr<FP>(w.lambda), p.x), q.x);
-    r.y = fe_sub<FP>(fe_mulx<FP>(w.lambda, fe_sub<FP>(p.x, r.x)), p.y);
-    const bool none = az && dz;                                                            // P + (-P)
-    r.x = fe_select(pz, q.x, fe_select(qz, p.x, fe_select(none, zero, r.x)));
-    r.y = fe_select(pz, q.y, fe_select(qz, p.y, fe_select(none, zero, r.y)));
-    return r;
 }
 
 // k = alpha + t_q, not reduced (mul.rs:421-455), as a 256-bit word

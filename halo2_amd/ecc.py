@@ -1,5 +1,7 @@
-"""Variable-base scalar multiplication over Pallas in bulk (halo2_amd/csrc/ecc.hip): n independent products [k_i]P_i, and the
-witness of the ECC chip's variable-base `mul` (halo2_gadgets ecc/chip/mul.rs) for many multiplications at once.
+"""Scalar multiplication over Pallas in bulk.  Variable base (halo2_amd/csrc/ecc.hip): n independent products [k_i]P_i, and the
+witness of the ECC chip's variable-base `mul` (halo2_gadgets ecc/chip/mul.rs) for many multiplications at once.  Fixed base
+(halo2_amd/csrc/ecc_fixed.hip): `FixedBase` builds a base's window table, Lagrange coefficients, z and u on the device
+(ecc/chip/constants.rs), `mul_fixed`, `mul_fixed_short` and `mul_fixed_trace` multiply and witness over them (ecc/chip/mul_fixed.rs).
 
 Points are arrays of uint64 Montgomery limbs, (..., 8), the identity (0, 0); scalars of `mul` are CANONICAL integers of 4 limbs below
 2^255; the alphas of `mul_trace` are Montgomery elements of Fp, as cells are.  A CUDA int64 tensor is used in place and a CUDA tensor
@@ -10,12 +12,15 @@ import numpy as np
 
 from . import fields
 from ._lib import check, lib
-from .arithmetic import _is_torch, _stream_ptr
+from .arithmetic import _is_torch, _stream_ptr, scale_add
 
-__all__ = ["ROWS", "AUX", "mul", "mul_trace", "OffCurve", "Vanishing"]
+__all__ = ["ROWS", "AUX", "mul", "mul_trace", "OffCurve", "Vanishing",
+           "NUM_WINDOWS", "NUM_WINDOWS_SHORT", "FIXED_AUX", "FixedBase", "mul_fixed", "mul_fixed_short", "mul_fixed_trace"]
 
 ROWS = 137                                      # rows of the region "variable-base scalar mul" (mul.rs:164-293)
 AUX = 16                                        # s, the 14 running sums of its range check, eta (mul/overflow.rs:101-208)
+NUM_WINDOWS, NUM_WINDOWS_SHORT = 85, 22         # 3-bit windows of a full-width and of a 64-bit scalar (constants.rs:18-23)
+FIXED_AUX = 11                                  # the complete addition's nine cells and the product (add.rs:213-295)
 
 
 class OffCurve(ValueError):
@@ -85,4 +90,103 @@ def mul_trace(bases, alphas, with_status: bool = False):
     if with_status:
         return columns, aux, status.cpu().numpy() if host else status
     _raise(status, Vanishing, "ecc.mul_trace: no witness for")
+    return columns, aux
+
+
+class FixedBase:
+    """The four tables of a fixed base over its 3-bit windows (constants.rs: compute_window_table, compute_lagrange_coeffs,
+    find_zs_and_us), built once on the device and kept there: `points` (num_windows, 8, 8) Montgomery affine, `lagrange`
+    (num_windows, 8, 4), `zs` (num_windows,) and `us` (num_windows, 8, 4), int64 CUDA tensors.  base_xy: 8 uint64 Montgomery limbs,
+    a point of the curve.  z_limit: the exclusive bound on the z searched, 0 for the reference's 1000 * 2^16; a window without one
+    raises `_lib.NotFound`.  The integer views -- generator(), window_table(), lagrange_coeffs(), z(), u() -- read each table back once."""
+
+    def __init__(self, base_xy, num_windows: int = NUM_WINDOWS, z_limit: int = 0):
+        import ctypes as C
+
+        import torch
+        base = np.ascontiguousarray(base_xy, dtype=np.uint64).reshape(-1)
+        if base.shape != (8,):
+            raise ValueError("FixedBase: a base of 8 uint64 limbs")
+        self.num_windows, self._base, self._host = int(num_windows), base, {}
+        nw, dev = max(self.num_windows, 0), fields.current_device()
+        self.points = torch.zeros((nw, 8, 8), dtype=torch.int64, device=dev)
+        self.lagrange = torch.zeros((nw, 8, 4), dtype=torch.int64, device=dev)
+        self.zs = torch.zeros((nw,), dtype=torch.int64, device=dev)
+        self.us = torch.zeros((nw, 8, 4), dtype=torch.int64, device=dev)
+        check(lib().h2_ecc_fixed_tables_device(base.ctypes.data_as(C.POINTER(C.c_uint64)), self.num_windows, int(z_limit),
+                                               self.points.data_ptr(), self.lagrange.data_ptr(), self.zs.data_ptr(), self.us.data_ptr(),
+                                               _stream_ptr()), "h2_ecc_fixed_tables_device")
+
+    def _ints(self, name, tensor):
+        if name not in self._host:
+            flat = fields.from_limbs(tensor.cpu().numpy().view(np.uint64).reshape(-1, 4), fields.FP, True)
+            self._host[name] = flat
+        return self._host[name]
+
+    def generator(self):
+        """the base as (x, y)"""
+        return tuple(fields.from_limbs(self._base.reshape(2, 4), fields.FP, True))
+
+    def window_table(self):
+        """[w][k] = (x, y)"""
+        v = self._ints("points", self.points)
+        return [[(v[16 * w + 2 * k], v[16 * w + 2 * k + 1]) for k in range(8)] for w in range(self.num_windows)]
+
+    def lagrange_coeffs(self):
+        """[w][c]: the coefficient of X^c of window w's interpolation polynomial"""
+        v = self._ints("lagrange", self.lagrange)
+        return [v[8 * w:8 * w + 8] for w in range(self.num_windows)]
+
+    def z(self):
+        if "z" not in self._host:
+            self._host["z"] = [int(v) for v in self.zs.cpu().numpy().view(np.uint64)]
+        return self._host["z"]
+
+    def u(self):
+        """[w][k] with u^2 = y + z"""
+        v = self._ints("u", self.us)
+        return [v[8 * w:8 * w + 8] for w in range(self.num_windows)]
+
+
+def mul_fixed(fixed_base: FixedBase, scalars):
+    """[k_i]B: scalars (n, 4) canonical, of which the low 3 * num_windows bits are read -> (n, 8).  k = 0 gives the identity."""
+    import torch
+    k, host = _device(scalars, 4, "ecc.mul_fixed scalars")
+    n = k.shape[0]
+    out = torch.empty((n, 8), dtype=torch.int64, device=k.device)
+    check(lib().h2_ecc_mul_fixed_device(fixed_base.points.data_ptr(), fixed_base.num_windows, _ptr(k), n, _ptr(out), _stream_ptr()),
+          "h2_ecc_mul_fixed_device")
+    return out.cpu().numpy().view(np.uint64) if host else out
+
+
+def mul_fixed_short(fixed_base: FixedBase, magnitudes, signs):
+    """[sign_i magnitude_i]B (mul_fixed/short.rs): magnitudes (n, 4) canonical, signs n values of 1 or -1; the product of the magnitude,
+    negated here where the sign is -1."""
+    import torch
+    out = mul_fixed(fixed_base, magnitudes)
+    host = not _is_torch(out)
+    pts = torch.from_numpy(out.view(np.int64)).to(fields.current_device()) if host else out
+    s = torch.as_tensor(np.asarray(signs.cpu() if _is_torch(signs) else signs, dtype=np.int64), device=pts.device)
+    if s.shape != (pts.shape[0],) or not bool(((s == 1) | (s == -1)).all()):
+        raise ValueError("ecc.mul_fixed_short: one sign of 1 or -1 per magnitude")
+    y = pts[:, 4:].contiguous()
+    neg_y = scale_add(y.clone(), fields.scalar_limbs(fields.P - 1, fields.FP), torch.zeros_like(y), fields.FP) if y.shape[0] else y
+    pts = torch.cat([pts[:, :4], torch.where((s == -1)[:, None], neg_y, pts[:, 4:])], dim=1)
+    return pts.cpu().numpy().view(np.uint64) if host else pts
+
+
+def mul_fixed_trace(fixed_base: FixedBase, scalars):
+    """What the chip's full-width `mul_fixed` witnesses for `count` scalars (as `mul_fixed`) -> (columns, aux): columns
+    (6, num_windows * count, 4), the advice columns x_p, y_p, x_qr, y_qr, window, u with multiplication i in rows num_windows i ..,
+    zero where the reference assigns nothing; aux (count, FIXED_AUX, 4), the closing complete addition and the product (see
+    include/halo2_mi355x.h)."""
+    import torch
+    k, host = _device(scalars, 4, "ecc.mul_fixed_trace scalars")
+    count, nw = k.shape[0], fixed_base.num_windows
+    columns = torch.empty((6, nw * count, 4), dtype=torch.int64, device=k.device)
+    aux = torch.empty((count, FIXED_AUX, 4), dtype=torch.int64, device=k.device)
+    check(lib().h2_ecc_mul_fixed_trace_device(fixed_base.points.data_ptr(), fixed_base.us.data_ptr(), nw, _ptr(k), count, _ptr(columns),
+                                              _ptr(aux), _stream_ptr()), "h2_ecc_mul_fixed_trace_device")
+    if host:
+        return columns.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
     return columns, aux

@@ -1,7 +1,9 @@
-"""The variable-base half of the ECC gadget of halo2_gadgets (src/ecc.rs, ecc/chip.rs, chip/witness_point.rs, chip/add_incomplete.rs,
-chip/add.rs, chip/mul.rs, mul/incomplete.rs, mul/complete.rs, mul/overflow.rs) against `halo2_amd.circuit`, over Pallas: `EccChip`
-with `witness_point`, `witness_point_non_id`, `add_incomplete`, `add` and variable-base `mul`, and the wrappers `Point`,
-`NonIdentityPoint` and `ScalarVar`.
+"""The ECC gadget of halo2_gadgets (src/ecc.rs, ecc/chip.rs, chip/witness_point.rs, chip/add_incomplete.rs, chip/add.rs, chip/mul.rs,
+mul/incomplete.rs, mul/complete.rs, mul/overflow.rs, chip/mul_fixed.rs, mul_fixed/full_width.rs, mul_fixed/short.rs,
+mul_fixed/base_field_elem.rs) against `halo2_amd.circuit`, over Pallas: `EccChip` with `witness_point`, `witness_point_non_id`,
+`witness_point_from_constant`, `add_incomplete`, `add`, variable-base `mul`, fixed-base `mul_fixed` (full-width), `mul_fixed_short` and `mul_fixed_base_field_elem`,
+and `mul_sign`, and the wrappers `Point`, `NonIdentityPoint`, `ScalarVar`, `ScalarFixed`, `ScalarFixedShort`, `FixedPoint`,
+`FixedPointShort` and `FixedPointBaseField`.
 
 The mirror assigns cell by cell with Python integers and inv0 (x / 0 = 0, what the reference's `Assigned` evaluates to) -- the same
 regions, offsets, gates, constraint names and copy constraints as the reference:
@@ -14,7 +16,14 @@ What the reference does not have is the bulk path: `EccChip.mul_many` lays `coun
 ten advice columns come from the device (`halo2_amd.ecc.mul_trace`), then three bulk regions with their overflow checks; per
 multiplication the same gates, cells and equality constraints as `mul`, grouped differently.
 
-Fixed-base multiplication (full-width, short, base-field) and `CommitDomain` are not built."""
+`EccChip.configure(..., fixed_bases=FixedPoints(...))` goes on to the fixed-base configs in the reference's order: `mul_fixed`
+(its running sum, `fixed_z` and the gate "Running sum coordinates check"), `full_width`, `short` and `base_field_elem`.  `FixedBaseTables` holds a base's
+tables as integers, from the device (`FixedBaseTables.of(halo2_amd.ecc.FixedBase(...))`) or from anywhere else.
+`EccChip.mul_fixed_many` is the bulk path of `mul_fixed`: one region of 85 rows per multiplication whose six advice columns come from
+`halo2_amd.ecc.mul_fixed_trace` and whose fixed columns are the base's tables tiled, then one region with the complete additions.
+
+The mirror of the reference's test circuit (`MyEccCircuit`, tests/ecc_fixed_cases.py) reproduces the reference's pinned `vk_ecc_chip`
+bit for bit and its stored proof verifies.  `CommitDomain` is not built."""
 from __future__ import annotations
 
 import numpy as np
@@ -23,7 +32,7 @@ from .. import ecc as primitive
 from .. import fields
 from ..circuit import AssignedCell, Cell, ConstraintSystem, Expression, Rotation, Synthesis
 from .sinsemilla import DoubleAndAdd, NonIdentityEccPoint
-from .utilities import K, LookupRangeCheckConfig, bool_check, ternary, value_int
+from .utilities import K, LookupRangeCheckConfig, RunningSumConfig, bool_check, decompose_word, range_check, ternary, value_int
 
 FP = 0
 ROWS = primitive.ROWS
@@ -33,6 +42,8 @@ INCOMPLETE_LEN = NUM_BITS - 1 - NUM_COMPLETE_BITS
 INCOMPLETE_HI_LEN = INCOMPLETE_LEN // 2
 INCOMPLETE_LO_LEN = INCOMPLETE_LEN - INCOMPLETE_HI_LEN
 CURVE_B = 5
+FIXED_BASE_WINDOW_SIZE, H = 3, 8                                              # constants.rs:12-15
+NUM_WINDOWS, NUM_WINDOWS_SHORT = primitive.NUM_WINDOWS, primitive.NUM_WINDOWS_SHORT
 
 
 class EccPoint:
@@ -95,6 +106,12 @@ class WitnessPointConfig:
         self.q_point.enable(region, offset)
         x = region.assign_advice(self.x, offset, lambda: value[0])
         y = region.assign_advice(self.y, offset, lambda: value[1])
+        return EccPoint(x, y)
+
+    def constant_point(self, value, offset: int, region) -> EccPoint:       # witness_point.rs:145-164; the identity is (0, 0)
+        self.q_point.enable(region, offset)
+        x = region.assign_advice_from_constant(self.x, offset, value[0])
+        y = region.assign_advice_from_constant(self.y, offset, value[1])
         return EccPoint(x, y)
 
     def point_non_id(self, value, offset: int, region) -> NonIdentityEccPoint:      # witness_point.rs:167-187
@@ -550,11 +567,330 @@ class MulConfig:
         return self.add_config.assign_region(EccPoint(x, y), acc, offset, region), z_0
 
 
+# ---- constants.rs, ecc.rs FixedPoint: a base's tables ------------------------------------------------------------------------------------
+class FixedBaseTables:
+    """What the chip reads of a fixed base (ecc/chip.rs FixedPoint: generator, u, z, lagrange_coeffs) as Python integers, and the window
+    table the reference recomputes point by point while it assigns: window_table[w][k] = (x, y), lagrange_coeffs[w][c], z[w], u[w][k].
+    `device` is the `halo2_amd.ecc.FixedBase` they were read from, which the bulk path multiplies over, or None."""
+
+    def __init__(self, generator, window_table, lagrange_coeffs, z, u, device=None):
+        self.generator, self.window_table, self.lagrange_coeffs, self.z, self.u = generator, window_table, lagrange_coeffs, z, u
+        self.num_windows, self.device = len(window_table), device
+        assert len(lagrange_coeffs) == len(z) == len(u) == self.num_windows
+
+    @staticmethod
+    def of(fixed_base: "primitive.FixedBase") -> "FixedBaseTables":
+        return FixedBaseTables(fixed_base.generator(), fixed_base.window_table(), fixed_base.lagrange_coeffs(), fixed_base.z(),
+                               fixed_base.u(), device=fixed_base)
+
+
+class FixedPoints:
+    """ecc.rs FixedPoints: the bases of a circuit by the form of their scalars."""
+
+    def __init__(self, full_width=(), short=(), base_field=()):
+        self.full_width, self.short, self.base_field = tuple(full_width), tuple(short), tuple(base_field)
+
+
+# ---- mul_fixed.rs ----------------------------------------------------------------------------------------------------------------------------
+class MulFixedConfig:
+    def __init__(self, modulus, running_sum_config, lagrange_coeffs, fixed_z, window, u, add_config, add_incomplete_config):
+        self.modulus, self.running_sum_config, self.lagrange_coeffs, self.fixed_z = modulus, running_sum_config, list(lagrange_coeffs), fixed_z
+        self.window, self.u, self.add_config, self.add_incomplete_config = window, u, add_config, add_incomplete_config
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, lagrange_coeffs, window, u, add_config: AddConfig,
+                  add_incomplete_config: AddIncompleteConfig) -> "MulFixedConfig":      # mul_fixed.rs:56-104
+        meta.enable_equality(window)
+        meta.enable_equality(u)
+        q_running_sum = meta.selector()
+        running_sum_config = RunningSumConfig.configure(meta, q_running_sum, window, FIXED_BASE_WINDOW_SIZE)
+        config = MulFixedConfig(meta.modulus, running_sum_config, lagrange_coeffs, meta.fixed_column(), window, u, add_config,
+                                add_incomplete_config)
+        assert add_config.x_p == add_incomplete_config.x_p and add_config.y_p == add_incomplete_config.y_p
+        assert not {window, u} & add_config.output_columns()
+
+        def running_sum_coords(cells):                                        # mul_fixed.rs:115-129
+            q = cells.query_selector(running_sum_config.q_range_check)
+            z_cur = cells.query_advice(window, Rotation.cur())
+            z_next = cells.query_advice(window, Rotation.next())
+            word = z_cur - z_next * H                                         # a_i = z_i - 8 z_(i+1)
+            return [(name, q * poly) for name, poly in config.coords_check(cells, word)]
+        meta.create_gate("Running sum coordinates check", running_sum_coords)
+        return config
+
+    def coords_check(self, cells, window: Expression) -> list:               # mul_fixed.rs:133-169
+        y_p = cells.query_advice(self.add_config.y_p, Rotation.cur())
+        x_p = cells.query_advice(self.add_config.x_p, Rotation.cur())
+        z = cells.query_fixed(self.fixed_z)
+        u = cells.query_advice(self.u, Rotation.cur())
+        window_pow = []
+        for power in range(H):
+            acc = Expression.constant(1)
+            for _ in range(power):
+                acc = acc * window
+            window_pow.append(acc)
+        interpolated_x = Expression.constant(0)
+        for power, coeff in zip(window_pow, self.lagrange_coeffs):
+            interpolated_x = interpolated_x + (power * cells.query_fixed(coeff))
+        x_check = interpolated_x - x_p
+        y_check = u.square() - y_p - z
+        on_curve = y_p.square() - x_p.square() * x_p - Expression.constant(CURVE_B)
+        return [("check x", x_check), ("check y", y_check), ("on-curve", on_curve)]
+
+    def assign_region_inner(self, region, offset: int, windows, base: FixedBaseTables, coords_check_toggle):      # mul_fixed.rs:172-193
+        """windows: the scalar's num_windows values, integers or None.  -> (acc, mul_b): the sum of all windows but the last, and
+        the last window's point, both NonIdentityEccPoint"""
+        nw = base.num_windows
+        assert len(windows) == nw
+        for w in range(nw):                                                   # assign_fixed_constants, mul_fixed.rs:196-252
+            coords_check_toggle.enable(region, w + offset)
+            for k in range(H):
+                region.assign_fixed(self.lagrange_coeffs[k], w + offset, lambda w=w, k=k: base.lagrange_coeffs[w][k])
+            region.assign_fixed(self.fixed_z, w + offset, lambda w=w: base.z[w])
+        acc = self._process_window(region, offset, 0, windows[0], base)       # initialize_accumulator
+        for w in range(1, nw - 1):                                            # add_incomplete, mul_fixed.rs:323-360
+            mul_b = self._process_window(region, offset, w, windows[w], base)
+            acc = self.add_incomplete_config.assign_region(mul_b, acc, offset + w, region)
+        return acc, self._process_window(region, offset, nw - 1, windows[nw - 1], base)      # process_msb
+
+    def _process_window(self, region, offset: int, w: int, k, base: FixedBaseTables) -> NonIdentityEccPoint:      # mul_fixed.rs:255-305
+        point = None if k is None else base.window_table[w][k]
+        if point is not None and (point[0] == 0 or point[1] == 0):
+            raise Synthesis("mul_fixed: a window's point has a zero coordinate")
+        x = region.assign_advice(self.add_config.x_p, offset + w, lambda: point[0])
+        y = region.assign_advice(self.add_config.y_p, offset + w, lambda: point[1])
+        region.assign_advice(self.u, offset + w, lambda: base.u[w][k])
+        return NonIdentityEccPoint(x, y)
+
+
+# ---- mul_fixed/full_width.rs -----------------------------------------------------------------------------------------------------------------
+class ScalarFixed:
+    """chip.rs EccScalarFixed: a full-width scalar, an integer below 2^255 or None, and its window cells once it has been used"""
+
+    def __init__(self, value, windows=None):
+        self.value, self.windows = value, windows
+
+    @staticmethod
+    def new(chip, layouter, value) -> "ScalarFixed":                         # ecc.rs:251-259, chip.rs witness_scalar_fixed: lazily
+        return chip.witness_scalar_fixed(layouter, value)
+
+
+class FullWidthConfig:
+    def __init__(self, q_mul_fixed_full, super_config: MulFixedConfig):
+        self.q_mul_fixed_full, self.super_config = q_mul_fixed_full, super_config
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, super_config: MulFixedConfig) -> "FullWidthConfig":      # full_width.rs:20-51
+        config = FullWidthConfig(meta.selector(), super_config)
+
+        def gate(cells):
+            q = cells.query_selector(config.q_mul_fixed_full)
+            window = cells.query_advice(super_config.window, Rotation.cur())
+            checks = super_config.coords_check(cells, window) + [("window range check", range_check(window, H))]
+            return [(name, q * poly) for name, poly in checks]
+        meta.create_gate("Full-width fixed-base scalar mul", gate)
+        return config
+
+    def _witness(self, region, offset: int, value) -> ScalarFixed:          # full_width.rs:56-114
+        for idx in range(NUM_WINDOWS):
+            self.q_mul_fixed_full.enable(region, offset + idx)
+        words = [None] * NUM_WINDOWS if value is None else decompose_word(value, NUM_BITS, FIXED_BASE_WINDOW_SIZE)
+        cells = [region.assign_advice(self.super_config.window, offset + idx, lambda v=word: v) for idx, word in enumerate(words)]
+        return ScalarFixed(value, cells)
+
+    def assign(self, layouter, scalar: ScalarFixed, base: FixedBaseTables):  # full_width.rs:116-177
+        """-> (EccPoint, ScalarFixed)"""
+        assert scalar.windows is None and base.num_windows == NUM_WINDOWS
+        if scalar.value is not None and not 0 <= scalar.value < 1 << NUM_BITS:
+            raise ValueError("mul_fixed: a scalar of at most 255 bits")
+
+        def incomplete(region):
+            witnessed = self._witness(region, 0, scalar.value)
+            words = [None] * NUM_WINDOWS if scalar.value is None else decompose_word(scalar.value, NUM_BITS, FIXED_BASE_WINDOW_SIZE)
+            acc, mul_b = self.super_config.assign_region_inner(region, 0, words, base, self.q_mul_fixed_full)
+            return witnessed, acc, mul_b
+        witnessed, acc, mul_b = layouter.assign_region("Full-width fixed-base mul (incomplete addition)", incomplete)
+        result = layouter.assign_region("Full-width fixed-base mul (last window, complete addition)",
+                                        lambda region: self.super_config.add_config.assign_region(EccPoint.of(mul_b), EccPoint.of(acc), 0,
+                                                                                                  region))
+        return result, witnessed
+
+
+# ---- mul_fixed/short.rs ----------------------------------------------------------------------------------------------------------------------
+L_SCALAR_SHORT = 64                                                           # constants.rs:27
+
+
+class ScalarFixedShort:
+    """chip.rs EccScalarFixedShort: a magnitude of at most 64 bits and a sign of 1 or -1, both cells, and the running sum of the
+    magnitude once it has been used"""
+
+    def __init__(self, magnitude: AssignedCell, sign: AssignedCell, running_sum=None):
+        self.magnitude, self.sign, self.running_sum = magnitude, sign, running_sum
+
+    @staticmethod
+    def new(chip, layouter, magnitude_sign) -> "ScalarFixedShort":          # ecc.rs:285-298
+        return chip.scalar_fixed_from_signed_short(layouter, magnitude_sign)
+
+
+def _running_sum_windows(zs, m: int) -> list:
+    """mul_fixed.rs:438-495: word_i = z_i - 8 z_(i+1), its low three bits the index into the window's table"""
+    values = [value_int(z.value(), m) for z in zs]
+    if any(v is None for v in values):
+        return [None] * (len(zs) - 1)
+    return [(cur - nxt * H) % m & (H - 1) for cur, nxt in zip(values, values[1:])]
+
+
+def _signed_y(sign: AssignedCell, y: AssignedCell, m: int):
+    s, y_v = value_int(sign.value(), m), value_int(y.value(), m)
+    return None if s is None or y_v is None else (-y_v % m if s == m - 1 else y_v)
+
+
+class ShortConfig:
+    def __init__(self, modulus, q_mul_fixed_short, super_config: MulFixedConfig):
+        self.modulus, self.q_mul_fixed_short, self.super_config = modulus, q_mul_fixed_short, super_config
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, super_config: MulFixedConfig) -> "ShortConfig":      # short.rs:21-77
+        config = ShortConfig(meta.modulus, meta.selector(), super_config)
+
+        def gate(cells):
+            q = cells.query_selector(config.q_mul_fixed_short)
+            y_p = cells.query_advice(super_config.add_config.y_p, Rotation.cur())
+            y_a = cells.query_advice(super_config.add_config.y_qr, Rotation.cur())
+            last_window = cells.query_advice(super_config.u, Rotation.cur())  # z_21 = k_21
+            sign = cells.query_advice(super_config.window, Rotation.cur())
+            one = Expression.constant(1)
+            last_window_check = bool_check(last_window)
+            sign_check = sign.square() - one
+            y_check = (y_p - y_a) * (y_p + y_a)
+            negation_check = sign * y_p - y_a
+            checks = (("last_window_check", last_window_check), ("sign_check", sign_check), ("y_check", y_check),
+                      ("negation_check", negation_check))
+            return [(name, q * poly) for name, poly in checks]
+        meta.create_gate("Short fixed-base mul gate", gate)
+        return config
+
+    def assign(self, layouter, scalar: ScalarFixedShort, base: FixedBaseTables):      # short.rs:108-243
+        """-> (EccPoint, ScalarFixedShort)"""
+        m, sup = self.modulus, self.super_config
+        assert scalar.running_sum is None and base.num_windows == NUM_WINDOWS_SHORT
+
+        def incomplete(region):
+            zs = sup.running_sum_config.copy_decompose(region, 0, scalar.magnitude, True, L_SCALAR_SHORT, NUM_WINDOWS_SHORT)
+            decomposed = ScalarFixedShort(scalar.magnitude, scalar.sign, zs)
+            acc, mul_b = sup.assign_region_inner(region, 0, _running_sum_windows(zs, m), base, sup.running_sum_config.q_range_check)
+            return decomposed, acc, mul_b
+        decomposed, acc, mul_b = layouter.assign_region("Short fixed-base mul (incomplete addition)", incomplete)
+
+        def last_window(region):
+            magnitude_mul = sup.add_config.assign_region(EccPoint.of(mul_b), EccPoint.of(acc), 0, region)
+            sign = decomposed.sign.copy_advice(region, sup.window, 1)
+            decomposed.running_sum[21].copy_advice(region, sup.u, 1)          # the last window, in a free cell of the u column
+            y_val = _signed_y(sign, magnitude_mul.y(), m)
+            self.q_mul_fixed_short.enable(region, 1)
+            y_var = region.assign_advice(sup.add_config.y_p, 1, lambda: y_val)
+            return EccPoint(magnitude_mul.x(), y_var)
+        return layouter.assign_region("Short fixed-base mul (most significant word)", last_window), decomposed
+
+    def assign_scalar_sign(self, layouter, sign: AssignedCell, point: EccPoint) -> EccPoint:      # short.rs:247-305
+        m, sup = self.modulus, self.super_config
+
+        def assign(region):
+            self.q_mul_fixed_short.enable(region, 0)
+            region.assign_advice_from_constant(sup.u, 0, 0)                   # the "last window" is irrelevant here
+            sign.copy_advice(region, sup.window, 0)
+            point.y().copy_advice(region, sup.add_config.y_qr, 0)
+            signed_y = region.assign_advice(sup.add_config.y_p, 0, lambda: _signed_y(sign, point.y(), m))
+            return EccPoint(point.x(), signed_y)
+        return layouter.assign_region("Signed point", assign)
+
+
+# ---- mul_fixed/base_field_elem.rs ------------------------------------------------------------------------------------------------------------
+class BaseFieldElemConfig:
+    def __init__(self, modulus, q_mul_fixed_base_field, canon_advices, lookup_config, super_config: MulFixedConfig):
+        self.modulus, self.q_mul_fixed_base_field, self.canon_advices = modulus, q_mul_fixed_base_field, list(canon_advices)
+        self.lookup_config, self.super_config = lookup_config, super_config
+        self.t_p = modulus - (1 << 254)
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, canon_advices, lookup_config: LookupRangeCheckConfig,
+                  super_config: MulFixedConfig) -> "BaseFieldElemConfig":    # base_field_elem.rs:32-163
+        for advice in canon_advices:
+            meta.enable_equality(advice)
+        config = BaseFieldElemConfig(meta.modulus, meta.selector(), canon_advices, lookup_config, super_config)
+        inc = super_config.add_incomplete_config
+        assert not set(canon_advices) & {inc.x_p, inc.y_p, inc.x_qr, inc.y_qr}
+        c = config.canon_advices
+
+        def gate(cells):
+            q = cells.query_selector(config.q_mul_fixed_base_field)
+            alpha = cells.query_advice(c[0], Rotation.prev())
+            z_84_alpha = cells.query_advice(c[2], Rotation.prev())            # the last three bits of alpha
+            # alpha = alpha_0 (252 bits) || alpha_1 (2 bits) || alpha_2 (1 bit); alpha_0 is derived, not witnessed
+            alpha_0 = alpha - (z_84_alpha * (1 << 252))
+            alpha_1 = cells.query_advice(c[1], Rotation.cur())
+            alpha_2 = cells.query_advice(c[2], Rotation.cur())
+            alpha_0_prime = cells.query_advice(c[0], Rotation.cur())
+            z_13_alpha_0_prime = cells.query_advice(c[0], Rotation.next())
+            z_44_alpha = cells.query_advice(c[1], Rotation.next())
+            z_43_alpha = cells.query_advice(c[2], Rotation.next())
+            alpha_1_range_check = range_check(alpha_1, 1 << 2)
+            alpha_2_range_check = bool_check(alpha_2)
+            z_84_alpha_check = z_84_alpha - (alpha_1 + alpha_2 * (1 << 2))
+            alpha_0_prime_check = alpha_0_prime - (alpha_0 + Expression.constant(1 << 130) - Expression.constant(config.t_p))
+            # MSB = 1: alpha_1 = 0, alpha_0 < 2^130 (its top 120 bits and bits 130, 131 vanish) and alpha_0 + 2^130 - t_p < 2^130
+            alpha_0_hi_120 = z_44_alpha - z_84_alpha * Expression.constant(1 << 120)
+            a_43 = z_43_alpha - z_44_alpha * H
+            checks = (("MSB = 1 => alpha_1 = 0", alpha_2 * alpha_1),
+                      ("MSB = 1 => alpha_0_hi_120 = 0", alpha_2 * alpha_0_hi_120),
+                      ("MSB = 1 => a_43 = 0 or 1", alpha_2 * bool_check(a_43)),
+                      ("MSB = 1 => z_13_alpha_0_prime = 0", alpha_2 * z_13_alpha_0_prime),
+                      ("alpha_1_range_check", alpha_1_range_check), ("alpha_2_range_check", alpha_2_range_check),
+                      ("z_84_alpha_check", z_84_alpha_check), ("alpha_0_prime check", alpha_0_prime_check))
+            return [(name, q * poly) for name, poly in checks]
+        meta.create_gate("Canonicity checks", gate)
+        return config
+
+    def assign(self, layouter, scalar: AssignedCell, base: FixedBaseTables) -> EccPoint:      # base_field_elem.rs:165-378
+        m, sup, c = self.modulus, self.super_config, self.canon_advices
+        assert base.num_windows == NUM_WINDOWS
+
+        def incomplete(region):
+            zs = sup.running_sum_config.copy_decompose(region, 0, scalar, True, NUM_BITS, NUM_WINDOWS)
+            acc, mul_b = sup.assign_region_inner(region, 0, _running_sum_windows(zs, m), base, sup.running_sum_config.q_range_check)
+            return zs, acc, mul_b
+        zs, acc, mul_b = layouter.assign_region("Base-field elem fixed-base mul (incomplete addition)", incomplete)
+        result = layouter.assign_region("Base-field elem fixed-base mul (complete addition)",
+                                        lambda region: sup.add_config.assign_region(EccPoint.of(mul_b), EccPoint.of(acc), 0, region))
+        alpha, z_43_alpha, z_44_alpha, z_84_alpha = zs[0], zs[43], zs[44], zs[84]
+        alpha_v, z_84_v = value_int(alpha.value(), m), value_int(z_84_alpha.value(), m)
+        known = alpha_v is not None and z_84_v is not None
+        alpha_0_prime_v = (alpha_v - z_84_v * (1 << 252) + (1 << 130) - self.t_p) % m if known else None
+        sums = self.lookup_config.witness_check(layouter, alpha_0_prime_v, 13, False)
+        alpha_0_prime, z_13_alpha_0_prime = sums[0], sums[13]
+
+        def canonicity(region):
+            self.q_mul_fixed_base_field.enable(region, 1)
+            alpha.copy_advice(region, c[0], 0)
+            z_84_alpha.copy_advice(region, c[2], 0)
+            alpha_0_prime.copy_advice(region, c[0], 1)
+            region.assign_advice(c[1], 1, lambda: alpha_v >> 252 & 3)         # alpha_1 = alpha[252..=253]
+            region.assign_advice(c[2], 1, lambda: alpha_v >> 254 & 1)         # alpha_2 = alpha[254]
+            z_13_alpha_0_prime.copy_advice(region, c[0], 2)
+            z_44_alpha.copy_advice(region, c[1], 2)
+            z_43_alpha.copy_advice(region, c[2], 2)
+        layouter.assign_region("Canonicity checks", canonicity)
+        return result
+
+
 # ---- chip.rs -------------------------------------------------------------------------------------------------------------------------------
 class EccConfig:
-    def __init__(self, advices, add_incomplete, add, mul, witness_point, lookup_config, lagrange_coeffs):
+    def __init__(self, advices, add_incomplete, add, mul, witness_point, lookup_config, lagrange_coeffs, fixed_bases=None,
+                 mul_fixed=None, mul_fixed_full=None, mul_fixed_short=None, mul_fixed_base_field=None):
         self.advices, self.add_incomplete, self.add, self.mul = list(advices), add_incomplete, add, mul
         self.witness_point, self.lookup_config, self.lagrange_coeffs = witness_point, lookup_config, list(lagrange_coeffs)
+        self.fixed_bases, self.mul_fixed, self.mul_fixed_full, self.mul_fixed_short = fixed_bases, mul_fixed, mul_fixed_full, mul_fixed_short
+        self.mul_fixed_base_field = mul_fixed_base_field
 
 
 class ScalarVar:
@@ -587,23 +923,50 @@ class MulMany:
         return self.alpha_cells.cell(3 * i + 1)
 
 
+class MulFixedMany:
+    """What `mul_fixed_many` returns: the cells of multiplication i by position.  outputs: (count, 2, 4) Montgomery x and y of the
+    products (None without a witness)."""
+
+    def __init__(self, config: EccConfig, count: int):
+        self.config, self.count, self.region_index, self.add_region_index, self.outputs = config, count, None, None, None
+
+    def result_x(self, i: int) -> Cell:
+        return Cell(self.add_region_index, 2 * i + 1, self.config.add.x_qr)
+
+    def result_y(self, i: int) -> Cell:
+        return Cell(self.add_region_index, 2 * i + 1, self.config.add.y_qr)
+
+    def window(self, i: int, w: int) -> Cell:
+        return Cell(self.region_index, NUM_WINDOWS * i + w, self.config.mul_fixed.window)
+
+
 class EccChip:
     def __init__(self, config: EccConfig):
         self.config = config
 
     @staticmethod
-    def configure(meta: ConstraintSystem, advices, lagrange_coeffs, range_check: LookupRangeCheckConfig) -> EccConfig:
-        """chip.rs:273-333, the variable-base part: the gates of witness_point, add_incomplete, add and mul (hi, lo, complete, overflow,
-        then the LSB gate) on the reference's columns, with enable_equality, selectors and gates created in the reference's order.
-        The fixed-base configs are NOT created and `lagrange_coeffs` is stored unused: a follow-up appends the fixed-base gates after
-        these, and only then does a circuit reproduce the reference's pinned vk_ecc_chip."""
+    def configure(meta: ConstraintSystem, advices, lagrange_coeffs, range_check: LookupRangeCheckConfig,
+                  fixed_bases: FixedPoints | None = None) -> EccConfig:
+        """chip.rs:273-333: the gates of witness_point, add_incomplete, add and mul (hi, lo, complete, overflow, then the LSB gate) on
+        the reference's columns, with enable_equality, selectors and gates created in the reference's order.  With `fixed_bases` it goes
+        on as chip.rs:296-320 does: mul_fixed (window and u on advices 4 and 5, the running sum's "range check" gate, fixed_z, "Running
+        sum coordinates check"), then full_width, short and base_field_elem (on advices 6 - 8).  Without, nothing fixed-base is created
+        and `lagrange_coeffs` is stored unused.  A circuit configured this way reproduces the reference's pinned vk_ecc_chip
+        (tests/test_gpu_ecc_fixed_circuit.py)."""
         a = list(advices)
         assert len(a) == 10 and len(lagrange_coeffs) == 8
         witness_point = WitnessPointConfig.configure(meta, a[0], a[1])
         add_incomplete = AddIncompleteConfig.configure(meta, a[0], a[1], a[2], a[3])
         add = AddConfig.configure(meta, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8])
         mul = MulConfig.configure(meta, add, range_check, a)
-        return EccConfig(a, add_incomplete, add, mul, witness_point, range_check, lagrange_coeffs)
+        if fixed_bases is None:
+            return EccConfig(a, add_incomplete, add, mul, witness_point, range_check, lagrange_coeffs)
+        mul_fixed = MulFixedConfig.configure(meta, lagrange_coeffs, a[4], a[5], add, add_incomplete)
+        mul_fixed_full = FullWidthConfig.configure(meta, mul_fixed)
+        mul_fixed_short = ShortConfig.configure(meta, mul_fixed)
+        mul_fixed_base_field = BaseFieldElemConfig.configure(meta, a[6:9], range_check, mul_fixed)
+        return EccConfig(a, add_incomplete, add, mul, witness_point, range_check, lagrange_coeffs, fixed_bases, mul_fixed, mul_fixed_full,
+                         mul_fixed_short, mul_fixed_base_field)
 
     # ---- EccInstructions (chip.rs:431-600) -------------------------------------------------------------------------------------------------
     def constrain_equal(self, layouter, a, b) -> None:
@@ -615,6 +978,10 @@ class EccChip:
     def witness_point(self, layouter, value) -> EccPoint:
         """value: (x, y) integers, (0, 0) or None for the identity... None alone is an unknown value"""
         return layouter.assign_region("witness point", lambda region: self.config.witness_point.point(value, 0, region))
+
+    def witness_point_from_constant(self, layouter, value) -> EccPoint:
+        """value: (x, y) integers fixed by the circuit, (0, 0) the identity (chip.rs:471-481)"""
+        return layouter.assign_region("witness point (constant)", lambda region: self.config.witness_point.constant_point(value, 0, region))
 
     def witness_point_non_id(self, layouter, value) -> NonIdentityEccPoint:
         return layouter.assign_region("witness non-identity point", lambda region: self.config.witness_point.point_non_id(value, 0, region))
@@ -635,7 +1002,117 @@ class EccChip:
         alpha = scalar.cell if isinstance(scalar, ScalarVar) else scalar
         return self.config.mul.assign(layouter, alpha, base)
 
-    # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def witness_scalar_fixed(self, layouter, value) -> ScalarFixed:          # chip.rs:536-548: witnessed lazily, where it is used
+        return ScalarFixed(value)
+
+    def mul_fixed(self, layouter, scalar: ScalarFixed, base: FixedBaseTables):
+        """[scalar]base, full-width (chip.rs:602-613).  -> (EccPoint, ScalarFixed)"""
+        if self.config.mul_fixed_full is None:
+            raise ValueError("mul_fixed: the chip was configured without fixed_bases")
+        return self.config.mul_fixed_full.assign(layouter, scalar, base)
+
+    def scalar_fixed_from_signed_short(self, layouter, magnitude_sign) -> ScalarFixedShort:      # chip.rs:516-528: constrained lazily
+        magnitude, sign = magnitude_sign
+        return ScalarFixedShort(magnitude, sign)
+
+    def mul_fixed_short(self, layouter, scalar: ScalarFixedShort, base: FixedBaseTables):
+        """[sign magnitude]base over the base's 22-window tables (chip.rs:613-625).  -> (EccPoint, ScalarFixedShort)"""
+        if self.config.mul_fixed_short is None:
+            raise ValueError("mul_fixed_short: the chip was configured without fixed_bases")
+        return self.config.mul_fixed_short.assign(layouter, scalar, base)
+
+    def mul_fixed_base_field_elem(self, layouter, base_field_elem: AssignedCell, base: FixedBaseTables) -> EccPoint:
+        """[alpha]base for a cell alpha of Fp read as an integer, with its canonicity checked (chip.rs:627-640)"""
+        if self.config.mul_fixed_base_field is None:
+            raise ValueError("mul_fixed_base_field_elem: the chip was configured without fixed_bases")
+        return self.config.mul_fixed_base_field.assign(layouter, base_field_elem, base)
+
+    def mul_sign(self, layouter, sign: AssignedCell, point: EccPoint) -> EccPoint:
+        """[sign]point for a sign constrained to 1 or -1 by the short gate (chip.rs:564-578)"""
+        if self.config.mul_fixed_short is None:
+            raise ValueError("mul_sign: the chip was configured without fixed_bases")
+        return self.config.mul_fixed_short.assign_scalar_sign(layouter, sign, EccPoint.of(point))
+
+    # ---- the bulk paths --------------------------------------------------------------------------------------------------------------------
+    def mul_fixed_many(self, layouter, fixed_base: FixedBaseTables, scalars, values=None, trace=None) -> MulFixedMany:
+        """`count` full-width multiplications [k_i]B: ONE region of 85 * count rows whose advice columns 0 - 5 come from the device
+        (`ecc.mul_fixed_trace`) and whose fixed columns are the base's tables tiled, then one region with the `count` complete
+        additions, two rows each.  Per multiplication the gates, cells and equality constraints of `mul_fixed`.
+
+        scalars: integers below 2^255 (None each without a witness).  values: (count, 4) canonical limbs where the caller has them on
+        the device already; trace: (columns, aux) where the caller has them (else `ecc.mul_fixed_trace`, once, over
+        `fixed_base.device`).  Without a witness (keygen) the same shape is laid out and nothing is launched."""
+        import torch
+        c = self.config
+        if c.mul_fixed_full is None:
+            raise ValueError("mul_fixed_many: the chip was configured without fixed_bases")
+        count, nw = len(scalars), NUM_WINDOWS
+        assert fixed_base.num_windows == nw
+        total = nw * count
+        if not layouter.cs.collect_advice:
+            trace = None
+        elif trace is None and count:
+            if values is None:
+                if any(k is None for k in scalars):
+                    raise Synthesis("mul_fixed_many: a witness is needed and there is none")
+                values = fields.to_limbs(list(scalars), FP, montgomery=False)
+            if fixed_base.device is None:
+                raise ValueError("mul_fixed_many: the tables have no device copy to multiply over")
+            k = values if torch.is_tensor(values) else torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint64).view(np.int64)) \
+                .to(fields.current_device())
+            trace = primitive.mul_fixed_trace(fixed_base.device, k)
+        columns = aux = None
+        if trace is not None:
+            columns, aux = [t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64))
+                            for t in trace]
+            if tuple(columns.shape) != (6, total, 4) or tuple(aux.shape) != (count, primitive.FIXED_AUX, 4):
+                raise ValueError("mul_fixed_many: the trace is ((6, 85 * count, 4), (count, 11, 4))")
+
+        def blank(rows):
+            return np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (rows, 4))
+        add, inc, fixed, full = c.add, c.add_incomplete, c.mul_fixed, c.mul_fixed_full
+        a = c.advices
+        base_rows = nw * np.arange(count, dtype=np.int64)
+        result = MulFixedMany(c, count)
+
+        def assign(region):
+            index = region.region_index
+            for j in range(6):
+                assert a[j] == (add.x_p, add.y_p, add.x_qr, add.y_qr, fixed.window, fixed.u)[j]
+                region.assign_advice_column(a[j], 0, blank(total) if columns is None else columns[j])
+            if count:
+                for k in range(H):
+                    coeffs = fields.to_limbs([row[k] for row in fixed_base.lagrange_coeffs], FP)
+                    region.assign_fixed_column(fixed.lagrange_coeffs[k], 0, np.tile(coeffs, (count, 1)))
+                region.assign_fixed_column(fixed.fixed_z, 0, np.tile(fields.to_limbs(list(fixed_base.z), FP), (count, 1)))
+            region.enable_selector_rows(full.q_mul_fixed_full, np.arange(total, dtype=np.int64))
+            region.enable_selector_rows(inc.q_add_incomplete, (base_rows[:, None] + np.arange(1, nw - 1, dtype=np.int64)[None, :]).reshape(-1))
+            for i in range(count):                                            # window 1's addition starts from window 0's point
+                region.constrain_equal(Cell(index, nw * i + 1, add.x_qr), Cell(index, nw * i, add.x_p))
+                region.constrain_equal(Cell(index, nw * i + 1, add.y_qr), Cell(index, nw * i, add.y_p))
+            return index
+        result.region_index = layouter.assign_region("Full-width fixed-base mul (incomplete addition) many", assign)
+
+        def additions(region):
+            index = region.region_index
+            for j, column in enumerate((add.x_p, add.y_p, add.x_qr, add.y_qr, add.lambda_, add.alpha, add.beta, add.gamma, add.delta)):
+                if aux is None:
+                    values_ = blank(2 * count)
+                else:
+                    second = aux[:, 9 + (j - 2)] if j in (2, 3) else torch.zeros_like(aux[:, j])
+                    values_ = torch.stack([aux[:, j], second], dim=1).reshape(2 * count, 4)
+                region.assign_advice_column(column, 0, values_)
+            region.enable_selector_rows(add.q_add, 2 * np.arange(count, dtype=np.int64))
+            for i in range(count):
+                last = nw * i + nw - 1
+                for column in (add.x_p, add.y_p, add.x_qr, add.y_qr):         # the last window's point and the accumulator
+                    region.constrain_equal(Cell(index, 2 * i, column), Cell(result.region_index, last, column))
+            return index
+        result.add_region_index = layouter.assign_region("Full-width fixed-base mul (last window, complete addition) many", additions)
+        if aux is not None and count:
+            result.outputs = aux[:, 9:11].contiguous()
+        return result
+
     def mul_many(self, layouter, bases, alphas, values=None, trace=None) -> MulMany:
         """`count` multiplications [alpha_i] base_i: ONE region of ROWS * count rows whose ten advice columns come from the device,
         then three bulk regions with the overflow checks (the s cells; the 14-row range checks of s; the 3-row gate blocks).  Per
@@ -812,6 +1289,59 @@ class Point(_PointBase):
     @staticmethod
     def new(chip: EccChip, layouter, value) -> "Point":
         return Point(chip, chip.witness_point(layouter, value))
+
+    @staticmethod
+    def new_from_constant(chip: EccChip, layouter, value) -> "Point":       # ecc.rs:500-508
+        return Point(chip, chip.witness_point_from_constant(layouter, value))
+
+    def mul_sign(self, layouter, sign: AssignedCell) -> "Point":            # ecc.rs:441-451
+        return Point(self.chip, self.chip.mul_sign(layouter, sign, self._inner))
+
+
+class FixedPoint:
+    """ecc.rs:577-607: a full-width fixed base"""
+
+    def __init__(self, chip: EccChip, inner: FixedBaseTables):
+        self.chip, self._inner = chip, inner
+
+    @staticmethod
+    def from_inner(chip: EccChip, inner: FixedBaseTables) -> "FixedPoint":
+        return FixedPoint(chip, inner)
+
+    def mul(self, layouter, by: ScalarFixed):
+        """-> (Point, ScalarFixed)"""
+        point, scalar = self.chip.mul_fixed(layouter, by, self._inner)
+        return Point(self.chip, point), scalar
+
+
+class FixedPointShort:
+    """ecc.rs:640-672: a fixed base multiplied by short signed scalars, over its 22-window tables"""
+
+    def __init__(self, chip: EccChip, inner: FixedBaseTables):
+        self.chip, self._inner = chip, inner
+
+    @staticmethod
+    def from_inner(chip: EccChip, inner: FixedBaseTables) -> "FixedPointShort":
+        return FixedPointShort(chip, inner)
+
+    def mul(self, layouter, by: ScalarFixedShort):
+        """-> (Point, ScalarFixedShort)"""
+        point, scalar = self.chip.mul_fixed_short(layouter, by, self._inner)
+        return Point(self.chip, point), scalar
+
+
+class FixedPointBaseField:
+    """ecc.rs:609-638: a fixed base multiplied by elements of the base field"""
+
+    def __init__(self, chip: EccChip, inner: FixedBaseTables):
+        self.chip, self._inner = chip, inner
+
+    @staticmethod
+    def from_inner(chip: EccChip, inner: FixedBaseTables) -> "FixedPointBaseField":
+        return FixedPointBaseField(chip, inner)
+
+    def mul(self, layouter, by: AssignedCell) -> "Point":
+        return Point(self.chip, self.chip.mul_fixed_base_field_elem(layouter, by, self._inner))
 
 
 class NonIdentityPoint(_PointBase):

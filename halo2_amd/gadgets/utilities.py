@@ -4,6 +4,7 @@ calls, so that a circuit built from them prints the reference's pinned key.
 
     LookupRangeCheckConfig   the K = 10 running-sum range check over a lookup table (the plain variant)
     CondSwapChip             a' , b' = swap ? (b, a) : (a, b)
+    RunningSumConfig         the running-sum decomposition into windows of at most 3 bits (utilities/decompose_running_sum.rs)
     bool_check, ternary, range_check, bitrange_subset, i2lebsp, lebs2ip, load_private"""
 from __future__ import annotations
 
@@ -42,6 +43,13 @@ def i2lebsp(value: int, num_bits: int) -> list:
 
 def lebs2ip(bits) -> int:
     return sum(1 << i for i, b in enumerate(bits) if b)
+
+
+def decompose_word(word: int, word_num_bits: int, window_num_bits: int) -> list:
+    """utilities.rs:184-204: the low word_num_bits bits of `word` in windows of window_num_bits, low window first, the last one padded"""
+    word &= (1 << word_num_bits) - 1
+    count = -(-word_num_bits // window_num_bits)
+    return [word >> (window_num_bits * i) & ((1 << window_num_bits) - 1) for i in range(count)]
 
 
 def value_int(value, modulus: int):
@@ -241,3 +249,51 @@ class CondSwapChip:
             b_swapped = region.assign_advice(c.b_swapped, 0, lambda: second)
             return a_swapped, b_swapped
         return layouter.assign_region("swap", assign)
+
+
+# ---- RunningSumConfig (decompose_running_sum.rs:47-206) ----------------------------------------------------------------------------------------
+class RunningSumConfig:
+    """z_0 = alpha, z_(i+1) = (z_i - k_i) / 2^window_num_bits with every k_i range-checked by a polynomial of degree 2^window_num_bits."""
+
+    def __init__(self, modulus, q_range_check, z, window_num_bits):
+        self.modulus, self.q_range_check, self.z, self.window_num_bits = modulus, q_range_check, z, window_num_bits
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, q_range_check: Selector, z: Column, window_num_bits: int = 3) -> "RunningSumConfig":
+        assert window_num_bits <= 3
+        meta.enable_equality(z)
+        config = RunningSumConfig(meta.modulus, q_range_check, z, window_num_bits)
+
+        def gate(cells):
+            q = cells.query_selector(config.q_range_check)
+            z_cur = cells.query_advice(config.z, Rotation.cur())
+            z_next = cells.query_advice(config.z, Rotation.next())
+            word = z_cur - z_next * (1 << window_num_bits)                    # k_i = z_i - 2^K z_(i+1)
+            return [("range check", q * range_check(word, 1 << window_num_bits))]
+        meta.create_gate("range check", gate)
+        return config
+
+    def witness_decompose(self, region, offset: int, alpha, strict: bool, word_num_bits: int, num_windows: int) -> list:
+        z_0 = region.assign_advice(self.z, offset, lambda: alpha)
+        return self._decompose(region, offset, z_0, strict, word_num_bits, num_windows)
+
+    def copy_decompose(self, region, offset: int, alpha: AssignedCell, strict: bool, word_num_bits: int, num_windows: int) -> list:
+        z_0 = alpha.copy_advice(region, self.z, offset)
+        return self._decompose(region, offset, z_0, strict, word_num_bits, num_windows)
+
+    def _decompose(self, region, offset: int, z_0: AssignedCell, strict: bool, word_num_bits: int, num_windows: int) -> list:
+        """-> [z_0 .. z_num_windows]"""
+        bits, m = self.window_num_bits, self.modulus
+        assert bits * num_windows < word_num_bits + bits                      # no empty window
+        for idx in range(num_windows):
+            self.q_range_check.enable(region, offset + idx)
+        z_v = value_int(z_0.value(), m)
+        words = [None] * num_windows if z_v is None else decompose_word(z_v, word_num_bits, bits)[:num_windows]
+        inv = pow(1 << bits, -1, m)
+        zs = [z_0]
+        for i, word in enumerate(words):
+            z_v = None if z_v is None else (z_v - word) * inv % m
+            zs.append(region.assign_advice(self.z, offset + i + 1, lambda v=z_v: v))
+        if strict:
+            region.constrain_constant(zs[-1].cell(), 0)
+        return zs

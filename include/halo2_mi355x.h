@@ -46,6 +46,7 @@ extern "C" {
 #define H2_ERR_DECODE 5 /* a compressed point does not decode (where pasta_curves' from_bytes returns None) */
 #define H2_ERR_LOOKUP 6 /* permute_expression_pair: an input value does not occur in the table (Error::ConstraintSystemFailure) */
 #define H2_ERR_PEER 7   /* a split multiexp / commit: ANOTHER rank failed its range; no result is written (a partial sum would be a wrong point) */
+#define H2_ERR_NOTFOUND 8 /* h2_ecc_fixed_tables_device: a window has no z below z_limit (find_zs_and_us returns None) */
 
 #define H2_FP 0
 #define H2_FQ 1
@@ -646,6 +647,44 @@ int h2_sinsemilla_trace_device(const void *d_pieces, size_t count, const uint32_
 int h2_ecc_mul_device(const void *d_bases_xy, const void *d_scalars, size_t n, void *d_out_xy, void *d_status, void *stream);
 int h2_ecc_mul_trace_device(const void *d_bases_xy, const void *d_alphas, size_t count, void *d_columns, void *d_aux, void *d_status,
                             void *stream);
+
+/* ---- Fixed-base scalar multiplication over Pallas (halo2_gadgets ecc/chip/constants.rs, mul_fixed.rs, mul_fixed/full_width.rs) ---- */
+/* A fixed base B has four tables over its 3-bit windows; num_windows is 85 (NUM_WINDOWS) or 22 (NUM_WINDOWS_SHORT), any value from 2 to
+ * 85 is accepted, another is H2_ERR_ARGS.  Points are Montgomery affine (8 limbs), the identity is (0, 0).
+ *
+ * h2_ecc_fixed_tables_device: compute_window_table, compute_lagrange_coeffs and find_zs_and_us of the base base_xy (HOST memory, 8
+ * limbs) in one call; the four outputs are device buffers.  d_points: num_windows * 8 points, [w][k] = [(k + 2) 8^w]B for
+ * w < num_windows - 1 and [k 8^w - sum_{j<w} 2^(3j+1)]B for the last window.  d_lagrange: num_windows * 8 Montgomery coefficients,
+ * [w][c] the coefficient of X^c of the polynomial of degree 7 through (k, x(points[w][k])), k = 0 .. 7.  d_z: num_windows uint64, the
+ * SMALLEST z >= 0 such that for all eight y of the window z + y is a square or zero and z - y is neither.  d_u: num_windows * 8
+ * Montgomery elements with u^2 = y + z; the reference does not pin which root: it is the one this library's Tonelli-Shanks
+ * (field_sqrt.cuh, fe_sqrt) returns, zero for zero.  z_limit is the exclusive bound on the candidates, 0 for the reference's
+ * 1000 * 2^16; a window without a z below it makes the call return H2_ERR_NOTFOUND (the reference's None): d_points and d_lagrange
+ * are then complete, d_z holds 2^64 - 1 for each such window and d_u is not written.  A base that is the identity, off the curve
+ * or not reduced, and a null pointer, are H2_ERR_ARGS.  The search runs in rounds of 2^15 candidates per unfinished window and the
+ * host reads the minima back after each, so the call returns with the stream idle and the tables complete.  Scratch (under 100 KB)
+ * belongs to the (device, stream) context and goes back with h2_trim.
+ *
+ * h2_ecc_mul_fixed_device: n products d_out_xy[i] = [k_i]B from d_points, one lane each.  d_scalars holds n CANONICAL integers of 4
+ * limbs of which only the low 3 * num_windows bits are read (any value below 2^255 at 85 windows, as h2_ecc_mul_device).  The sum is
+ * the reference's, sum_{w < nw-1} points[w][k_w] + points[nw-1][k_(nw-1)], its last addition complete: k = 0 gives (0, 0).  n > 2^30
+ * or a null pointer with n > 0 are H2_ERR_ARGS.
+ *
+ * h2_ecc_mul_fixed_trace_device: the witness of mul_fixed::Config::assign_region_inner for `count` scalars (as above), and of the
+ * complete addition full_width::Config::assign closes with.  d_columns is ONE buffer of 6 vectors of num_windows * count Montgomery
+ * elements, the chip's advice columns 0 .. 5 one after the other: x_p, y_p, x_qr, y_qr, window, u.  Rows num_windows i .. belong to
+ * multiplication i; row w holds points[w][k_w] in x_p, y_p, k_w in window, u[w][k_w] in u; rows 1 .. nw-2 hold the accumulator before
+ * the row's incomplete addition in x_qr, y_qr, row nw-1 the accumulator after the last one, and row 0 zeros there (the reference
+ * assigns nothing).  Every element is written.  d_aux holds 11 Montgomery elements per multiplication: the complete addition's row
+ * x_p, y_p (the last window's point), x_qr, y_qr (the accumulator), lambda, alpha, beta, gamma, delta (add.rs), then the product's x
+ * and y.  Scratch (32 bytes per element, num_windows - 2 elements per multiplication, at most 2^23 elements at a time: 101 067
+ * multiplications of 85 windows a chunk) belongs to the (device, stream) context and goes back with h2_trim.  Bad arguments are
+ * H2_ERR_ARGS. */
+int h2_ecc_fixed_tables_device(const uint64_t *base_xy, unsigned num_windows, uint64_t z_limit, void *d_points, void *d_lagrange, void *d_z,
+                               void *d_u, void *stream);
+int h2_ecc_mul_fixed_device(const void *d_points, unsigned num_windows, const void *d_scalars, size_t n, void *d_out_xy, void *stream);
+int h2_ecc_mul_fixed_trace_device(const void *d_points, const void *d_u, unsigned num_windows, const void *d_scalars, size_t count,
+                                  void *d_columns, void *d_aux, void *stream);
 
 #ifdef __cplusplus
 }
