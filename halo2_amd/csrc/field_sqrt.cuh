@@ -1,5 +1,11 @@
 // Square roots in the Pasta base fields (Tonelli-Shanks: p - 1 = 2^32 T for both) and the curve constant b = 5, shared by the
-// point codec (points.hip: `from_bytes`) and the hash-to-curve map (h2c.hip: simplified SWU).
+// point codec (points.hip: `from_bytes`) and the hash-to-curve map (h2c_map.cuh: simplified SWU).
+// Checked against the oracle's sqrt_mod (the same algorithm from the same 5^T, so the same root of the two) through the codec
+// (tests/test_gpu_params_io.py) and the map (tests/test_gpu_reference_goldens.py) on random and hashed inputs, and on its own in
+// tests/test_gpu_h2c_edges.py (driver: tests/native/h2c_edge_driver.hip): four elements of every 2-adic order 2^0 .. 2^32 of a^T --
+// the loop never entered, every `v - k - 1` that can occur (0 .. 30: k >= 1 in the loop), the `++k == v` exit -- a = 0, p - 1, and
+// waves whose lanes need different numbers of rounds; test_decoder_at_every_two_adic_order there does the same through
+// points_decompress.
 #pragma once
 #include "field.cuh"
 

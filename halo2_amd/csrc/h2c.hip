@@ -16,11 +16,9 @@
 #include <vector>
 
 #include "common.h"
-#include "field_sqrt.cuh"
+#include "h2c_map.cuh"
 
 namespace h2 {
-
-#include "h2c_consts.inc"
 
 typedef unsigned long long u64l;
 
@@ -95,27 +93,6 @@ template <int F> __device__ fe h2c_field_from_be64(const unsigned char d[64]) {
     return fe_add<F>(fe_mulx<F>(lo, fe_r2<F>()), fe_mulx<F>(hi, h2c_r3<F>()));
 }
 
-template <int F> __device__ __forceinline__ u32 fe_sgn0(const fe &a_mont) { return fe_from_mont<F>(a_mont).v[0] & 1u; }
-
-template <int F> __device__ __forceinline__ fe iso_rhs(const fe &x) {      // x^3 + a x + b on the iso curve
-    return fe_add<F>(fe_mulx<F>(fe_add<F>(fe_sqr<F>(x), h2c_iso_a<F>()), x), h2c_iso_b<F>());
-}
-
-// RFC 9380 6.6.2 (AB != 0)
-template <int F> __device__ void map_to_curve_simple_swu(const fe &u, fe &x, fe &y) {
-    const fe zu2 = fe_mulx<F>(h2c_swu_z<F>(), fe_sqr<F>(u));
-    const fe tv = fe_add<F>(fe_sqr<F>(zu2), zu2);
-    fe x1;
-    if (fe_is_zero(tv)) x1 = h2c_b_over_za<F>();
-    else x1 = fe_mulx<F>(h2c_neg_b_over_a<F>(), fe_add<F>(fe_one<F>(), fe_inv<F>(tv)));
-    x = x1;
-    if (!fe_sqrt<F>(iso_rhs<F>(x1), y)) {
-        x = fe_mulx<F>(zu2, x1);
-        (void)fe_sqrt<F>(iso_rhs<F>(x), y);          // one of the two is always a square
-    }
-    if (fe_sgn0<F>(u) != fe_sgn0<F>(y)) y = fe_neg<F>(y);
-}
-
 template <int F>
 __global__ void __launch_bounds__(128) h2c_kernel(const unsigned char *__restrict__ msgs, u32 msg_len, size_t count, H2cDst dst, int out_mont,
                                                   u32 *__restrict__ out_xy) {
@@ -135,36 +112,8 @@ __global__ void __launch_bounds__(128) h2c_kernel(const unsigned char *__restric
     blake2b_512([&](u32 k) -> unsigned char { return k < 64 ? b0[k] : k == 64 ? 1 : dst.b[k - 65]; }, 65 + dl, b1);
     blake2b_512([&](u32 k) -> unsigned char { return k < 64 ? (unsigned char)(b0[k] ^ b1[k]) : k == 64 ? 2 : dst.b[k - 65]; }, 65 + dl, b2);
     const fe u0 = h2c_field_from_be64<F>(b1), u1 = h2c_field_from_be64<F>(b2);
-    fe x0, y0, x1, y1;
-    map_to_curve_simple_swu<F>(u0, x0, y0);
-    map_to_curve_simple_swu<F>(u1, x1, y1);
-    // Q0 + Q1 on the iso curve (affine chord / tangent; the sum is the identity when Q1 = -Q0)
-    fe ox = fe_zero(), oy = fe_zero();
-    bool inf = false;
-    fe lam;
-    if (fe_eq(x0, x1)) {
-        if (fe_eq(y0, y1) && !fe_is_zero(y0)) {
-            const fe xx = fe_sqr<F>(x0);
-            lam = fe_mulx<F>(fe_add<F>(fe_add<F>(fe_dbl<F>(xx), xx), h2c_iso_a<F>()), fe_inv<F>(fe_dbl<F>(y0)));
-        } else {
-            inf = true;
-        }
-    } else {
-        lam = fe_mulx<F>(fe_sub<F>(y1, y0), fe_inv<F>(fe_sub<F>(x1, x0)));
-    }
-    if (!inf) {
-        const fe x3 = fe_sub<F>(fe_sub<F>(fe_sqr<F>(lam), x0), x1);
-        const fe y3 = fe_sub<F>(fe_mulx<F>(lam, fe_sub<F>(x0, x3)), y0);
-        // iso_map (Velu, normalised): X = c^2 (x + t / d + u / d^2), Y = c^3 y (1 - t / d^2 - 2u / d^3), d = x - x0
-        const fe d = fe_sub<F>(x3, h2c_iso_x0<F>());
-        if (!fe_is_zero(d)) {                              // a kernel point maps to the identity
-            const fe di = fe_inv<F>(d), di2 = fe_sqr<F>(di), di3 = fe_mulx<F>(di2, di);
-            const fe X = fe_add<F>(x3, fe_add<F>(fe_mulx<F>(h2c_iso_t<F>(), di), fe_mulx<F>(h2c_iso_u<F>(), di2)));
-            const fe Y = fe_mulx<F>(y3, fe_sub<F>(fe_sub<F>(fe_one<F>(), fe_mulx<F>(h2c_iso_t<F>(), di2)), fe_mulx<F>(h2c_iso_u2<F>(), di3)));
-            ox = fe_mulx<F>(h2c_iso_c2<F>(), X);
-            oy = fe_mulx<F>(h2c_iso_c3<F>(), Y);
-        }
-    }
+    fe ox, oy;
+    h2c_map_pair<F>(u0, u1, ox, oy);               // swu(u0) + swu(u1) on the iso curve, then the isogeny (h2c_map.cuh)
     if (!out_mont) {
         ox = fe_from_mont<F>(ox);
         oy = fe_from_mont<F>(oy);

@@ -194,7 +194,10 @@ def test_polynomial_tags_through_the_device_transforms(keygen):
 
 def test_hash_to_curve_on_the_device():
     """h2_hash_to_curve == the restated pasta_curves map, both curves, several prefixes and message lengths (0 .. 64 bytes);
-    w of Params::new is the value the reference pins."""
+    w of Params::new is the value the reference pins.  These messages give BLAKE2b inputs away from a multiple of 128 bytes and
+    u0, u1 that take none of the map's rare branches: tests/test_gpu_h2c_edges.py covers the block boundaries
+    (test_blake2b_block_boundaries) and u = 0, the tangent and identity sums and the isogeny's kernel point
+    (test_swu_at_the_edges_of_u, test_pairs_through_tangent_identity_and_zero, test_add_and_isogeny_on_their_own)."""
     from oracle import hash_to_curve as oh
     for curve, cid in ((h.VESTA, "vesta"), (h.PALLAS, "pallas")):
         for prefix, msgs in (("Halo2-Parameters", [b"\x00" + i.to_bytes(4, "little") for i in (0, 1, 2, 31, 0xDEADBEEF)]),
