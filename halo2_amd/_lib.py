@@ -157,6 +157,10 @@ SIGNATURES = {
     "h2_ecc_fixed_tables_device": ([u64p, C.c_uint, C.c_uint64, vp, vp, vp, vp, vp], C.c_int),
     "h2_ecc_mul_fixed_device": ([vp, C.c_uint, vp, C.c_size_t, vp, vp], C.c_int),
     "h2_ecc_mul_fixed_trace_device": ([vp, vp, C.c_uint, vp, C.c_size_t, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_hash_from_device": ([vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_commit_device": ([vp, C.c_size_t, C.c_size_t, u64p, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_trace_from_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, vp, vp, vp, vp, vp], C.c_int),
+    "h2_ecc_add_trace_device": ([vp, vp, C.c_size_t, vp, vp], C.c_int),
 }
 
 

@@ -199,5 +199,6 @@ extern "C" int h2_trim(void) {
     h2::sinsemilla_release_workspaces();
     h2::ecc_release_workspaces();
     h2::ecc_fixed_release_workspaces();
+    h2::sinsemilla_commit_release_workspaces();
     return H2_OK;
 }

@@ -127,6 +127,7 @@ void mock_release_workspaces();
 void sinsemilla_release_workspaces();
 void ecc_release_workspaces();
 void ecc_fixed_release_workspaces();
+void sinsemilla_commit_release_workspaces();
 
 // The field-element sort of lookup.hip for other translation units (mock_prover.hip): `n` elements of d_src as canonical keys into
 // `keys`, padded to the next power of two with all-ones keys and sorted ascending; and the sort alone of 2^log_n keys already in place.

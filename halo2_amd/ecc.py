@@ -5,7 +5,10 @@ witness of the ECC chip's variable-base `mul` (halo2_gadgets ecc/chip/mul.rs) fo
 
 Points are arrays of uint64 Montgomery limbs, (..., 8), the identity (0, 0); scalars of `mul` are CANONICAL integers of 4 limbs below
 2^255; the alphas of `mul_trace` are Montgomery elements of Fp, as cells are.  A CUDA int64 tensor is used in place and a CUDA tensor
-comes back; a numpy array is uploaded and a numpy array comes back."""
+comes back; a numpy array is uploaded and a numpy array comes back.
+
+`add` and `add_trace` are the group's complete addition in bulk (halo2_amd/csrc/sinsemilla_commit.hip, ecc/chip/add.rs): n sums
+P_i + Q_i, and the nine cells the chip witnesses for each."""
 from __future__ import annotations
 
 import numpy as np
@@ -15,7 +18,8 @@ from ._lib import check, lib
 from .arithmetic import _is_torch, _stream_ptr, scale_add
 
 __all__ = ["ROWS", "AUX", "mul", "mul_trace", "OffCurve", "Vanishing",
-           "NUM_WINDOWS", "NUM_WINDOWS_SHORT", "FIXED_AUX", "FixedBase", "mul_fixed", "mul_fixed_short", "mul_fixed_trace"]
+           "NUM_WINDOWS", "NUM_WINDOWS_SHORT", "FIXED_AUX", "FixedBase", "mul_fixed", "mul_fixed_short", "mul_fixed_trace",
+           "add", "add_trace"]
 
 ROWS = 137                                      # rows of the region "variable-base scalar mul" (mul.rs:164-293)
 AUX = 16                                        # s, the 14 running sums of its range check, eta (mul/overflow.rs:101-208)
@@ -190,3 +194,25 @@ def mul_fixed_trace(fixed_base: FixedBase, scalars):
     if host:
         return columns.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
     return columns, aux
+
+
+def add_trace(p, q):
+    """What the chip's complete addition witnesses for n pairs (add.rs:213-295): p, q (n, 8) Montgomery affine, the identity (0, 0) ->
+    (n, FIXED_AUX, 4): x_p, y_p, x_qr, y_qr, lambda, alpha, beta, gamma, delta and the sum's x and y, the order of `mul_fixed_trace`'s
+    aux.  Every branch is the reference's: P + P, P + (-P) and the identity on either side."""
+    import torch
+    a, host = _device(p, 8, "ecc.add_trace p")
+    b, host_b = _device(q, 8, "ecc.add_trace q")
+    if a.shape[0] != b.shape[0] or host != host_b:
+        raise ValueError("ecc.add_trace: as many q as p, both of one kind")
+    n = a.shape[0]
+    aux = torch.empty((n, FIXED_AUX, 4), dtype=torch.int64, device=a.device)
+    check(lib().h2_ecc_add_trace_device(_ptr(a), _ptr(b), n, _ptr(aux), _stream_ptr()), "h2_ecc_add_trace_device")
+    return aux.cpu().numpy().view(np.uint64) if host else aux
+
+
+def add(p, q):
+    """P_i + Q_i, complete: (n, 8) and (n, 8) -> (n, 8)."""
+    aux = add_trace(p, q)
+    out = aux[:, 9:11].reshape(-1, 8)
+    return np.ascontiguousarray(out) if isinstance(out, np.ndarray) else out.contiguous()

@@ -23,7 +23,8 @@ tables as integers, from the device (`FixedBaseTables.of(halo2_amd.ecc.FixedBase
 `halo2_amd.ecc.mul_fixed_trace` and whose fixed columns are the base's tables tiled, then one region with the complete additions.
 
 The mirror of the reference's test circuit (`MyEccCircuit`, tests/ecc_fixed_cases.py) reproduces the reference's pinned `vk_ecc_chip`
-bit for bit and its stored proof verifies.  `CommitDomain` is not built."""
+bit for bit and its stored proof verifies.  `CommitDomain`, which multiplies its R through `FixedPoint` and adds through `add`, is in
+`halo2_amd/gadgets/sinsemilla.py`."""
 from __future__ import annotations
 
 import numpy as np

@@ -1,6 +1,7 @@
 """The Sinsemilla gadget of halo2_gadgets (src/sinsemilla.rs, sinsemilla/chip.rs, chip/hash_to_point.rs, chip/generator_table.rs,
 sinsemilla/merkle.rs, merkle/chip.rs) against `halo2_amd.circuit`: `SinsemillaChip`, `Message` / `MessagePiece`, `HashDomain`,
-`MerkleChip` and `MerklePath`, over the Pallas base field with public Q.
+`MerkleChip`, `MerklePath` and `CommitDomain`, over the Pallas base field, with Q public or -- on a chip configured with
+`allow_init_from_private_point` -- a witnessed point (`hash_to_point_with_private_init`).
 
 The mirror assigns cell by cell with host `Assigned` rationals -- the same regions, offsets, gate and lookup shapes and copy
 constraints as the reference, one message word per row:
@@ -10,14 +11,17 @@ constraints as the reference, one message word per row:
     point, zs = SinsemillaChip(config).hash_to_point(layouter, Q, [piece, ...])
 
 What the reference does not have is the bulk path: `SinsemillaChip.hash_to_point_many` lays `count` hashes of one piece structure
-back to back in ONE region whose five advice columns come from the device (`halo2_amd.sinsemilla.trace`), with the q_sinsemilla2
-pattern tiled; cell for cell the layout of `count` calls of `hash_to_point`.
+back to back in ONE region whose five advice columns come from the device (`halo2_amd.sinsemilla.trace`, or `trace_from` where a
+hash starts under a row of its own for y_Q), with the q_sinsemilla2 pattern tiled; cell for cell the layout of `count` calls of
+`hash_to_point`.  `CommitDomain.commit_many` puts `count` commitments M_i + [r_i]R into three bulk regions: the fixed-base products
+(`EccChip.mul_fixed_many`), the hashes, and the complete additions (`halo2_amd.ecc.add_trace`).
 
 The generator table is `halo2_amd.sinsemilla`'s, built on the device once per process; `table=` injects another (1024 (x, y) pairs)."""
 from __future__ import annotations
 
 import numpy as np
 
+from .. import ecc as ecc_primitive
 from .. import fields
 from .. import sinsemilla as primitive
 from ..circuit import Assigned, AssignedCell, Cell, Column, ConstraintSystem, Expression, Rotation, Synthesis
@@ -54,8 +58,8 @@ class DoubleAndAdd:
 
 class SinsemillaConfig:
     def __init__(self, modulus, q_sinsemilla1, q_sinsemilla2, q_sinsemilla4, fixed_y_q, double_and_add, bits, witness_pieces,
-                 generator_table, lookup_config, table, injected_table=None):
-        self.modulus = modulus
+                 generator_table, lookup_config, table, injected_table=None, allow_init_from_private_point=False):
+        self.modulus, self.allow_init_from_private_point = modulus, allow_init_from_private_point
         self.q_sinsemilla1, self.q_sinsemilla2, self.q_sinsemilla4, self.fixed_y_q = q_sinsemilla1, q_sinsemilla2, q_sinsemilla4, fixed_y_q
         self.double_and_add, self.bits, self.witness_pieces = double_and_add, bits, witness_pieces
         self.generator_table, self.lookup_config = generator_table, lookup_config
@@ -86,6 +90,14 @@ class MessagePiece:
         return chip.witness_message_piece(layouter, field_elem, num_words)
 
     @staticmethod
+    def from_bitstring(chip, layouter, bitstring) -> "MessagePiece":
+        """sinsemilla.rs MessagePiece::from_bitstring: a multiple of K bits (booleans, or None each without a witness), low bit first"""
+        bits = list(bitstring)
+        assert len(bits) % K == 0 and len(bits) // K <= PIECE_MAX_WORDS
+        elem = None if any(b is None for b in bits) else sum(int(bool(b)) << i for i, b in enumerate(bits))
+        return MessagePiece.from_field_elem(chip, layouter, elem, len(bits) // K)
+
+    @staticmethod
     def from_subpieces(chip, layouter, subpieces) -> "MessagePiece":
         """sinsemilla.rs:256-278: the subpieces (RangeConstrained integers) concatenated, low bits first; assigned, not constrained"""
         elem, total_bits = 0, 0
@@ -97,7 +109,24 @@ class MessagePiece:
         return MessagePiece.from_field_elem(chip, layouter, elem, total_bits // K)
 
 
-Message = list                                                                # sinsemilla/message.rs Message: the pieces in order
+class Message(list):
+    """sinsemilla.rs Message: the pieces in order (a list of MessagePiece, which is all the chip asks for)."""
+
+    @staticmethod
+    def from_pieces(chip, pieces) -> "Message":
+        return Message(pieces)
+
+    @staticmethod
+    def from_bitstring(chip, layouter, bitstring) -> "Message":
+        """a multiple of K bits, at most C words, cut into pieces of floor(CAPACITY / K) = 25 words, the last one shorter"""
+        bits = list(bitstring)
+        assert len(bits) % K == 0 and len(bits) // K <= C_MAX
+        step = PIECE_MAX_WORDS * K
+        return Message(MessagePiece.from_bitstring(chip, layouter, bits[at:at + step]) for at in range(0, len(bits), step))
+
+
+class IllegalHashFromPrivatePoint(ValueError):
+    """Error::IllegalHashFromPrivatePoint: the chip was configured without allow_init_from_private_point"""
 
 
 class NonIdentityEccPoint:
@@ -115,10 +144,11 @@ class HashMany:
     """What `hash_to_point_many` returns: the cells of hash i by position.  outputs: (count, 2, 4) Montgomery x and y of the hashes
     (None without a witness)."""
 
-    def __init__(self, region_index, config, count, num_words, outputs):
+    def __init__(self, region_index, config, count, num_words, outputs, first=0):
         self.region_index, self.config, self.count, self.num_words, self.outputs = region_index, config, count, list(num_words), outputs
-        self.rows = sum(num_words) + 1
-        self.piece_offsets = [sum(num_words[:k]) for k in range(len(num_words))]
+        self.first = first                                                    # 1 where every hash starts under a row for y_Q
+        self.rows = sum(num_words) + 1 + first
+        self.piece_offsets = [first + sum(num_words[:k]) for k in range(len(num_words))]
 
     def x_a(self, i: int) -> Cell:
         return Cell(self.region_index, self.rows * i + self.rows - 1, self.config.double_and_add.x_a)
@@ -143,8 +173,10 @@ class SinsemillaChip:
 
     @staticmethod
     def configure(meta: ConstraintSystem, advices, witness_pieces: Column, fixed_y_q: Column, lookup, range_check: LookupRangeCheckConfig,
-                  table=None) -> SinsemillaConfig:
-        """chip.rs:170-288 with allow_init_from_private_point = false.  All five advice columns become equality-enabled."""
+                  table=None, allow_init_from_private_point: bool = False) -> SinsemillaConfig:
+        """chip.rs:170-288.  All five advice columns become equality-enabled.  With allow_init_from_private_point the gate "Initial y_Q"
+        reads y_Q from x_p one row above instead of from fixed_y_q: the chip can hash from a witnessed point, and a hash from a public
+        Q takes one row more."""
         advices = list(advices)
         assert len(advices) == 5
         for advice in advices:
@@ -155,7 +187,7 @@ class SinsemillaChip:
             meta.modulus, q_sinsemilla1=meta.complex_selector(), q_sinsemilla2=meta.fixed_column(), q_sinsemilla4=meta.selector(),
             fixed_y_q=fixed_y_q, double_and_add=DoubleAndAdd(advices[0], advices[1], advices[3], advices[4]), bits=advices[2],
             witness_pieces=witness_pieces, generator_table=GeneratorTableConfig(*lookup), lookup_config=range_check, table=table,
-            injected_table=injected)
+            injected_table=injected, allow_init_from_private_point=allow_init_from_private_point)
         dna = config.double_and_add
 
         def generator_lookup(cells):                                          # generator_table.rs:46-82
@@ -181,7 +213,7 @@ class SinsemillaChip:
 
         def initial_y_q(cells):
             q_s4 = cells.query_selector(config.q_sinsemilla4)
-            y_q = cells.query_fixed(config.fixed_y_q)
+            y_q = cells.query_advice(dna.x_p, Rotation.prev()) if allow_init_from_private_point else cells.query_fixed(config.fixed_y_q)
             y_a_cur = dna.Y_A(cells, Rotation.cur())
             return [("init_y_q_check", q_s4 * (y_q * 2 - y_a_cur))]           # 2 y_Q - Y_{A,0} = 0
         meta.create_gate("Initial y_Q", initial_y_q)
@@ -215,20 +247,46 @@ class SinsemillaChip:
         assert sum(p.num_words for p in message) <= C_MAX
         return layouter.assign_region("hash_to_point", lambda region: self._hash_message(region, Q, message))
 
+    def hash_to_point_with_private_init(self, layouter, Q: NonIdentityEccPoint, message):      # noqa: N803
+        """the hash from a witnessed Q, whose two cells are copied in (chip.rs, hash_to_point.rs:68-105)"""
+        assert sum(p.num_words for p in message) <= C_MAX
+        if not self.config.allow_init_from_private_point:
+            raise IllegalHashFromPrivatePoint("hash_to_point_with_private_init: the chip was configured without allow_init_from_private_point")
+        return layouter.assign_region("hash_to_point", lambda region: self._hash_message(region, Q, message, private=True))
+
     @staticmethod
     def extract(point: NonIdentityEccPoint) -> AssignedCell:
         return point.x()
 
     # ---- hash_to_point.rs ------------------------------------------------------------------------------------------------------------------
-    def _hash_message(self, region, Q, message):                              # noqa: N803
+    def _public_q_initialization(self, region, Q):                            # noqa: N803 -- hash_to_point.rs:107-166
         c, m = self.config, self.config.modulus
         x_q, y_q = int(Q[0]) % m, int(Q[1]) % m
-        # public Q: q_sinsemilla4 and y_Q (fixed) on the first row, x_Q constrained to the constant
-        c.q_sinsemilla4.enable(region, 0)
-        region.assign_fixed(c.fixed_y_q, 0, lambda: y_q)
-        x_a = region.assign_advice_from_constant(c.double_and_add.x_a, 0, x_q)
+        offset = 0
+        if c.allow_init_from_private_point:                                   # y_Q in x_p on a row of its own, q_sinsemilla4 on the second
+            c.q_sinsemilla4.enable(region, 1)
+            region.assign_advice_from_constant(c.double_and_add.x_p, 0, y_q)
+            offset = 1
+        else:                                                                 # q_sinsemilla4 and y_Q (fixed) on the first row
+            c.q_sinsemilla4.enable(region, 0)
+            region.assign_fixed(c.fixed_y_q, 0, lambda: y_q)
+        x_a = region.assign_advice_from_constant(c.double_and_add.x_a, offset, x_q)
         y_a = Assigned.trivial(y_q, m) if region.layouter and region.layouter.cs.collect_advice else None
-        offset, zs_sum = 0, []
+        return offset, x_a, y_a
+
+    def _private_q_initialization(self, region, Q: NonIdentityEccPoint):      # noqa: N803 -- hash_to_point.rs:168-213
+        c = self.config
+        if not c.allow_init_from_private_point:
+            raise IllegalHashFromPrivatePoint("the chip was configured without allow_init_from_private_point")
+        c.q_sinsemilla4.enable(region, 1)
+        y_cell = Q.y().copy_advice(region, c.double_and_add.x_p, 0)
+        x_a = Q.x().copy_advice(region, c.double_and_add.x_a, 1)
+        return 1, x_a, y_cell.value().inner
+
+    def _hash_message(self, region, Q, message, private=False):               # noqa: N803
+        c = self.config
+        offset, x_a, y_a = self._private_q_initialization(region, Q) if private else self._public_q_initialization(region, Q)
+        zs_sum = []
         for idx, piece in enumerate(message):
             x_a, y_a, zs = self._hash_piece(region, offset, piece, x_a, y_a, idx == len(message) - 1)
             offset += piece.num_words
@@ -282,19 +340,27 @@ class SinsemillaChip:
 
     # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
     def hash_to_point_many(self, layouter, Q, num_words, pieces, values=None, trace=None) -> HashMany:      # noqa: N803
-        """`count` hashes of one piece structure back to back in one region of (sum(num_words) + 1) * count rows; cell for cell what
-        `count` calls of `hash_to_point` lay out.
+        """`count` hashes of one piece structure back to back in one region; cell for cell what `count` calls of `hash_to_point` (or of
+        `hash_to_point_with_private_init`) lay out.  Q: an (x, y) pair, public and shared, or a list of `count` NonIdentityEccPoint,
+        one witnessed Q per hash, on a chip configured with allow_init_from_private_point.  Each hash takes sum(num_words) + 1 rows,
+        and one more in front, for y_Q, on such a chip.
 
         pieces: pieces[i][k] is the MessagePiece k of hash i (their cells are copied into z_0).  values: the (count, n_pieces, 4)
         CANONICAL limbs of the pieces where the caller has them on the device already (else they are read from the cells); trace:
-        the (5, rows * count, 4) columns where the caller has them (else `sinsemilla.trace`, once).  Without a witness (keygen) the
-        same shape is laid out and nothing is launched."""
+        the (5, rows * count, 4) columns where the caller has them (else `sinsemilla.trace` or `trace_from`, once).  Without a witness
+        (keygen) the same shape is laid out and nothing is launched."""
         import torch
         c, m = self.config, self.config.modulus
         num_words = [int(w) for w in num_words]
-        count, n_pieces, rows = len(pieces), len(num_words), sum(num_words) + 1
+        private = not (len(Q) == 2 and not any(hasattr(q, "x") for q in Q))     # cells, not the two coordinates of a public point
+        if private and not c.allow_init_from_private_point:
+            raise IllegalHashFromPrivatePoint("hash_to_point_many: the chip was configured without allow_init_from_private_point")
+        first = 1 if c.allow_init_from_private_point else 0
+        count, n_pieces, rows = len(pieces), len(num_words), sum(num_words) + 1 + first
         if any(len(p) != n_pieces or any(q.num_words != w for q, w in zip(p, num_words)) for p in pieces):
             raise ValueError("hash_to_point_many: every hash has the pieces of the one structure")
+        if private and len(Q) != count:
+            raise ValueError("hash_to_point_many: one Q per hash")
         backend = layouter.cs
         total = rows * count
         if not backend.collect_advice:
@@ -307,7 +373,16 @@ class SinsemillaChip:
                 values = fields.to_limbs(ints, FP, montgomery=False).reshape(count, n_pieces, 4)
             if not torch.is_tensor(values):
                 values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint64).view(np.int64)).to(fields.current_device())
-            trace = primitive.trace(values, num_words, Q, table=c.injected_table)
+            if private:
+                coords = [value_int(cell.value(), m) for q in Q for cell in (q.x(), q.y())]
+                if any(v is None for v in coords):
+                    raise Synthesis("hash_to_point_many: a witness is needed and there is none")
+                start = torch.from_numpy(fields.to_limbs(coords, FP).reshape(count, 8).view(np.int64)).to(values.device)
+                trace = primitive.trace_from(values, num_words, start, table=c.injected_table)
+            elif first:
+                trace = primitive.trace_from(values, num_words, (int(Q[0]) % m, int(Q[1]) % m), table=c.injected_table)
+            else:
+                trace = primitive.trace(values, num_words, Q, table=c.injected_table)
         if trace is not None:
             if not torch.is_tensor(trace):
                 trace = torch.from_numpy(np.ascontiguousarray(trace, dtype=np.uint64).view(np.int64))
@@ -315,34 +390,43 @@ class SinsemillaChip:
                 raise ValueError("hash_to_point_many: the trace is (5, rows * count, 4)")
         blank = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (total, 4))
         advice = [blank] * 5 if trace is None else [trace[j] for j in range(5)]
-        # q_sinsemilla2 of one hash: 1 on the rows of a piece but its last, 0 there, 2 on the last word row; nothing on the final row
-        # (a fixed cell nobody assigns is zero, so the tiled pattern carries a zero there)
-        pattern = []
+        # q_sinsemilla2 of one hash: 1 on the rows of a piece but its last, 0 there, 2 on the last word row; nothing on the row of y_Q
+        # nor on the final row (a fixed cell nobody assigns is zero, so the tiled pattern carries a zero there)
+        pattern = [0] * first
         for k, w in enumerate(num_words):
             pattern += [1] * (w - 1) + [2 if k == n_pieces - 1 else 0]
         q_s2 = blank
         if backend.collect_fixed and count:
             q_s2 = np.tile(fields.to_limbs(pattern + [0], FP), (count, 1))
         base = rows * np.arange(count, dtype=np.int64)
-        word_rows = (base[:, None] + np.arange(rows - 1, dtype=np.int64)[None, :]).reshape(-1)
-        x_q, y_q = int(Q[0]) % m, int(Q[1]) % m
+        word_rows = (base[:, None] + np.arange(first, rows - 1, dtype=np.int64)[None, :]).reshape(-1)
         dna = c.double_and_add
-        result = HashMany(None, c, count, num_words, None)
+        result = HashMany(None, c, count, num_words, None, first)
 
         def assign(region):
+            index = region.region_index
             for column, values_ in zip((dna.x_a, dna.x_p, c.bits, dna.lambda_1, dna.lambda_2), advice):
                 region.assign_advice_column(column, 0, values_)
             region.enable_selector_rows(c.q_sinsemilla1, word_rows)
-            region.enable_selector_rows(c.q_sinsemilla4, base)
+            region.enable_selector_rows(c.q_sinsemilla4, base + first)
             region.assign_fixed_column(c.q_sinsemilla2, 0, q_s2)
             for i in range(count):
-                region.assign_fixed(c.fixed_y_q, rows * i, lambda: y_q)
-                region.constrain_constant(Cell(region.region_index, rows * i, dna.x_a), x_q)
                 at = rows * i
+                if private:
+                    region.constrain_equal(Cell(index, at, dna.x_p), Q[i].y().cell())
+                    region.constrain_equal(Cell(index, at + 1, dna.x_a), Q[i].x().cell())
+                else:
+                    x_q, y_q = int(Q[0]) % m, int(Q[1]) % m
+                    if first:
+                        region.constrain_constant(Cell(index, at, dna.x_p), y_q)
+                    else:
+                        region.assign_fixed(c.fixed_y_q, at, lambda: y_q)
+                    region.constrain_constant(Cell(index, at + first, dna.x_a), x_q)
+                at += first
                 for k, w in enumerate(num_words):
-                    region.constrain_equal(Cell(region.region_index, at, c.bits), pieces[i][k].cell_value.cell())
+                    region.constrain_equal(Cell(index, at, c.bits), pieces[i][k].cell_value.cell())
                     at += w
-            return region.region_index
+            return index
         result.region_index = layouter.assign_region("hash_to_point many", assign)
         if trace is not None and count:
             last = torch.from_numpy(base + rows - 1).to(trace.device)
@@ -359,9 +443,127 @@ class HashDomain:
     def hash_to_point(self, layouter, message):
         return self.chip.hash_to_point(layouter, self.Q, message)
 
+    def hash_to_point_with_private_init(self, layouter, Q: NonIdentityEccPoint, message):      # noqa: N803 -- sinsemilla.rs:344-360
+        return self.chip.hash_to_point_with_private_init(layouter, Q, message)
+
     def hash(self, layouter, message):                                        # noqa: A003
         point, zs = self.hash_to_point(layouter, message)
         return self.chip.extract(point), zs
+
+
+# ---- CommitDomain (sinsemilla.rs:395-520) -----------------------------------------------------------------------------------------------------
+class CommitDomains:
+    """What a CommitDomain reads of its domain (sinsemilla.rs CommitDomains): the hash's public Q as (x, y) integers and R's tables, an
+    `ecc.FixedBaseTables` of 85 windows."""
+
+    def __init__(self, Q, R):                                                 # noqa: N803
+        self.Q, self.R = (int(Q[0]), int(Q[1])), R
+
+    @staticmethod
+    def of(domain: "primitive.CommitDomain") -> "CommitDomains":
+        """from `halo2_amd.sinsemilla.CommitDomain`, whose tables of R are built on the device"""
+        from .ecc import FixedBaseTables
+        return CommitDomains(domain.M.Q, FixedBaseTables.of(domain.fixed_base))
+
+
+class CommitMany:
+    """What `commit_many` returns: the cells of commitment i by position, the bulk hashes (`hashes.z(i, piece, j)` are the running sums)
+    and the bulk blinding products.  outputs: (count, 2, 4) Montgomery x and y of the commitments (None without a witness)."""
+
+    def __init__(self, add_config, blinds, hashes):
+        self.add_config, self.blinds, self.hashes, self.add_region_index, self.outputs = add_config, blinds, hashes, None, None
+
+    def result_x(self, i: int) -> Cell:
+        return Cell(self.add_region_index, 2 * i + 1, self.add_config.x_qr)
+
+    def result_y(self, i: int) -> Cell:
+        return Cell(self.add_region_index, 2 * i + 1, self.add_config.y_qr)
+
+
+class CommitDomain:
+    """SinsemillaCommit and SinsemillaShortCommit over a SinsemillaChip and an EccChip: M + [r]R, the regions in the reference's
+    order -- "[r] R", then "M", then "M + [r] R"."""
+
+    def __init__(self, sinsemilla_chip, ecc_chip, domain: CommitDomains):
+        from .ecc import FixedPoint
+        self.M = HashDomain(sinsemilla_chip, domain.Q)
+        self.R = FixedPoint.from_inner(ecc_chip, domain.R)
+        self.ecc_chip, self._tables = ecc_chip, domain.R
+
+    def _point(self, inner):
+        from .ecc import NonIdentityPoint
+        return NonIdentityPoint(self.ecc_chip, inner)
+
+    def hash_with_private_init(self, layouter, Q, message):                   # noqa: N803
+        """Q: an ecc NonIdentityPoint (or the chip's NonIdentityEccPoint).  -> (NonIdentityPoint, running sums)"""
+        point, zs = self.M.hash_to_point_with_private_init(layouter, Q.inner() if hasattr(Q, "inner") else Q, message)
+        return self._point(point), zs
+
+    def q_init(self) -> tuple:
+        return self.M.Q
+
+    def blinding_factor(self, layouter, r):
+        """[r]R for a ScalarFixed r -> Point"""
+        blind, _ = self.R.mul(layouter, r)
+        return blind
+
+    def commit(self, layouter, message, r):
+        """-> (Point, running sums)"""
+        blind, _ = self.R.mul(layouter, r)
+        p, zs = self.M.hash_to_point(layouter, message)
+        return self._point(p).add(layouter, blind), zs
+
+    def short_commit(self, layouter, message, r):
+        """-> (the x cell, running sums)"""
+        p, zs = self.commit(layouter, message, r)
+        return p.extract_p(), zs
+
+    def commit_many(self, layouter, pieces, num_words, scalars, values=None, trace=None) -> CommitMany:
+        """`count` commitments M_i + [r_i]R in three bulk regions, in the order of `commit`: one `mul_fixed_many` (with its region of
+        closing additions), one `hash_to_point_many`, and one region of `count` complete additions, two rows each as the bulk
+        additions of `mul_fixed_many`, filled from `ecc.add_trace` and copy-constrained to the outputs of the other two.
+
+        pieces, num_words: as `hash_to_point_many`; scalars: integers below 2^255 (None each without a witness).  values: (the pieces'
+        limbs, the scalars' limbs) as the two bulk calls take them, either may be None; trace: (the `mul_fixed_trace` pair, the hash's
+        columns, the additions' (count, 11, 4) rows), each None where the caller has none."""
+        import torch
+        piece_values, scalar_values = values if values is not None else (None, None)
+        fixed_trace, hash_trace, add_trace = trace if trace is not None else (None, None, None)
+        count = len(pieces)
+        if len(scalars) != count:
+            raise ValueError("commit_many: one scalar per message")
+        blinds = self.ecc_chip.mul_fixed_many(layouter, self._tables, scalars, values=scalar_values, trace=fixed_trace)
+        hashes = self.M.chip.hash_to_point_many(layouter, self.M.Q, num_words, pieces, values=piece_values, trace=hash_trace)
+        add = self.ecc_chip.config.add
+        result = CommitMany(add, blinds, hashes)
+        aux = None
+        if layouter.cs.collect_advice and count:
+            if add_trace is None:
+                add_trace = ecc_primitive.add_trace(hashes.outputs.reshape(count, 8), blinds.outputs.reshape(count, 8))
+            aux = add_trace if torch.is_tensor(add_trace) else torch.from_numpy(np.ascontiguousarray(add_trace, dtype=np.uint64).view(np.int64))
+            if tuple(aux.shape) != (count, ecc_primitive.FIXED_AUX, 4):
+                raise ValueError("commit_many: the additions' trace is (count, 11, 4)")
+
+        def additions(region):
+            index = region.region_index
+            for j, column in enumerate((add.x_p, add.y_p, add.x_qr, add.y_qr, add.lambda_, add.alpha, add.beta, add.gamma, add.delta)):
+                if aux is None:
+                    values_ = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (2 * count, 4))
+                else:
+                    second = aux[:, 9 + (j - 2)] if j in (2, 3) else torch.zeros_like(aux[:, j])
+                    values_ = torch.stack([aux[:, j], second], dim=1).reshape(2 * count, 4)
+                region.assign_advice_column(column, 0, values_)
+            region.enable_selector_rows(add.q_add, 2 * np.arange(count, dtype=np.int64))
+            for i in range(count):                                            # p = M_i, q = [r_i]R
+                region.constrain_equal(Cell(index, 2 * i, add.x_p), hashes.x_a(i))
+                region.constrain_equal(Cell(index, 2 * i, add.y_p), hashes.y_a(i))
+                region.constrain_equal(Cell(index, 2 * i, add.x_qr), blinds.result_x(i))
+                region.constrain_equal(Cell(index, 2 * i, add.y_qr), blinds.result_y(i))
+            return index
+        result.add_region_index = layouter.assign_region("M + [r] R many", additions)
+        if aux is not None:
+            result.outputs = aux[:, 9:11].contiguous()
+        return result
 
 
 # ---- MerkleChip, MerklePath (merkle/chip.rs, merkle.rs) ------------------------------------------------------------------------------------

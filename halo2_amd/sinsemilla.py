@@ -6,7 +6,11 @@ witness of the Sinsemilla chip.  Zcash protocol specification 5.4.1.9: K = 10, C
 
 Field elements and points are arrays of uint64 Montgomery limbs ((..., 4) and (..., 8)): a CUDA int64 tensor is used in place and a
 CUDA tensor comes back; a numpy array is uploaded and a numpy array comes back.  The 1024-point table S is built once per process and
-device by h2_hash_to_curve_device and stays in HBM (64 KiB)."""
+device by h2_hash_to_curve_device and stays in HBM (64 KiB).
+
+`CommitDomain` is the `sinsemilla` crate's: SinsemillaCommit and SinsemillaShortCommit (specification 5.4.8.4), hash and blinding
+product in one launch (halo2_amd/csrc/sinsemilla_commit.hip).  `HashDomain.hash_to_point(.., Q=)` and `trace_from` start every message
+from a point of its own: the reference's hash_to_point_with_private_init."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +22,7 @@ from ._lib import FORM_MONTGOMERY, check, lib
 from .arithmetic import _is_torch, _p, _stream_ptr
 
 __all__ = ["K", "C_MAX", "HashDomain", "generator_table", "generator_table_ints", "q_point", "merkle_crh", "merkle_root", "trace",
-           "Bottom", "MERKLE_CRH_DOMAIN"]
+           "trace_from", "CommitDomain", "Bottom", "MERKLE_CRH_DOMAIN"]
 
 K = 10
 C_MAX = 253                                     # the specification's C: words per message
@@ -104,6 +108,39 @@ def _raise_bottom(status, what):
         raise Bottom(f"{what}: message {int(bad[0])} meets an exceptional addition ({bad.numel()} of {status.numel()} do)")
 
 
+def _device_words(words, what):
+    """-> ((n, len) int16 CUDA tensor, whether `words` came from the host)"""
+    import torch
+    host = not _is_torch(words)
+    if host:
+        w = np.asarray(words)
+        if w.ndim != 2 or (w.size and (w.min() < 0 or w.max() >= 1 << K)):
+            raise ValueError(f"{what}: an (n, len) array of 10-bit words")
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint16).view(np.int16)).to(fields.current_device())
+    else:
+        w = words.contiguous()
+        if w.dtype != torch.int16 or w.ndim != 2 or not w.is_cuda:
+            raise ValueError(f"{what}: an (n, len) CUDA int16 tensor of 10-bit words")
+    if w.shape[1] > C_MAX:
+        raise ValueError(f"{what}: a message has at most 253 words")
+    return w, host
+
+
+def _device_limbs(a, n, width, host, what):
+    """-> (n, width) int64 CUDA tensor from an array of the kind of the call's first argument"""
+    import torch
+    if host == _is_torch(a):
+        raise ValueError(f"{what}: every argument of one kind, numpy arrays or CUDA tensors")
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else a.contiguous()
+    if t.shape != (n, width) or t.dtype != torch.int64 or not t.is_cuda:
+        raise ValueError(f"{what}: an ({n}, {width}) array of uint64 limbs")
+    return t
+
+
+def _device_points(q, n, host, what):
+    return _device_limbs(q, n, 8, host, what + " Q")
+
+
 class HashDomain:
     """`HashDomain::new(name)` (halo2_gadgets/src/sinsemilla.rs), or a domain with a caller's Q: `HashDomain((x, y))`.
     `table=` replaces the generator table (host tests inject one computed on the CPU)."""
@@ -112,28 +149,23 @@ class HashDomain:
         self.Q = q_point(name_or_q) if isinstance(name_or_q, (str, bytes)) else (int(name_or_q[0]), int(name_or_q[1]))
         self.table = table
 
-    def hash_to_point(self, words, with_status: bool = False):
+    def hash_to_point(self, words, with_status: bool = False, Q=None):
         """n messages of `len` words (< 1024): an (n, len) integer array or CUDA int16 tensor -> (n, 8) affine points.  A message without
-        a value raises `Bottom`; with_status: returns (points, status) instead -- status[i] = 1 and a zero point for such a message."""
+        a value raises `Bottom`; with_status: returns (points, status) instead -- status[i] = 1 and a zero point for such a message.
+        Q: (n, 8) Montgomery affine points, of the kind of `words`: message i starts from Q[i] instead of the domain's Q."""
         import torch
-        host = not _is_torch(words)
-        if host:
-            w = np.asarray(words)
-            if w.ndim != 2 or (w.size and (w.min() < 0 or w.max() >= 1 << K)):
-                raise ValueError("sinsemilla.hash_to_point: an (n, len) array of 10-bit words")
-            w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint16).view(np.int16)).to(fields.current_device())
-        else:
-            w = words.contiguous()
-            if w.dtype != torch.int16 or w.ndim != 2 or not w.is_cuda:
-                raise ValueError("sinsemilla.hash_to_point: an (n, len) CUDA int16 tensor of 10-bit words")
+        w, host = _device_words(words, "sinsemilla.hash_to_point")
         n, length = w.shape
-        if length > C_MAX:
-            raise ValueError("sinsemilla.hash_to_point: a message has at most 253 words")
         tab = _device_table(self.table)
         out = torch.empty((n, 8), dtype=torch.int64, device=w.device)
         status = torch.empty((n,), dtype=torch.uint8, device=w.device)
-        check(lib().h2_sinsemilla_hash_device(_ptr(w), n, length, _p(_q_limbs(self.Q)), tab.data_ptr(), _ptr(out), _ptr(status), _stream_ptr()),
-              "h2_sinsemilla_hash_device")
+        if Q is None:
+            check(lib().h2_sinsemilla_hash_device(_ptr(w), n, length, _p(_q_limbs(self.Q)), tab.data_ptr(), _ptr(out), _ptr(status),
+                                                  _stream_ptr()), "h2_sinsemilla_hash_device")
+        else:
+            q = _device_points(Q, n, host, "sinsemilla.hash_to_point")
+            check(lib().h2_sinsemilla_hash_from_device(_ptr(w), n, length, _ptr(q), tab.data_ptr(), _ptr(out), _ptr(status), _stream_ptr()),
+                  "h2_sinsemilla_hash_from_device")
         if with_status:
             return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
         _raise_bottom(status, "sinsemilla.hash_to_point")
@@ -223,3 +255,81 @@ def trace(pieces, num_words, Q, table=None, with_status: bool = False):
         return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
     _raise_bottom(status, "sinsemilla.trace")
     return out.cpu().numpy().view(np.uint64) if host else out
+
+
+def trace_from(pieces, num_words, Q, table=None, with_status: bool = False):
+    """`trace` for messages that start from a cell: what hash_message_with_private_init witnesses, and a hash from a public Q on a chip
+    configured with allow_init_from_private_point (hash_to_point.rs:117-121, :179-182).  Q: (count, 8) Montgomery affine points of the
+    kind of `pieces`, or one (x, y) pair of integers for all.  -> (5, rows * count, 4) with rows = sum(num_words) + 2: row 0 of a
+    message holds y_Q in x_p and zeros elsewhere, the rest are the rows of `trace` from that Q."""
+    import torch
+    num_words = [int(w) for w in num_words]
+    host = not _is_torch(pieces)
+    p = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else pieces.contiguous()
+    if p.ndim != 3 or p.shape[1] != len(num_words) or p.shape[2] != 4 or p.dtype != torch.int64:
+        raise ValueError("sinsemilla.trace_from: pieces is a (count, n_pieces, 4) array of canonical limbs")
+    if not num_words or any(not 1 <= w <= 25 for w in num_words) or sum(num_words) > C_MAX:
+        raise ValueError("sinsemilla.trace_from: 1 .. 25 words per piece, 253 per message")
+    count, rows = p.shape[0], sum(num_words) + 2
+    if isinstance(Q, (tuple, list)) and len(Q) == 2 and all(isinstance(c, int) for c in Q):
+        q = torch.from_numpy(_q_limbs(Q).view(np.int64)).to(p.device).repeat(count, 1)
+    else:
+        q = _device_points(Q, count, host, "sinsemilla.trace_from")
+    tab = _device_table(table)
+    out = torch.empty((5, rows * count, 4), dtype=torch.int64, device=p.device)
+    status = torch.empty((count,), dtype=torch.uint8, device=p.device)
+    nw = (C.c_uint32 * len(num_words))(*num_words)
+    check(lib().h2_sinsemilla_trace_from_device(_ptr(p), count, nw, len(num_words), _ptr(q), tab.data_ptr(), _ptr(out), _ptr(status),
+                                                _stream_ptr()), "h2_sinsemilla_trace_from_device")
+    if with_status:
+        return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
+    _raise_bottom(status, "sinsemilla.trace_from")
+    return out.cpu().numpy().view(np.uint64) if host else out
+
+
+class CommitDomain:
+    """`CommitDomain::new(name)` (the `sinsemilla` crate): M = HashDomain(name + "-M") and R = hash_to_curve(name + "-r")(""), the
+    personalisation being the domain string itself.  `fixed_base` is R's `ecc.FixedBase` of 85 windows, built on first use; it is
+    what the gadget's `FixedBaseTables.of` takes."""
+
+    def __init__(self, name, table=None):
+        from .commitment import hash_to_curve
+        name = name.decode() if isinstance(name, bytes) else str(name)
+        self.M = HashDomain(name + "-M", table=table)
+        self._r_limbs = hash_to_curve(PALLAS, name + "-r", [b""])[0]
+        self.R = _points_to_ints(self._r_limbs)[0]
+        self._fixed_base = None
+
+    @property
+    def fixed_base(self):
+        if self._fixed_base is None:
+            from . import ecc
+            self._fixed_base = ecc.FixedBase(self._r_limbs, ecc.NUM_WINDOWS)
+        return self._fixed_base
+
+    def commit(self, words, r, with_status: bool = False, Q=None):
+        """SinsemillaHashToPoint(Q, words_i) + [r_i]R for n messages: words as `HashDomain.hash_to_point`, r (n, 4) CANONICAL limbs read
+        as `ecc.mul_fixed` reads them, Q as `hash_to_point` -> (n, 8).  The sum is the group's, so it may be the identity, (0, 0); only
+        a HASH without a value raises `Bottom`, or is flagged in the returned status with with_status."""
+        import torch
+        w, host = _device_words(words, "sinsemilla.commit")
+        n, length = w.shape
+        k = _device_limbs(r, n, 4, host, "sinsemilla.commit r")
+        q = None if Q is None else _device_points(Q, n, host, "sinsemilla.commit")
+        tab = _device_table(self.M.table)
+        out = torch.empty((n, 8), dtype=torch.int64, device=w.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=w.device)
+        check(lib().h2_sinsemilla_commit_device(_ptr(w), n, length, _p(_q_limbs(self.M.Q)) if q is None else None,
+                                                None if q is None else q.data_ptr(), tab.data_ptr(), self.fixed_base.points.data_ptr(),
+                                                _ptr(k), _ptr(out), _ptr(status), _stream_ptr()), "h2_sinsemilla_commit_device")
+        if with_status:
+            return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
+        _raise_bottom(status, "sinsemilla.commit")
+        return out.cpu().numpy().view(np.uint64) if host else out
+
+    def short_commit(self, words, r, with_status: bool = False, Q=None):
+        """The x coordinates of `commit`, 0 for the identity (extract_p): -> (n, 4)."""
+        res = self.commit(words, r, with_status, Q)
+        pts = res[0] if with_status else res
+        xs = np.ascontiguousarray(pts[:, :4]) if isinstance(pts, np.ndarray) else pts[:, :4].contiguous()
+        return (xs, res[1]) if with_status else xs

@@ -686,6 +686,40 @@ int h2_ecc_mul_fixed_device(const void *d_points, unsigned num_windows, const vo
 int h2_ecc_mul_fixed_trace_device(const void *d_points, const void *d_u, unsigned num_windows, const void *d_scalars, size_t count,
                                   void *d_columns, void *d_aux, void *stream);
 
+/* ---- Sinsemilla commitments and hashing from a private point (halo2_gadgets src/sinsemilla.rs CommitDomain; specification 5.4.8.4) ---- */
+/* The conventions are those of the Sinsemilla and fixed-base entries above: Montgomery affine points of 8 limbs, the identity (0, 0),
+ * one lane per message.  n or count above 2^30, words > 253 and a null pointer with n > 0 are H2_ERR_ARGS.
+ *
+ * h2_sinsemilla_hash_from_device: h2_sinsemilla_hash_device with the initial point of message i read from d_q_xy[i] (device memory, n
+ * points): the reference's hash_to_point_with_private_init.  d_status[i] = 1 and a zero point where the chain meets an exceptional
+ * addition or Q_i is the identity.
+ *
+ * h2_sinsemilla_commit_device: d_out_xy[i] = SinsemillaHashToPoint(Q, M_i) + [r_i]R in one launch.  Exactly one of q_xy (HOST memory, one Q
+ * shared by all messages) and d_q_xy (device memory, one Q per message) is non-null; anything else is H2_ERR_ARGS.  d_r_points is the
+ * 85 * 8 window table of R as h2_ecc_fixed_tables_device writes it; d_scalars holds n CANONICAL integers of 4 limbs read as
+ * h2_ecc_mul_fixed_device reads them (255 bits, not reduced).  The final addition is the group's: M = [r]R gives the double,
+ * M = -[r]R gives (0, 0) with status 0, r = 0 gives M.  d_status[i] = 1 and a zero point mean only that the HASH is bottom.
+ *
+ * h2_sinsemilla_trace_from_device: the witness of hash_message_with_private_init, and of a hash from a public Q on a chip configured
+ * with allow_init_from_private_point (sinsemilla/chip/hash_to_point.rs:117-121, :179-182), for `count` messages of one piece
+ * structure (d_pieces, num_words, n_pieces as h2_sinsemilla_trace_device) from the points d_q_xy[i] (device memory).  Each message
+ * takes rows = sum(num_words) + 2 rows of the five columns x_a, x_p, bits, lambda_1, lambda_2: row 0 holds y_Q in x_p and zeros in
+ * the other four (the reference assigns nothing there), rows 1 .. are the rows h2_sinsemilla_trace_device writes from Q_i.  Every
+ * element is written.  Scratch (32 bytes per row but the first, at most 2^20 / rows messages at a time) belongs to the (device,
+ * stream) context and goes back with h2_trim.
+ *
+ * h2_ecc_add_trace_device: n complete additions P_i + Q_i (ecc/chip/add.rs), each with its witness row.  d_aux holds 11 Montgomery
+ * elements per addition in the order of h2_ecc_mul_fixed_trace_device's d_aux: x_p, y_p, x_qr, y_qr, lambda, alpha, beta, gamma,
+ * delta, then the sum's x and y; the inverses are inv0 (zero for zero).  Every branch is covered: P + P, P + (-P), either operand or
+ * both the identity.  d_aux must not overlap the inputs. */
+int h2_sinsemilla_hash_from_device(const void *d_words, size_t n, size_t words, const void *d_q_xy, const void *d_table, void *d_out_xy,
+                                   void *d_status, void *stream);
+int h2_sinsemilla_commit_device(const void *d_words, size_t n, size_t words, const uint64_t *q_xy, const void *d_q_xy, const void *d_table,
+                                const void *d_r_points, const void *d_scalars, void *d_out_xy, void *d_status, void *stream);
+int h2_sinsemilla_trace_from_device(const void *d_pieces, size_t count, const uint32_t *num_words, size_t n_pieces, const void *d_q_xy,
+                                    const void *d_table, void *d_columns, void *d_status, void *stream);
+int h2_ecc_add_trace_device(const void *d_p_xy, const void *d_q_xy, size_t n, void *d_aux, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
