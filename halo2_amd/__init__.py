@@ -11,6 +11,7 @@ from .domain import EvaluationDomain  # noqa: F401
 from . import poseidon  # noqa: F401
 from . import sinsemilla  # noqa: F401
 from . import ecc  # noqa: F401
+from . import range_check  # noqa: F401
 from .poly import Coeff, ExtendedLagrangeCoeff, LagrangeCoeff, Polynomial  # noqa: F401
 from .circuit import (Assigned, Circuit, Column, ConstraintSystem, Expression, Rotation, Selector, SimpleFloorPlanner, TableColumn,  # noqa: F401
                       Value, create_proof, keygen_pk, keygen_vk, lower)

@@ -161,6 +161,8 @@ SIGNATURES = {
     "h2_sinsemilla_commit_device": ([vp, C.c_size_t, C.c_size_t, u64p, vp, vp, vp, vp, vp, vp, vp], C.c_int),
     "h2_sinsemilla_trace_from_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, vp, vp, vp, vp, vp], C.c_int),
     "h2_ecc_add_trace_device": ([vp, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_range_check_trace_device": ([C.c_int, vp, C.c_size_t, C.c_uint, vp, vp, vp], C.c_int),
+    "h2_short_range_check_trace_device": ([C.c_int, vp, C.c_size_t, C.c_uint, vp, vp, vp], C.c_int),
 }
 
 

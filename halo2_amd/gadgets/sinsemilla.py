@@ -621,10 +621,16 @@ class MerkleChip:
     def hash_to_point(self, layouter, Q, message):                            # noqa: N803
         return self._sinsemilla.hash_to_point(layouter, Q, message)
 
+    def hash_to_point_with_private_init(self, layouter, Q, message):          # noqa: N803 -- merkle/chip.rs:568-577
+        return self._sinsemilla.hash_to_point_with_private_init(layouter, Q, message)
+
     extract = staticmethod(SinsemillaChip.extract)
 
     def swap(self, layouter, pair, swap):
         return self._cond_swap.swap(layouter, pair, swap)
+
+    def mux(self, layouter, choice, left, right):                             # merkle/chip.rs:471-481
+        return self._cond_swap.mux(layouter, choice, left, right)
 
     def load_private(self, layouter, column, value):
         return load_private(layouter, column, value)

@@ -3,12 +3,20 @@
 calls, so that a circuit built from them prints the reference's pinned key.
 
     LookupRangeCheckConfig   the K = 10 running-sum range check over a lookup table (the plain variant)
-    CondSwapChip             a' , b' = swap ? (b, a) : (a, b)
+    LookupRangeCheck4_5BConfig   the same with a tag column: 4- and 5-bit checks take one row instead of three
+    CondSwapChip             a' , b' = swap ? (b, a) : (a, b), and mux
     RunningSumConfig         the running-sum decomposition into windows of at most 3 bits (utilities/decompose_running_sum.rs)
-    bool_check, ternary, range_check, bitrange_subset, i2lebsp, lebs2ip, load_private"""
+    bool_check, ternary, range_check, bitrange_subset, i2lebsp, lebs2ip, load_private
+
+What the reference does not have is the bulk path: `range_check_many` and `short_range_check_many` lay the checks of many values back
+to back in ONE region whose running_sum column comes from the device (`halo2_amd.range_check`), cell for cell the layout of as many
+single calls."""
 from __future__ import annotations
 
-from ..circuit import Assigned, AssignedCell, Column, ConstraintSystem, Expression, Rotation, Selector, TableColumn, Value
+import numpy as np
+
+from .. import range_check as primitive
+from ..circuit import Assigned, AssignedCell, Cell, Column, ConstraintSystem, Expression, Rotation, Selector, Synthesis, TableColumn, Value
 
 K = 10
 
@@ -201,6 +209,195 @@ class LookupRangeCheckConfig:
         region.assign_advice(self.running_sum, 1, lambda: None if v is None else v * (1 << (K - num_bits)) % m)
         region.assign_advice_from_constant(self.running_sum, 2, pow(1 << num_bits, -1, m))
 
+    # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def _field(self) -> int:
+        from .. import fields
+        return next(f for f, m in fields.MODULUS.items() if m == self.modulus)
+
+    def _bulk_rows(self, layouter, elements, values, trace, rows: int, what: str, launch):
+        """The running_sum column of a bulk region, (len(elements) * rows, 4): zeros without a witness, else `trace` or launch(values)."""
+        import torch
+
+        from .. import fields
+        count, m = len(elements), self.modulus
+        if not layouter.cs.collect_advice or not count:
+            return np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (count * rows, 4))
+        if trace is None:
+            if values is None:
+                ints = [value_int(e.value(), m) if isinstance(e, AssignedCell) else (None if e is None else int(e) % m) for e in elements]
+                if any(v is None for v in ints):
+                    raise Synthesis(f"{what}: a witness is needed and there is none")
+                values = fields.to_limbs(ints, self._field(), montgomery=False)
+            if not torch.is_tensor(values):
+                values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint64).view(np.int64)).to(fields.current_device())
+            trace = launch(values)
+        if not torch.is_tensor(trace):
+            trace = torch.from_numpy(np.ascontiguousarray(trace, dtype=np.uint64).view(np.int64))
+        if trace.numel() != count * rows * 4:
+            raise ValueError(f"{what}: the trace is (count, {rows}, 4)")
+        return trace.reshape(count * rows, 4)
+
+    def range_check_many(self, layouter, elements, num_words: int, strict: bool, values=None, trace=None) -> list:
+        """`witness_check` (an integer, or None without a witness) or `copy_check` (an AssignedCell) of every element, back to back in one
+        region of len(elements) * (num_words + 1) rows; per element the gates, lookups and equality constraints of the single call.
+        values: the (count, 4) CANONICAL limbs of the elements where the caller has them on the device (else they are read from the
+        elements); trace: the (count, num_words + 1, 4) rows where the caller has them (else `range_check.decompose`, once).  Without a
+        witness (keygen) the same shape is laid out and nothing is launched.  -> per element the cells z_0 .. z_W."""
+        num_words = int(num_words)
+        assert 1 <= num_words and num_words * K <= self.modulus.bit_length() - 1
+        count, rows = len(elements), num_words + 1
+        column = self._bulk_rows(layouter, elements, values, trace, rows, "range_check_many",
+                                 lambda v: primitive.decompose(v, num_words, field=self._field()))
+        base = rows * np.arange(count, dtype=np.int64)
+        word_rows = (base[:, None] + np.arange(num_words, dtype=np.int64)[None, :]).reshape(-1)
+
+        def assign(region):
+            index = region.region_index
+            region.assign_advice_column(self.running_sum, 0, column)
+            region.enable_selector_rows(self.q_lookup, word_rows)
+            region.enable_selector_rows(self.q_running, word_rows)
+            for i, element in enumerate(elements):
+                if isinstance(element, AssignedCell):
+                    region.constrain_equal(Cell(index, rows * i, self.running_sum), element.cell())
+                if strict:
+                    region.constrain_constant(Cell(index, rows * i + num_words, self.running_sum), 0)
+            return index
+        index = layouter.assign_region(f"{num_words} words range check many", assign)
+        return [[Cell(index, rows * i + j, self.running_sum) for j in range(rows)] for i in range(count)]
+
+    def _short_selectors(self, num_bits: int):
+        """the selectors a short check of num_bits enables beside q_lookup on its one row, or None where it takes the three rows"""
+        return None
+
+    def short_range_check_many(self, layouter, elements, num_bits: int, values=None, trace=None) -> list:
+        """`witness_short_check` (an integer, or None) or `copy_short_check` (an AssignedCell) of every element in one region: three rows
+        each -- the element, its shift (q_lookup on both, q_bitshift on the second) and the constant 2^-num_bits -- or one row each
+        where the config has a selector for num_bits (the 4- and 5-bit checks of LookupRangeCheck4_5BConfig).  values: as
+        `range_check_many`; trace: the (count, 3, 4) rows of `range_check.short`.  -> per element the cell of the element."""
+        num_bits = int(num_bits)
+        assert 0 <= num_bits <= K
+        count, m = len(elements), self.modulus
+        rows3 = self._bulk_rows(layouter, elements, values, trace, 3, "short_range_check_many",
+                                lambda v: primitive.short(v, num_bits, field=self._field()))
+        tagged = self._short_selectors(num_bits)
+        rows = 3 if tagged is None else 1
+        column = rows3 if tagged is None else rows3[0::3]
+        base = rows * np.arange(count, dtype=np.int64)
+        inv_two_pow_s = pow(1 << num_bits, -1, m)
+
+        def assign(region):
+            index = region.region_index
+            region.assign_advice_column(self.running_sum, 0, column)
+            if tagged is None:
+                region.enable_selector_rows(self.q_lookup, np.stack([base, base + 1], axis=1).reshape(-1))
+                region.enable_selector_rows(self.q_bitshift, base + 1)
+            else:
+                region.enable_selector_rows(self.q_lookup, base)
+                region.enable_selector_rows(tagged, base)
+            for i, element in enumerate(elements):
+                if isinstance(element, AssignedCell):
+                    region.constrain_equal(Cell(index, rows * i, self.running_sum), element.cell())
+                if tagged is None:
+                    region.constrain_constant(Cell(index, rows * i + 2, self.running_sum), inv_two_pow_s)
+            return index
+        index = layouter.assign_region(f"Range check {num_bits} bits many", assign)
+        return [Cell(index, rows * i, self.running_sum) for i in range(count)]
+
+
+# ---- LookupRangeCheck4_5BConfig (lookup_range_check.rs:504-851) ----------------------------------------------------------------------------------
+class LookupRangeCheck4_5BConfig(LookupRangeCheckConfig):
+    """The range check over a table of 2^10 + 2^4 + 2^5 rows with a tag column (0, 4, 5): a 4- or 5-bit check is ONE lookup of
+    (value, tag) instead of the three rows of the shifted pair.  The shared methods are the base's; they read q_lookup, q_running,
+    q_bitshift and running_sum from this object, as the reference's trait reads them through config()."""
+
+    def __init__(self, modulus, q_lookup, q_running, q_bitshift, running_sum, table_idx, q_range_check_4, q_range_check_5,
+                 table_range_check_tag):
+        super().__init__(modulus, q_lookup, q_running, q_bitshift, running_sum, table_idx)
+        self.q_range_check_4, self.q_range_check_5, self.table_range_check_tag = q_range_check_4, q_range_check_5, table_range_check_tag
+
+    @staticmethod
+    def configure(meta: ConstraintSystem, running_sum: Column, table_idx: TableColumn) -> "LookupRangeCheck4_5BConfig":
+        table_range_check_tag = meta.lookup_table_column()
+        return LookupRangeCheck4_5BConfig.configure_with_tag(meta, running_sum, table_idx, table_range_check_tag)
+
+    @staticmethod
+    def configure_with_tag(meta: ConstraintSystem, running_sum: Column, table_idx: TableColumn,
+                           table_range_check_tag: TableColumn) -> "LookupRangeCheck4_5BConfig":
+        meta.enable_equality(running_sum)
+        q_lookup = meta.complex_selector()
+        q_running = meta.complex_selector()
+        q_bitshift = meta.selector()
+        q_range_check_4 = meta.complex_selector()
+        q_range_check_5 = meta.complex_selector()
+        config = LookupRangeCheck4_5BConfig(meta.modulus, q_lookup, q_running, q_bitshift, running_sum, table_idx, q_range_check_4,
+                                            q_range_check_5, table_range_check_tag)
+
+        def lookup(cells):                                                    # the trees in the reference's order: the pinned key prints them
+            q_lookup_ = cells.query_selector(q_lookup)
+            q_running_ = cells.query_selector(q_running)
+            q_4 = cells.query_selector(q_range_check_4)
+            q_5 = cells.query_selector(q_range_check_5)
+            z_cur = cells.query_advice(running_sum, Rotation.cur())
+            one = Expression.constant(1)
+            z_next = cells.query_advice(running_sum, Rotation.next())
+            running_sum_word = z_cur - z_next * (1 << K)                      # a_i = z_i - 2^K z_{i+1}
+            running_sum_lookup = q_running_ * running_sum_word
+            q_short = one - q_running_
+            short_lookup = q_short * z_cur
+            q_range_check = one - (one - q_4) * (one - q_5)                   # 1 iff q_4 or q_5
+            num_bits = q_5 * Expression.constant(5) + (one - q_5) * q_4 * Expression.constant(4)
+            return [(q_lookup_ * ((one - q_range_check) * (running_sum_lookup + short_lookup) + q_range_check * z_cur), table_idx),
+                    (q_lookup_ * q_range_check * num_bits, table_range_check_tag)]
+        meta.lookup(lookup)
+
+        def bitshift(cells):
+            q = cells.query_selector(q_bitshift)
+            word = cells.query_advice(running_sum, Rotation.prev())
+            shifted_word = cells.query_advice(running_sum, Rotation.cur())
+            inv_two_pow_s = cells.query_advice(running_sum, Rotation.next())
+            return [q * (word * (1 << K) * inv_two_pow_s - shifted_word)]
+        meta.create_gate("Short lookup bitshift", bitshift)
+        return config
+
+    def load(self, generator_table_config, layouter, table) -> None:
+        """The generator table with its tag: rows 0 .. 1023 tagged 0, the first 16 again at 1024 .. tagged 4, the first 32 again at
+        1040 .. tagged 5; assigned in the reference's interleaved order."""
+        g = generator_table_config
+
+        def assign(t):
+            for index, (x, y) in enumerate(table):
+                copies = [(index, 0)]
+                if index < 1 << 4:
+                    copies.append((index + (1 << K), 4))
+                if index < 1 << 5:
+                    copies.append((index + (1 << K) + (1 << 4), 5))
+                for row, tag in copies:
+                    t.assign_cell(g.table_idx, row, index)
+                    t.assign_cell(g.table_x, row, x)
+                    t.assign_cell(g.table_y, row, y)
+                    t.assign_cell(self.table_range_check_tag, row, tag)
+        layouter.assign_table("generator_table", assign)
+
+    def load_range_check_table(self, layouter) -> None:
+        def assign(t):
+            offset = 0
+            for size, tag in ((1 << K, 0), (1 << 4, 4), (1 << 5, 5)):
+                for index in range(size):
+                    t.assign_cell(self.table_idx, offset + index, index)
+                    t.assign_cell(self.table_range_check_tag, offset + index, tag)
+                offset += size
+        layouter.assign_table("table_idx", assign)
+
+    def _short_selectors(self, num_bits: int):
+        return {4: self.q_range_check_4, 5: self.q_range_check_5}.get(num_bits)
+
+    def short_range_check(self, region, element: AssignedCell, num_bits: int) -> None:
+        tagged = self._short_selectors(num_bits)
+        if tagged is None:
+            return super().short_range_check(region, element, num_bits)
+        self.q_lookup.enable(region, 0)
+        tagged.enable(region, 0)
+
 
 # ---- CondSwapChip (cond_swap.rs:61-296) ----------------------------------------------------------------------------------------------------
 class CondSwapConfig:
@@ -249,6 +446,40 @@ class CondSwapChip:
             b_swapped = region.assign_advice(c.b_swapped, 0, lambda: second)
             return a_swapped, b_swapped
         return layouter.assign_region("swap", assign)
+
+    def mux(self, layouter, choice: AssignedCell, left: AssignedCell, right: AssignedCell) -> AssignedCell:
+        """cond_swap.rs:137-190: `left` where choice is 0, else `right`; the three cells are copied in"""
+        c = self.config
+
+        def is_zero(v):
+            return v.is_zero_vartime() if isinstance(v, Assigned) else int(v) == 0
+
+        def assign(region):
+            c.q_swap.enable(region, 0)
+            left_ = left.copy_advice(region, c.a, 0)
+            right_ = right.copy_advice(region, c.b, 0)
+            choice_ = choice.copy_advice(region, c.swap, 0)
+            l_v, r_v, c_v = left_.value().inner, right_.value().inner, choice_.value().inner
+            known = l_v is not None and r_v is not None and c_v is not None
+            a_swapped = (l_v if is_zero(c_v) else r_v) if known else None
+            b_swapped = (r_v if is_zero(c_v) else l_v) if known else None
+            region.assign_advice(c.b_swapped, 0, lambda: b_swapped)
+            return region.assign_advice(c.a_swapped, 0, lambda: a_swapped)
+        return layouter.assign_region("mux", assign)
+
+    def mux_on_points(self, layouter, choice: AssignedCell, left, right):
+        """cond_swap.rs:196-209 -> EccPoint (from unchecked coordinates)"""
+        from .ecc import EccPoint
+        x_cell = self.mux(layouter, choice, left.x(), right.x())
+        y_cell = self.mux(layouter, choice, left.y(), right.y())
+        return EccPoint(x_cell, y_cell)
+
+    def mux_on_non_identity_points(self, layouter, choice: AssignedCell, left, right):
+        """cond_swap.rs:213-226 -> NonIdentityEccPoint (from unchecked coordinates)"""
+        from .sinsemilla import NonIdentityEccPoint
+        x_cell = self.mux(layouter, choice, left.x(), right.x())
+        y_cell = self.mux(layouter, choice, left.y(), right.y())
+        return NonIdentityEccPoint(x_cell, y_cell)
 
 
 # ---- RunningSumConfig (decompose_running_sum.rs:47-206) ----------------------------------------------------------------------------------------

@@ -720,6 +720,27 @@ int h2_sinsemilla_trace_from_device(const void *d_pieces, size_t count, const ui
                                     const void *d_table, void *d_columns, void *d_status, void *stream);
 int h2_ecc_add_trace_device(const void *d_p_xy, const void *d_q_xy, size_t n, void *d_aux, void *stream);
 
+/* ---- The K = 10 lookup range check (halo2_gadgets utilities/lookup_range_check.rs), its witness in bulk ---- */
+/* One lane per OUTPUT ROW.  `field` is H2_FP or H2_FQ.  d_values holds `count` CANONICAL field elements of 4 limbs, as
+ * h2_sinsemilla_trace_device takes its pieces; every output is a Montgomery element, the form of a cell.  d_status (one byte per value)
+ * may be null.  count = 0 succeeds without a launch; count > 2^30 or a null d_values or d_rows with count > 0 are H2_ERR_ARGS.
+ *
+ * h2_range_check_trace_device: the running sums of LookupRangeCheck::range_check.  d_rows holds count * (num_words + 1) elements; rows
+ * i (num_words + 1) .. i (num_words + 1) + num_words are z_0 .. z_W of value i, z_j = value >> 10 j as an integer: the reference's
+ * z_{j+1} = (z_j - a_j) / 2^10 exactly, a_j being the j-th 10-bit word (the difference is a multiple of 2^10 below p).  d_status[i] = 1
+ * where z_W != 0, i.e. value >= 2^(10 num_words), else 0; the rows are written either way (a non-strict check uses them).  num_words
+ * outside 1 .. 25 (25 * 10 <= 254, the field's capacity) is H2_ERR_ARGS.
+ *
+ * h2_short_range_check_trace_device: the three rows of LookupRangeCheck::short_range_check.  d_rows holds 3 * count elements; rows 3 i,
+ * 3 i + 1, 3 i + 2 are value, value * 2^(10 - num_bits) IN THE FIELD (a value above 10 bits still gets the product the gate "Short
+ * lookup bitshift" checks) and the constant 2^-num_bits.  d_status[i] = 1 where the canonical value >= 2^num_bits, else 0.  The 4- and
+ * 5-bit checks of LookupRangeCheck4_5BConfig consume rows 3 i alone; the same three rows are written regardless.  num_bits > 10 is
+ * H2_ERR_ARGS. */
+int h2_range_check_trace_device(int field, const void *d_values, size_t count, unsigned num_words, void *d_rows, void *d_status,
+                                void *stream);
+int h2_short_range_check_trace_device(int field, const void *d_values, size_t count, unsigned num_bits, void *d_rows, void *d_status,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
