@@ -104,6 +104,40 @@ template <typename T> struct StreamContexts {
     }
 };
 
+// The workspace of a unit whose only cached device memory is one scratch buffer.  Each unit keeps its own StreamContexts of these:
+// no two units share scratch or a mutex.
+struct ScratchContext {
+    std::mutex mu;
+    DevBuf scratch;
+    void release_all() { scratch.release(); }
+};
+
+inline unsigned grid_of(size_t n, unsigned lanes) { return (unsigned)((n + lanes - 1) / lanes); }   // workgroups of `lanes` for n lanes
+
+// The two-pass scheme of the witness traces (the head of sinsemilla.hip): pass A stores `per_lane` Fp products of denominators for
+// each of `count` lanes, h2_batch_invert_device inverts them in place, pass B finds the inverses where the products were.  The lanes
+// go through in chunks whose scratch stays within `budget` elements; `scratch` is grown once, to the widest chunk.
+// pass(emit, first, chunk, scratch) enqueues pass A (emit = false) or pass B of lanes first .. first + chunk on `st` and returns
+// H2_OK or what failed; a launch error it left behind is picked up here.  per_lane = 0: nothing to invert, pass B alone runs.
+// The callers name pass A's kernel first (!emit ? k<false> : k<true>): a unit's kernels are laid out in the order of their first
+// use, and the other order moved ecc_mul_trace's timing (profiles/gadget_kernels_shared.txt).
+template <typename Pass> int two_pass_trace(DevBuf &scratch, size_t count, size_t per_lane, size_t budget, hipStream_t st, Pass pass) {
+    const size_t per_chunk = per_lane ? budget / per_lane : count;
+    int rc = scratch.reserve((count < per_chunk ? count : per_chunk) * per_lane * 32);
+    if (rc != H2_OK) return rc;
+    for (size_t first = 0; first < count; first += per_chunk) {
+        const size_t chunk = count - first < per_chunk ? count - first : per_chunk;
+        if (per_lane) {
+            if ((rc = pass(false, first, chunk, scratch.as<uint32_t>())) != H2_OK) return rc;
+            H2_HIP(hipGetLastError());
+            if ((rc = h2_batch_invert_device(H2_FP, scratch.ptr, chunk * per_lane, H2_FORM_MONTGOMERY, st)) != H2_OK) return rc;
+        }
+        if ((rc = pass(true, first, chunk, scratch.as<uint32_t>())) != H2_OK) return rc;
+        H2_HIP(hipGetLastError());
+    }
+    return H2_OK;
+}
+
 // Optional kernel timing with HIP events on the launching stream (h2_profile_enable): bench.py uses it to
 // measure the dominant kernels' average duration live, inside the timed region.
 enum ProfSlot { PROF_MSM_ACCUMULATE = 0, PROF_NTT_PASS = 1, PROF_MSM_SORT = 2, PROF_MSM_REDUCE = 3, PROF_SLOTS = 4 };

@@ -10,15 +10,17 @@
 //
 // The trace follows the reference's algorithm, not the fastest one: Acc = [2]P, then 251 merged steps Acc <- (Acc + (+-P)) + Acc with
 // INCOMPLETE addition over the bits k_254 .. k_4 of k = alpha + t_q, three steps with complete addition, and the last bit.  The merged
-// step is Sinsemilla's round (sinsemilla.hip; the round below is a copy, that file's kernels are pinned by their own resource test) with
-// S = +-P, and the same answer to the 502 inversions per lane: pass A runs the chain in XYZZ and stores one element per row, the product
-// ZZ ZZZ P D; h2_batch_invert_device inverts them all (zeros stay zero: inv0); pass B runs the chain again and emits affine rows.  Two
-// more elements ride in the same batch: ZZ ZZZ of the last accumulator, and z_130 whose inverse is the overflow check's eta.
+// step is Sinsemilla's round (double_add_round.cuh, shared with sinsemilla.hip) with S = +-P, and the same answer to the 502 inversions
+// per lane: pass A runs the chain in XYZZ and stores one element per row, the product ZZ ZZZ P D; h2_batch_invert_device inverts them
+// all (zeros stay zero: inv0); pass B runs the chain again, splits each inverse (round_row, the same header) and emits affine rows; the
+// chunks and the inversion between the passes are two_pass_trace's (common.h).  Two more elements ride in the same batch: ZZ ZZZ of
+// the last accumulator, and z_130 whose inverse is the overflow check's eta.
 // The 8 complete additions (row 0's [2]P, two per complete bit, one for the last bit) take their operands from the previous result
 // and run in a kernel of their own after pass B, which keeps the inversion's registers out of the chain's loop;
 // each (complete_add, ecc_add.cuh) forms the product of its nonzero denominators -- x_q - x_p (or y_q + y_p, or 2 y_p, when that vanishes), x_p, x_q -- inverts it
 // on the lane (field_inv.cuh) and splits it: 8 inversions against the 251 rounds of 32 products, measured in profiles/ecc.txt.
 #include "common.h"
+#include "double_add_round.cuh"
 #include "ecc_add.cuh"
 
 namespace h2 {
@@ -33,27 +35,6 @@ constexpr u32 kScratch = kRounds + 2;                      // scratch elements p
 // device is full, and at sinsemilla.hip's 2^20 elements a chunk is 4 143 lanes, 65 waves on 256 compute units: 32 768 multiplications
 // took eight chunks one after the other (profiles/ecc.txt).  Their ten columns are 1.4 GiB, so the scratch stays a fraction of the output.
 constexpr size_t kTraceScratchRows = (size_t)1 << 23;
-
-// A copy of sinsemilla.hip's round: Acc <- (Acc + S) + Acc; p and d are the two differences incomplete addition must not see vanish,
-// zz_r is (Acc + S)'s ZZ.  No branch: a vanishing difference leaves ZZ = 0 behind, which the caller reports.
-__device__ __forceinline__ void double_and_add_round(xyzz<FP> &a, const affine<FP> &s, fe &p, fe &r, fe &d, fe &zz_r) {
-    p = fe_sub<FP>(fe_mulx<FP>(s.x, a.zz), a.x);
-    r = fe_sub<FP>(fe_mulx<FP>(s.y, a.zzz), a.y);
-    const fe pp = fe_sqr<FP>(p), ppp = fe_mulx<FP>(p, pp);
-    const fe xa = fe_mulx<FP>(a.x, pp), ya = fe_mulx<FP>(a.y, ppp);                       // Acc over R's denominators
-    const fe xr = fe_sub<FP>(fe_sub<FP>(fe_sub<FP>(fe_sqr<FP>(r), ppp), xa), xa);
-    const fe yr = fe_sub<FP>(fe_mulx<FP>(r, fe_sub<FP>(xa, xr)), ya);
-    zz_r = fe_mulx<FP>(a.zz, pp);
-    const fe zzz_r = fe_mulx<FP>(a.zzz, ppp);
-    d = fe_sub<FP>(xa, xr);
-    const fe e = fe_sub<FP>(ya, yr);
-    const fe dd = fe_sqr<FP>(d), ddd = fe_mulx<FP>(d, dd);
-    const fe q = fe_mulx<FP>(xr, dd);
-    a.x = fe_sub<FP>(fe_sub<FP>(fe_sub<FP>(fe_sqr<FP>(e), ddd), q), q);
-    a.y = fe_sub<FP>(fe_mulx<FP>(e, fe_sub<FP>(q, a.x)), fe_mulx<FP>(yr, ddd));
-    a.zz = fe_mulx<FP>(zz_r, dd);
-    a.zzz = fe_mulx<FP>(zzz_r, ddd);
-}
 
 // the top bit of a 256-bit word, which then moves up by one
 __device__ __forceinline__ u32 take_top_bit(u32 (&k)[8]) {
@@ -143,39 +124,30 @@ __global__ void __launch_bounds__(kET) ecc_mul_trace(const u32 *__restrict__ bas
         const xyzz<FP> before = a;
         const fe zed = fe_mulx<FP>(a.zz, a.zzz);
         fe p, r, d, zz_r;
-        double_and_add_round(a, s, p, r, d, zz_r);
+        double_add_round(a, s, p, r, d, zz_r);
         bad = bad || fe_is_zero(p) || fe_is_zero(d);
         if (!EMIT) {
-            fe_store(t + 8 * j, fe_mulx<FP>(fe_mulx<FP>(zed, p), d));
+            fe_store(t + 8 * j, round_denominators(zed, p, d));
         } else {
-            const fe all = fe_load(t + 8 * j);                                             // 1 / (ZZ ZZZ P D)
-            const fe i_zed = fe_mulx<FP>(all, fe_mulx<FP>(p, d)), az = fe_mulx<FP>(all, zed);
-            const fe i_p = fe_mulx<FP>(az, d), i_d = fe_mulx<FP>(az, p);
-            const fe i_zzz = fe_mulx<FP>(before.zz, i_zed);
-            const fe x_a = fe_mulx<FP>(before.x, fe_mulx<FP>(before.zzz, i_zed));
-            // y_a - y_p = -r / ZZZ and x_a - x_p = -p / ZZ:  lambda_1 = r ZZ / (ZZZ p)
-            const fe lambda_1 = fe_mulx<FP>(fe_mulx<FP>(r, i_zzz), fe_mulx<FP>(before.zz, i_p));
-            // x_a - x_r = d / ZZ_R:  lambda_2 = 2 y_a ZZ_R / d - lambda_1
-            const fe y_a = fe_mulx<FP>(before.y, i_zzz);
-            const fe lambda_2 = fe_sub<FP>(fe_mulx<FP>(fe_dbl<FP>(y_a), fe_mulx<FP>(zz_r, i_d)), lambda_1);
+            const RoundRow v = round_row(before, zed, p, r, d, zz_r, fe_load(t + 8 * j));
             const u32 c_z = hi ? 9 : 6, c_xa = hi ? 3 : 7, c_l1 = hi ? 4 : 8, c_l2 = hi ? 5 : 2;
             if (j == 0 || j == kHiLen) {                                                   // a half starts: z and y_a one row above
                 fe_store(out + c_z * column + 8, z);
-                fe_store(out + c_l1 * column + 8, y_a);
+                fe_store(out + c_l1 * column + 8, v.y_a);
             }
             z = fe_dbl<FP>(z);
             if (bit) z = fe_add<FP>(z, fe_one<FP>());
             fe_store(out + c_z * column + 8 * row, z);
-            fe_store(out + c_xa * column + 8 * row, x_a);
-            fe_store(out + c_l1 * column + 8 * row, lambda_1);
-            fe_store(out + c_l2 * column + 8 * row, lambda_2);
+            fe_store(out + c_xa * column + 8 * row, v.x_a);
+            fe_store(out + c_l1 * column + 8 * row, v.lambda_1);
+            fe_store(out + c_l2 * column + 8 * row, v.lambda_2);
             if (!hi) {                                                                     // the lo half spans every row of the range
                 fe_store(out + 8 * row, base.x);
                 fe_store(out + column + 8 * row, base.y);
             }
             if (j == kHiLen) {                                                             // and the hi half ends on the same point
-                fe_store(out + 3 * column + 8 * (2 + kHiLen), x_a);
-                fe_store(out + 4 * column + 8 * (2 + kHiLen), y_a);
+                fe_store(out + 3 * column + 8 * (2 + kHiLen), v.x_a);
+                fe_store(out + 4 * column + 8 * (2 + kHiLen), v.y_a);
             }
         }
     }
@@ -269,14 +241,7 @@ __global__ void __launch_bounds__(kET) ecc_mul_complete(const u32 *__restrict__ 
     fe_store(x + 8 * 15, fe_load(inv + 8 * (local * kScratch + kRounds + 1)));
 }
 
-struct EccContext {
-    std::mutex mu;
-    DevBuf scratch;
-    void release_all() { scratch.release(); }
-};
-StreamContexts<EccContext> g_ecc_ctxs;
-
-inline unsigned grid_of(size_t n) { return (unsigned)((n + kET - 1) / kET); }
+StreamContexts<ScratchContext> g_ecc_ctxs;
 
 }  // namespace
 
@@ -291,7 +256,7 @@ extern "C" int h2_ecc_mul_device(const void *d_bases_xy, const void *d_scalars, 
     int rc = ensure_device();
     if (rc != H2_OK) return rc;
     if (!n) return H2_OK;
-    hipLaunchKernelGGL(ecc_mul, dim3(grid_of(n)), dim3(kET), 0, (hipStream_t)stream, (const u32 *)d_bases_xy, (const u32 *)d_scalars, n,
+    hipLaunchKernelGGL(ecc_mul, dim3(grid_of(n, kET)), dim3(kET), 0, (hipStream_t)stream, (const u32 *)d_bases_xy, (const u32 *)d_scalars, n,
                        (u32 *)d_out_xy, (uint8_t *)d_status);
     H2_HIP(hipGetLastError());
     return H2_OK;
@@ -303,25 +268,17 @@ extern "C" int h2_ecc_mul_trace_device(const void *d_bases_xy, const void *d_alp
     int rc = ensure_device();
     if (rc != H2_OK) return rc;
     if (!count) return H2_OK;
-    const size_t per_chunk = kTraceScratchRows / kScratch;
     hipStream_t st = (hipStream_t)stream;
-    EccContext &ctx = g_ecc_ctxs.get(st);
+    ScratchContext &ctx = g_ecc_ctxs.get(st);
     std::lock_guard<std::mutex> lk(ctx.mu);
-    const size_t widest = count < per_chunk ? count : per_chunk;
-    if ((rc = ctx.scratch.reserve(widest * kScratch * 32)) != H2_OK) return rc;
     H2_HIP(hipMemsetAsync(d_columns, 0, (size_t)10 * kRows * count * 32, st));    // zero where the reference assigns nothing
-    for (size_t first = 0; first < count; first += per_chunk) {
-        const size_t chunk = count - first < per_chunk ? count - first : per_chunk;
-        hipLaunchKernelGGL(ecc_mul_trace<false>, dim3(grid_of(chunk)), dim3(kET), 0, st, (const u32 *)d_bases_xy, (const u32 *)d_alphas, first,
-                           chunk, count, ctx.scratch.as<u32>(), (u32 *)d_columns, (uint8_t *)d_status);
+    return two_pass_trace(ctx.scratch, count, kScratch, kTraceScratchRows, st, [&](bool emit, size_t first, size_t chunk, u32 *scratch) {
+        hipLaunchKernelGGL(!emit ? ecc_mul_trace<false> : ecc_mul_trace<true>, dim3(grid_of(chunk, kET)), dim3(kET), 0, st,
+                           (const u32 *)d_bases_xy, (const u32 *)d_alphas, first, chunk, count, scratch, (u32 *)d_columns, (uint8_t *)d_status);
+        if (!emit) return H2_OK;
         H2_HIP(hipGetLastError());
-        if ((rc = h2_batch_invert_device(H2_FP, ctx.scratch.ptr, chunk * kScratch, H2_FORM_MONTGOMERY, stream)) != H2_OK) return rc;
-        hipLaunchKernelGGL(ecc_mul_trace<true>, dim3(grid_of(chunk)), dim3(kET), 0, st, (const u32 *)d_bases_xy, (const u32 *)d_alphas, first,
-                           chunk, count, ctx.scratch.as<u32>(), (u32 *)d_columns, (uint8_t *)d_status);
-        H2_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ecc_mul_complete, dim3(grid_of(chunk)), dim3(kET), 0, st, (const u32 *)d_bases_xy, (const u32 *)d_alphas, first,
-                           chunk, count, ctx.scratch.as<const u32>(), (u32 *)d_columns, (u32 *)d_aux);
-        H2_HIP(hipGetLastError());
-    }
-    return H2_OK;
+        hipLaunchKernelGGL(ecc_mul_complete, dim3(grid_of(chunk, kET)), dim3(kET), 0, st, (const u32 *)d_bases_xy, (const u32 *)d_alphas, first,
+                           chunk, count, (const u32 *)scratch, (u32 *)d_columns, (u32 *)d_aux);   // the rows pass B left to it, same chunk
+        return H2_OK;
+    });
 }

@@ -1,5 +1,5 @@
 // The ECC chip's complete addition with its witnesses (halo2_gadgets ecc/chip/add.rs) and the curve check, on one lane; shared by the
-// variable-base kernels (ecc.hip) and the fixed-base ones (ecc_fixed.hip).
+// variable-base kernels (ecc.hip), the fixed-base ones (ecc_fixed.hip) and the batched addition's trace (sinsemilla_commit.hip).
 #pragma once
 #include "curve.cuh"
 
@@ -47,6 +47,22 @@ __device__ __forceinline__ affine<FP> complete_add(const affine<FP> &p, const af
     r.x = fe_select(pz, q.x, fe_select(qz, p.x, fe_select(none, zero, r.x)));
     r.y = fe_select(pz, q.y, fe_select(qz, p.y, fe_select(none, zero, r.y)));
     return r;
+}
+
+// The 11 elements a trace keeps of one complete addition: x_p y_p x_qr y_qr lambda alpha beta gamma delta x_r y_r (d_aux of
+// h2_ecc_mul_fixed_trace_device and h2_ecc_add_trace_device)
+__device__ __forceinline__ void store_add_aux(u32 *x, const affine<FP> &p, const affine<FP> &q, const AddWitness &w, const affine<FP> &sum) {
+    fe_store(x, p.x);
+    fe_store(x + 8, p.y);
+    fe_store(x + 16, q.x);
+    fe_store(x + 24, q.y);
+    fe_store(x + 32, w.lambda);
+    fe_store(x + 40, w.alpha);
+    fe_store(x + 48, w.beta);
+    fe_store(x + 56, w.gamma);
+    fe_store(x + 64, w.delta);
+    fe_store(x + 72, sum.x);
+    fe_store(x + 80, sum.y);
 }
 
 }  // namespace h2

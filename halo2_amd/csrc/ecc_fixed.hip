@@ -11,7 +11,9 @@
 // The additions of windows 1 .. nw-2 are INCOMPLETE and need no exceptional branch: before window w the accumulator is [s]B with
 // 0 < s = sum_{j<w} (k_j + 2) 8^j < 2 8^w <= (k_w + 2) 8^w, so s differs from the window's scalar, and their sum is below 11 8^83 < q
 // (the group's order) through window 83, so they are not opposite either.  The last addition is complete: k = 0 ends on the identity,
-// and the octal strings 1333...3334 and its unreduced twin (full_width.rs, LAST_DOUBLING) end on a doubling.
+// and the octal strings 1333...3334 and its unreduced twin (full_width.rs, LAST_DOUBLING) end on a doubling.  The chain is
+// fixed_base_chain (ecc_fixed_chain.cuh), which the Sinsemilla commitment runs too; the trace walks the same windows one by one around
+// two_pass_trace (common.h) and closes on complete_add and its record (ecc_add.cuh).
 //
 // The table (680 points, 43.5 KB at 85 windows) is gathered from global memory: the window is uniform across a wave, so its 64 lanes
 // read within one 512-byte row of eight points, which the vector cache serves; staging in LDS was not measured.
@@ -119,11 +121,7 @@ __global__ void __launch_bounds__(kFT) ecc_fixed_mul(const u32 *__restrict__ poi
     if (i >= n) return;
     u32 k[8];
     load_scalar(scalars, i, k);
-    xyzz<FP> acc = xyzz_of(aff_load<FP>(table_entry(points, 0, take_window(k), 16)));
-#pragma unroll 1
-    for (u32 w = 1; w + 1 < nw; w++) xyzz_madd_incomplete(acc, aff_load<FP>(table_entry(points, w, take_window(k), 16)));
-    xyzz_madd<FP>(acc, aff_load<FP>(table_entry(points, nw - 1, take_window(k), 16)));
-    const affine<FP> res = xyzz_to_affine<FP>(acc);
+    const affine<FP> res = xyzz_to_affine<FP>(fixed_base_chain(points, nw, k));
     fe_store(out_xy + 16 * i, res.x);
     fe_store(out_xy + 16 * i + 8, res.y);
 }
@@ -178,30 +176,12 @@ __global__ void __launch_bounds__(kFT) ecc_fixed_trace(const u32 *__restrict__ p
         } else if (EMIT) {                                  // full_width.rs:150-159: the window's point first, the accumulator second
             AddWitness wit;
             const affine<FP> sum = complete_add(q, a, wit);
-            u32 *x = aux + 8 * 11 * i;
-            fe_store(x, q.x);
-            fe_store(x + 8, q.y);
-            fe_store(x + 16, a.x);
-            fe_store(x + 24, a.y);
-            fe_store(x + 32, wit.lambda);
-            fe_store(x + 40, wit.alpha);
-            fe_store(x + 48, wit.beta);
-            fe_store(x + 56, wit.gamma);
-            fe_store(x + 64, wit.delta);
-            fe_store(x + 72, sum.x);
-            fe_store(x + 80, sum.y);
+            store_add_aux(aux + 8 * 11 * i, q, a, wit, sum);
         }
     }
 }
 
-struct EccFixedContext {
-    std::mutex mu;
-    DevBuf scratch;
-    void release_all() { scratch.release(); }
-};
-StreamContexts<EccFixedContext> g_ecc_fixed_ctxs;
-
-inline unsigned grid_of(size_t n) { return (unsigned)((n + kFT - 1) / kFT); }
+StreamContexts<ScratchContext> g_ecc_fixed_ctxs;
 
 // ---- host arithmetic of the table build ---------------------------------------------------------------------------------------------------
 void host_neg(int f, u64 r[4], const u64 a[4]) {
@@ -296,7 +276,7 @@ static int tables_run(TableHost &host, unsigned nw, uint64_t limit, char *scratc
     H2_HIP(hipMemcpyAsync(scratch + off_matrix, host.matrix, sizeof host.matrix, hipMemcpyHostToDevice, st));
     int rc = h2_ecc_mul_device(scratch, scratch + off_scalars, entries, d_points, scratch + off_status, st);
     if (rc != H2_OK) return rc;
-    hipLaunchKernelGGL(ecc_fixed_lagrange, dim3(grid_of(entries)), dim3(kFT), 0, st, (const u32 *)d_points, (const u32 *)(scratch + off_matrix),
+    hipLaunchKernelGGL(ecc_fixed_lagrange, dim3(grid_of(entries, kFT)), dim3(kFT), 0, st, (const u32 *)d_points, (const u32 *)(scratch + off_matrix),
                        entries, (u32 *)d_lagrange);
     H2_HIP(hipGetLastError());
     H2_HIP(hipMemcpyAsync(d_z, host.z.data(), (size_t)8 * nw, hipMemcpyHostToDevice, st));
@@ -307,7 +287,7 @@ static int tables_run(TableHost &host, unsigned nw, uint64_t limit, char *scratc
         }
         const uint64_t span = limit - first < kSearchRound ? limit - first : kSearchRound;
         H2_HIP(hipMemcpyAsync(scratch + off_active, host.active.data(), 4 * host.active.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(ecc_fixed_search, dim3(grid_of(span), (unsigned)host.active.size()), dim3(kFT), 0, st, (const u32 *)d_points,
+        hipLaunchKernelGGL(ecc_fixed_search, dim3(grid_of(span, kFT), (unsigned)host.active.size()), dim3(kFT), 0, st, (const u32 *)d_points,
                            (const u32 *)(scratch + off_active), (u64)first, (u64)limit, (unsigned long long *)d_z);
         H2_HIP(hipGetLastError());
         H2_HIP(hipMemcpyAsync(host.z.data(), d_z, (size_t)8 * nw, hipMemcpyDeviceToHost, st));
@@ -316,7 +296,7 @@ static int tables_run(TableHost &host, unsigned nw, uint64_t limit, char *scratc
         for (unsigned w = 0; w < nw; w++)
             if (host.z[w] == kNoZ) host.active.push_back(w);
     }
-    hipLaunchKernelGGL(ecc_fixed_roots, dim3(grid_of(entries)), dim3(kFT), 0, st, (const u32 *)d_points, (const unsigned long long *)d_z, entries,
+    hipLaunchKernelGGL(ecc_fixed_roots, dim3(grid_of(entries, kFT)), dim3(kFT), 0, st, (const u32 *)d_points, (const unsigned long long *)d_z, entries,
                        (u32 *)d_u);
     H2_HIP(hipGetLastError());
     return H2_OK;
@@ -330,7 +310,7 @@ extern "C" int h2_ecc_fixed_tables_device(const uint64_t *base_xy, unsigned num_
     if (rc != H2_OK) return rc;
     const unsigned nw = num_windows;
     hipStream_t st = (hipStream_t)stream;
-    EccFixedContext &ctx = g_ecc_fixed_ctxs.get(st);
+    ScratchContext &ctx = g_ecc_fixed_ctxs.get(st);
     std::lock_guard<std::mutex> lk(ctx.mu);
     if ((rc = ctx.scratch.reserve((size_t)(64 + 32) * 8 * nw + 64 * 32 + 32 * nw + 4 * nw)) != H2_OK) return rc;
     TableHost host;
@@ -355,7 +335,7 @@ extern "C" int h2_ecc_mul_fixed_device(const void *d_points, unsigned num_window
     int rc = ensure_device();
     if (rc != H2_OK) return rc;
     if (!n) return H2_OK;
-    hipLaunchKernelGGL(ecc_fixed_mul, dim3(grid_of(n)), dim3(kFT), 0, (hipStream_t)stream, (const u32 *)d_points, num_windows,
+    hipLaunchKernelGGL(ecc_fixed_mul, dim3(grid_of(n, kFT)), dim3(kFT), 0, (hipStream_t)stream, (const u32 *)d_points, num_windows,
                        (const u32 *)d_scalars, n, (u32 *)d_out_xy);
     H2_HIP(hipGetLastError());
     return H2_OK;
@@ -369,24 +349,14 @@ extern "C" int h2_ecc_mul_fixed_trace_device(const void *d_points, const void *d
     int rc = ensure_device();
     if (rc != H2_OK) return rc;
     if (!count) return H2_OK;
-    const size_t slots = num_windows - 2;
-    const size_t per_chunk = slots ? kTraceScratchElems / slots : count;
     hipStream_t st = (hipStream_t)stream;
-    EccFixedContext &ctx = g_ecc_fixed_ctxs.get(st);
+    ScratchContext &ctx = g_ecc_fixed_ctxs.get(st);
     std::lock_guard<std::mutex> lk(ctx.mu);
-    const size_t widest = count < per_chunk ? count : per_chunk;
-    if ((rc = ctx.scratch.reserve(widest * slots * 32)) != H2_OK) return rc;
-    for (size_t first = 0; first < count; first += per_chunk) {
-        const size_t chunk = count - first < per_chunk ? count - first : per_chunk;
-        if (slots) {
-            hipLaunchKernelGGL(ecc_fixed_trace<false>, dim3(grid_of(chunk)), dim3(kFT), 0, st, (const u32 *)d_points, (const u32 *)d_u,
-                               num_windows, (const u32 *)d_scalars, first, chunk, count, ctx.scratch.as<u32>(), (u32 *)d_columns, (u32 *)d_aux);
-            H2_HIP(hipGetLastError());
-            if ((rc = h2_batch_invert_device(H2_FP, ctx.scratch.ptr, chunk * slots, H2_FORM_MONTGOMERY, stream)) != H2_OK) return rc;
-        }
-        hipLaunchKernelGGL(ecc_fixed_trace<true>, dim3(grid_of(chunk)), dim3(kFT), 0, st, (const u32 *)d_points, (const u32 *)d_u, num_windows,
-                           (const u32 *)d_scalars, first, chunk, count, ctx.scratch.as<u32>(), (u32 *)d_columns, (u32 *)d_aux);
-        H2_HIP(hipGetLastError());
-    }
-    return H2_OK;
+    // num_windows - 2 elements per lane; two windows have none, and pass B runs alone
+    return two_pass_trace(ctx.scratch, count, num_windows - 2, kTraceScratchElems, st, [&](bool emit, size_t first, size_t chunk, u32 *scratch) {
+        hipLaunchKernelGGL(!emit ? ecc_fixed_trace<false> : ecc_fixed_trace<true>, dim3(grid_of(chunk, kFT)), dim3(kFT), 0, st,
+                           (const u32 *)d_points, (const u32 *)d_u, num_windows, (const u32 *)d_scalars, first, chunk, count, scratch,
+                           (u32 *)d_columns, (u32 *)d_aux);
+        return H2_OK;
+    });
 }

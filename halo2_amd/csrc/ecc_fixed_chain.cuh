@@ -38,5 +38,15 @@ __device__ __forceinline__ void xyzz_madd_incomplete(xyzz<FP> &acc, const affine
 
 __device__ __forceinline__ const u32 *table_entry(const u32 *table, u32 w, u32 k, u32 limbs) { return table + limbs * (8 * w + k); }
 
+// [k]B over B's table of nw windows, which consumes k: window 0's point, the incomplete additions of windows 1 .. nw-2, and the last
+// window's, complete (the head of ecc_fixed.hip)
+__device__ __forceinline__ xyzz<FP> fixed_base_chain(const u32 *points, u32 nw, u32 (&k)[8]) {
+    xyzz<FP> acc = xyzz_of(aff_load<FP>(table_entry(points, 0, take_window(k), 16)));
+#pragma unroll 1
+    for (u32 w = 1; w + 1 < nw; w++) xyzz_madd_incomplete(acc, aff_load<FP>(table_entry(points, w, take_window(k), 16)));
+    xyzz_madd<FP>(acc, aff_load<FP>(table_entry(points, nw - 1, take_window(k), 16)));
+    return acc;
+}
+
 }  // namespace
 }  // namespace h2

@@ -231,30 +231,37 @@ def merkle_root(leaves, domain=None):
     return t[0].cpu().numpy().view(np.uint64) if host else t[0]
 
 
-def trace(pieces, num_words, Q, table=None, with_status: bool = False):
-    """What SinsemillaChip.hash_to_point witnesses for `count` messages of one piece structure.  pieces: (count, n_pieces, 4) CANONICAL
-    limbs (piece k carries num_words[k] <= 25 words, low bits first); Q an (x, y) pair.  -> (5, rows * count, 4) Montgomery limbs, the
-    columns x_a, x_p, bits, lambda_1, lambda_2 with rows = sum(num_words) + 1 per message (see include/halo2_mi355x.h).  A message
-    without a value raises `Bottom`, or is flagged in the returned status with with_status."""
+def _trace(name, entry, lead, pieces, num_words, q_of, table, with_status):
+    """What `trace` (lead = 0) and `trace_from` (lead = 1 more row per message) share: the checks of pieces and num_words, the call of
+    lib().<entry> and the status.  q_of(p, count, host) -> the entry point's Q argument, a host pointer or a CUDA tensor."""
     import torch
     num_words = [int(w) for w in num_words]
     host = not _is_torch(pieces)
     p = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else pieces.contiguous()
     if p.ndim != 3 or p.shape[1] != len(num_words) or p.shape[2] != 4 or p.dtype != torch.int64:
-        raise ValueError("sinsemilla.trace: pieces is a (count, n_pieces, 4) array of canonical limbs")
+        raise ValueError(f"sinsemilla.{name}: pieces is a (count, n_pieces, 4) array of canonical limbs")
     if not num_words or any(not 1 <= w <= 25 for w in num_words) or sum(num_words) > C_MAX:
-        raise ValueError("sinsemilla.trace: 1 .. 25 words per piece, 253 per message")
-    count, rows = p.shape[0], sum(num_words) + 1
+        raise ValueError(f"sinsemilla.{name}: 1 .. 25 words per piece, 253 per message")
+    count, rows = p.shape[0], sum(num_words) + 1 + lead
+    q = q_of(p, count, host)
     tab = _device_table(table)
     out = torch.empty((5, rows * count, 4), dtype=torch.int64, device=p.device)
     status = torch.empty((count,), dtype=torch.uint8, device=p.device)
     nw = (C.c_uint32 * len(num_words))(*num_words)
-    check(lib().h2_sinsemilla_trace_device(_ptr(p), count, nw, len(num_words), _p(_q_limbs(Q)), tab.data_ptr(), _ptr(out), _ptr(status),
-                                           _stream_ptr()), "h2_sinsemilla_trace_device")
+    check(getattr(lib(), entry)(_ptr(p), count, nw, len(num_words), _ptr(q) if _is_torch(q) else q, tab.data_ptr(), _ptr(out), _ptr(status),
+                                _stream_ptr()), entry)
     if with_status:
         return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
-    _raise_bottom(status, "sinsemilla.trace")
+    _raise_bottom(status, f"sinsemilla.{name}")
     return out.cpu().numpy().view(np.uint64) if host else out
+
+
+def trace(pieces, num_words, Q, table=None, with_status: bool = False):
+    """What SinsemillaChip.hash_to_point witnesses for `count` messages of one piece structure.  pieces: (count, n_pieces, 4) CANONICAL
+    limbs (piece k carries num_words[k] <= 25 words, low bits first); Q an (x, y) pair.  -> (5, rows * count, 4) Montgomery limbs, the
+    columns x_a, x_p, bits, lambda_1, lambda_2 with rows = sum(num_words) + 1 per message (see include/halo2_mi355x.h).  A message
+    without a value raises `Bottom`, or is flagged in the returned status with with_status."""
+    return _trace("trace", "h2_sinsemilla_trace_device", 0, pieces, num_words, lambda p, count, host: _p(_q_limbs(Q)), table, with_status)
 
 
 def trace_from(pieces, num_words, Q, table=None, with_status: bool = False):
@@ -262,29 +269,12 @@ def trace_from(pieces, num_words, Q, table=None, with_status: bool = False):
     configured with allow_init_from_private_point (hash_to_point.rs:117-121, :179-182).  Q: (count, 8) Montgomery affine points of the
     kind of `pieces`, or one (x, y) pair of integers for all.  -> (5, rows * count, 4) with rows = sum(num_words) + 2: row 0 of a
     message holds y_Q in x_p and zeros elsewhere, the rest are the rows of `trace` from that Q."""
-    import torch
-    num_words = [int(w) for w in num_words]
-    host = not _is_torch(pieces)
-    p = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.uint64).view(np.int64)).to(fields.current_device()) if host else pieces.contiguous()
-    if p.ndim != 3 or p.shape[1] != len(num_words) or p.shape[2] != 4 or p.dtype != torch.int64:
-        raise ValueError("sinsemilla.trace_from: pieces is a (count, n_pieces, 4) array of canonical limbs")
-    if not num_words or any(not 1 <= w <= 25 for w in num_words) or sum(num_words) > C_MAX:
-        raise ValueError("sinsemilla.trace_from: 1 .. 25 words per piece, 253 per message")
-    count, rows = p.shape[0], sum(num_words) + 2
-    if isinstance(Q, (tuple, list)) and len(Q) == 2 and all(isinstance(c, int) for c in Q):
-        q = torch.from_numpy(_q_limbs(Q).view(np.int64)).to(p.device).repeat(count, 1)
-    else:
-        q = _device_points(Q, count, host, "sinsemilla.trace_from")
-    tab = _device_table(table)
-    out = torch.empty((5, rows * count, 4), dtype=torch.int64, device=p.device)
-    status = torch.empty((count,), dtype=torch.uint8, device=p.device)
-    nw = (C.c_uint32 * len(num_words))(*num_words)
-    check(lib().h2_sinsemilla_trace_from_device(_ptr(p), count, nw, len(num_words), _ptr(q), tab.data_ptr(), _ptr(out), _ptr(status),
-                                                _stream_ptr()), "h2_sinsemilla_trace_from_device")
-    if with_status:
-        return (out.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (out, status)
-    _raise_bottom(status, "sinsemilla.trace_from")
-    return out.cpu().numpy().view(np.uint64) if host else out
+    def q_of(p, count, host):
+        if isinstance(Q, (tuple, list)) and len(Q) == 2 and all(isinstance(c, int) for c in Q):
+            import torch
+            return torch.from_numpy(_q_limbs(Q).view(np.int64)).to(p.device).repeat(count, 1)
+        return _device_points(Q, count, host, "sinsemilla.trace_from")
+    return _trace("trace_from", "h2_sinsemilla_trace_from_device", 1, pieces, num_words, q_of, table, with_status)
 
 
 class CommitDomain:

@@ -137,6 +137,30 @@ def test_trace_reports_bottom_per_message():
         sinsemilla.trace(pieces, [5], q)
 
 
+def test_trace_across_a_chunk_of_scratch():
+    """the trace goes through its scratch in chunks of 2^20 // rows messages: one message more than a chunk of the structure `one`
+    (2 rows), 65 messages over and over, so the rows on both sides of the boundary must be those of a call of their own"""
+    import torch
+    nw = STRUCTURES["one"]
+    rows = sum(nw) + 1
+    per_chunk = (1 << 20) // rows
+    count = per_chunk + 1
+    _, msgs = _trace_messages("one", 65)
+    q = sc.q_of(sc.MERKLE_DOMAIN)
+    p65 = _up(fields.to_limbs([p for m in msgs for p in m], FP, montgomery=False).reshape(65, 1, 4))
+    reps = (count + 64) // 65
+    cols, status = sinsemilla.trace(p65.repeat(reps, 1, 1)[:count].contiguous(), nw, q, with_status=True)
+    want = sinsemilla.trace(p65, nw, q)
+    assert not status.any()
+    for i in (0, per_chunk - 2, per_chunk - 1, per_chunk, count - 1):
+        j = i % 65
+        assert torch.equal(cols[:, rows * i:rows * (i + 1)], want[:, rows * j:rows * (j + 1)]), i
+    # in full, 65 messages at a time: a comparison against the broadcast `want` keeps the test's memory at the columns themselves
+    whole, got, want = count // 65, cols.view(5, count, rows, 4), want.view(5, 65, rows, 4)
+    assert bool((got[:, :65 * whole].view(5, whole, 65, rows, 4) == want[:, None]).all())
+    assert torch.equal(got[:, 65 * whole:], want[:, :count - 65 * whole])
+
+
 def test_trace_rejects_bad_structures():
     q = sc.q_of(sc.MERKLE_DOMAIN)
     for nw in ([26], [0], [25] * 10 + [4], []):
