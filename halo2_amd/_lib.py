@@ -25,6 +25,21 @@ IPA_SWITCH_DEFAULT = 0xFFFFFFFF
 IPA_WRITE_POINT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))     # h2_ipa_write_point_fn
 IPA_SQUEEZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))         # h2_ipa_squeeze_fn
 
+COMMIT_CALLER_DIRECT, COMMIT_CALLER_HOST_RANGE, COMMIT_CALLER_HOST_PIPELINED, COMMIT_CALLER_BATCH_COLUMNS = 1, 2, 3, 4
+COMMIT_CALLER_BATCH_FORK, COMMIT_CALLER_PAIR_TWO_PASS, COMMIT_CALLER_PAIR_SUBDIGIT = 5, 6, 7
+
+
+class CommitPlan(C.Structure):
+    """h2_commit_plan_t: what h2_commit_last_plan fills (every field a uint32_t, in the header's order)"""
+    _fields_ = [(name, C.c_uint32) for name in (
+        "caller", "caller_count", "cols_first", "cols_last", "empty", "lanes", "c", "W", "m", "K", "T", "lane_div",
+        "use_sort2", "s2_lowb", "s2_nh", "s2_side", "s2_s1_scalars", "s2_bins_form", "max_big", "zero_in_sort",
+        "fold9", "wide_reduce", "pair", "joined", "add_only", "fold_only")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 # every symbol include/halo2_mi355x.h declares: name -> (argtypes, restype)
 SIGNATURES = {
     "h2_device_count": ([], C.c_int),
@@ -54,6 +69,7 @@ SIGNATURES = {
     "h2_commit_batch_device": ([C.c_uint64, C.POINTER(vp), C.c_size_t, C.c_size_t, vp, C.POINTER(vp), C.c_int, C.c_int,
                                 C.POINTER(vp), vp], C.c_int),
     "h2_msm_last_path": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_int)], C.c_int),
+    "h2_commit_last_plan": ([vp, C.POINTER(CommitPlan)], C.c_int),
     "h2_msm_batch_device": ([C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_int, C.c_int,
                              C.POINTER(vp), vp], C.c_int),
     "h2_ntt_device": ([C.c_int, vp, C.c_uint, u64p, C.c_int, vp], C.c_int),

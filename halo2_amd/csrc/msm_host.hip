@@ -494,6 +494,12 @@ static int commit_host_pipelined_locked(HostPipe &hp, Bases &b, const uint64_t *
         rc = msm_dispatch(cx, b.curve, a, hp.copy);
     }
     if (rc != H2_OK) return rc;                      // (the caller drains the three streams)
+    {   // h2_commit_last_plan, on stream NULL (this entry point has none): the last range's plan, and that the shared fold followed it
+        msm_hand_last_plan(hp.comp[(chunks - 1) & 1], nullptr, chunks > 1 ? H2_COMMIT_CALLER_HOST_PIPELINED : H2_COMMIT_CALLER_HOST_RANGE, (u32)chunks);
+        MsmContext &c0 = msm_ctx(nullptr);
+        std::lock_guard<std::mutex> cl(c0.mu);
+        c0.last_plan.fold_only = 1;
+    }
     H2_HIP(hipMemcpyAsync(out, d_res, out_kind == H2_OUT_AFFINE ? 64 : 96, hipMemcpyDeviceToHost, hp.copy));
     H2_HIP(hipStreamSynchronize(hp.copy));
     return H2_OK;

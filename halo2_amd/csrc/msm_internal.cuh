@@ -299,9 +299,15 @@ struct MsmContext {
         u32 acc_lanes = 0;     // the largest T of its accumulate launches
         int c = 0;
     } last;
+    // h2_commit_last_plan: what the last call of msm_launch over a registered table decided (msm_launch.hip; caller == 0: none yet).  The entry
+    // points that wrap it in a form of their own (host ranges, column batches, the paired commit) fill the caller fields behind it.
+    h2_commit_plan_t last_plan = {};
 };
 
 MsmContext &msm_ctx(hipStream_t st = nullptr);          // msm_launch.hip
+// h2_commit_last_plan for calls that ran on the library's own streams: the record of `from`'s context, with the caller form filled in, becomes
+// that of `to`'s (each context's mutex taken in turn, never both)
+void msm_hand_last_plan(hipStream_t from, hipStream_t to, u32 caller, u32 count, u32 cols_first = 0, u32 cols_last = 0);
 
 struct MsmArgs {
     const void *d_scalars;       // n_used scalars

@@ -262,6 +262,19 @@ static MsmContext *msm_ctx_find(hipStream_t st) {
     auto it = g_ctxs.find(std::make_pair(dev, st));
     return it == g_ctxs.end() ? nullptr : it->second.get();
 }
+void msm_hand_last_plan(hipStream_t from, hipStream_t to, u32 caller, u32 count, u32 cols_first, u32 cols_last) {
+    h2_commit_plan_t r;
+    {
+        MsmContext &src = msm_ctx(from);
+        std::lock_guard<std::mutex> cl(src.mu);
+        r = src.last_plan;
+    }
+    if (!r.caller) return;
+    r.caller = caller; r.caller_count = count; r.cols_first = cols_first; r.cols_last = cols_last;
+    MsmContext &dst = msm_ctx(to);
+    std::lock_guard<std::mutex> cl(dst.mu);
+    dst.last_plan = r;
+}
 // h2_trim: the per-(device, stream) scratch of this device goes back to the allocator (the device is idle by then)
 void msm_release_workspaces() {
     msm_release_host_pipe();
@@ -770,10 +783,33 @@ template <int FB> static int slice_split_accumulate_fold(MsmContext &cx, const M
                        (const u32 *)(ssums + 32 * (size_t)sh.slices));
     return H2_OK;
 }
+// h2_commit_last_plan: the plan of a call over a registered table as plain integers (the caller holds cx.mu)
+static void record_plan(MsmContext &cx, const MsmPlan &p, u32 lanes) {
+    h2_commit_plan_t &r = cx.last_plan;
+    r = {};
+    r.caller = H2_COMMIT_CALLER_DIRECT;
+    r.caller_count = 1;
+    r.lanes = lanes;
+    r.c = (u32)p.sh.c; r.W = (u32)p.sh.W; r.m = (u32)p.m; r.K = p.K; r.T = p.T; r.lane_div = p.lane_div;
+    r.use_sort2 = p.use_sort2;
+    if (p.use_sort2) { r.s2_lowb = (u32)p.S2.lowb; r.s2_nh = p.S2.nh; r.s2_side = (u32)p.S2.side; r.s2_s1_scalars = p.S2.s1_scalars; }
+    r.s2_bins_form = p.s2_bins_form; r.max_big = p.max_big; r.zero_in_sort = p.zero_in_sort;
+    r.fold9 = p.fold9; r.wide_reduce = p.wide_reduce; r.pair = p.pair; r.joined = p.joined; r.add_only = p.add_only; r.fold_only = p.fold_only;
+}
+static void record_empty(MsmContext &cx, const MsmArgs &a, u32 kind) {
+    h2_commit_plan_t &r = cx.last_plan;
+    r = {};
+    r.caller = H2_COMMIT_CALLER_DIRECT;
+    r.caller_count = 1;
+    r.empty = kind;
+    r.c = (u32)a.c;
+    r.add_only = a.add_into != nullptr;
+}
 // One multiexp, or one phase of it (MsmArgs::phase): 1 = the sort; 2 = accumulate + fold behind a phase-1 sort; 3 = the accumulate; 4 = the fold.
 // The fold-only call (fold_from) is the 8 x 32 fold alone.
 template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a, hipStream_t st) {
     const bool empty = a.n_used + (a.d_extra_scalar ? 1 : 0) == 0;
+    if (empty && a.table && !a.fold_from) record_empty(cx, a, a.add_into ? 2u : 1u);
     if (empty && a.add_into) return H2_OK;           // an empty range adds nothing
     if (empty && !a.fold_from) return msm_empty<FB>(cx, a, st);
     int rc;
@@ -791,6 +827,7 @@ template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a
         cx.last.acc_lanes = p.T;
         cx.last.c = p.sh.c;
     }
+    if (a.table) record_plan(cx, p, lanes);                    // (h2_commit_last_plan)
     if ((rc = msm_reserve(cx, p, st)) != H2_OK) return rc;
     // which stages this call runs (phases >= 2 resume behind a sort the phase-1 call enqueued and timed)
     const bool sorts = !p.fold_only && a.phase < 2, accumulates = !p.fold_only && a.phase != 1 && a.phase != 4, folds = a.phase != 1 && a.phase != 3;
@@ -1081,6 +1118,9 @@ extern "C" int h2_commit_batch_device(h2_bases_t g, const void *const *d_scalars
                 H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
                 H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
             }
+        if (taken && rc == H2_OK)          // h2_commit_last_plan on the caller's stream: the last group's plan and the groups it came in
+            msm_hand_last_plan(forked ? bs.s[(groups - 1) & 1] : user, user, H2_COMMIT_CALLER_BATCH_COLUMNS, (u32)groups,
+                               (u32)(count / groups + (count % groups ? 1 : 0)), (u32)(count / groups));
         if (taken || rc != H2_OK) return rc;
     }
     H2_HIP(hipEventRecord(bs.fork, user));
@@ -1091,6 +1131,7 @@ extern "C" int h2_commit_batch_device(h2_bases_t g, const void *const *d_scalars
         H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
         H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
     }
+    if (rc == H2_OK) msm_hand_last_plan(bs.s[(count - 1) % want], user, H2_COMMIT_CALLER_BATCH_FORK, (u32)count);
     return rc;
 }
 
@@ -1150,6 +1191,15 @@ extern "C" int h2_msm_last_path(void *stream, int *path, int *groups, unsigned *
     if (groups) *groups = cx->last.groups;
     if (acc_lanes) *acc_lanes = cx->last.acc_lanes;
     if (window_bits) *window_bits = cx->last.c;
+    return H2_OK;
+}
+
+extern "C" int h2_commit_last_plan(void *stream, h2_commit_plan_t *out) {
+    MsmContext *cx = out ? msm_ctx_find((hipStream_t)stream) : nullptr;
+    if (!cx) return H2_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(cx->mu);
+    if (!cx->last_plan.caller) return H2_ERR_ARGS;
+    *out = cx->last_plan;
     return H2_OK;
 }
 

@@ -286,6 +286,12 @@ static int pair_subdigit_launch(MsmContext &cx, const Bases &b, const void *d_sc
     // round for three of them (finisher 35 -> 54 us): 9 per lane there
     const u32 lane_div = glv ? 9 : 8;
     const u32 T = (u32)std::min<size_t>(lanes, std::max<size_t>(256, (max_entries / lane_div + 255) / 256 * 256));
+    {                                   // h2_commit_last_plan: this form has no msm_plan
+        h2_commit_plan_t &r = cx.last_plan;
+        r = {};
+        r.caller = H2_COMMIT_CALLER_PAIR_SUBDIGIT; r.caller_count = 1;
+        r.lanes = lanes; r.c = (u32)b.c; r.W = (u32)b.W; r.m = (u32)n; r.K = 1; r.T = T; r.lane_div = lane_div; r.pair = 1;
+    }
     if ((rc = cx.hist.reserve(((size_t)2 * nblk + 1) * kSubKeys * 4)) != H2_OK || (rc = cx.starts.reserve((tb + 2) * 4)) != H2_OK ||
         (rc = cx.entries.reserve(max_entries * 4)) != H2_OK || (rc = cx.seg9.reserve(((size_t)T + tb) * 144)) != H2_OK ||
         (rc = cx.partial.reserve((size_t)nsl * (8 + 1) * 144)) != H2_OK)
@@ -334,6 +340,8 @@ extern "C" int h2_commit_pair_device(h2_bases_t g, const void *d_scalars, size_t
     MsmArgs a{d_scalars, nullptr, b->d_table, nullptr, n, true, b->c, b->stride, (u32)b->n, form, out_kind, d_out};
     a.pair_shift = (int)pair_shift;
     a.pair_n = (u32)(n - 4);
-    return msm_dispatch(cx, b->curve, a, st);
+    rc = msm_dispatch(cx, b->curve, a, st);
+    if (rc == H2_OK) cx.last_plan.caller = H2_COMMIT_CALLER_PAIR_TWO_PASS;       // (h2_commit_last_plan)
+    return rc;
 }
 

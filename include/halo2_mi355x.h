@@ -565,6 +565,45 @@ int h2_profile_read_busy(int slot, double *total_ms, double *busy_ms, uint64_t *
 #define H2_MSM_PATH_GROUPED_LATENCY 4
 #define H2_MSM_PATH_GROUPED_THROUGHPUT 5
 int h2_msm_last_path(void *stream, int *path, int *groups, unsigned *acc_lanes, int *window_bits);
+/* The same for commits over a REGISTERED basis (h2_commit*, h2_commit_range_device, h2_commit_pair_device, h2_commit_batch_device):
+ * what the last one enqueued on `stream` of the current device decided before it launched anything, and which caller form wrapped it.
+ * Host-side bookkeeping: no device work, no synchronisation.  h2_commit (host memory) has no stream: it records on stream NULL, the last
+ * range's plan (add_only = 1) with fold_only / wide_reduce taken from the fold the ranges share.  h2_commit_batch_device records the
+ * last group's (or column's) plan on the caller's `stream` whatever stream of the library ran it.
+ *   caller        H2_COMMIT_CALLER_*:
+ *                 DIRECT          h2_commit_device / h2_commit_range_device (and the library's own commits)
+ *                 HOST_RANGE      h2_commit, one range
+ *                 HOST_PIPELINED  h2_commit, `caller_count` ranges (add_only) and one fold (fold_only)
+ *                 BATCH_COLUMNS   h2_commit_batch_device, `caller_count` column-batched groups of cols_first .. cols_last columns
+ *                 BATCH_FORK      h2_commit_batch_device, one commit per column over `caller_count` columns
+ *                 PAIR_TWO_PASS   h2_commit_pair_device, two bucket slices behind the two-pass sort
+ *                 PAIR_SUBDIGIT   h2_commit_pair_device, the 8-bit sub-digit form (only c, W, m, T, lane_div, pair, lanes are filled)
+ *   empty         1: nothing to sum, the identity was written and nothing else is filled; 2: an empty range of a host commit
+ *   lanes         lanes of the accumulate kernel the device holds at once (T never exceeds it)
+ *   c, W, m       window bits, digits per scalar, scalars incl. the blind;  K columns of the launch set;  T lanes of the accumulate,
+ *                 which aims at lane_div entries per lane
+ *   use_sort2     two-pass sort (s2_lowb low bucket bits per pass-1 bin, s2_nh bins, s2_side: the 16-bit side array, s2_s1_scalars
+ *                 scalars per pass-1 workgroup, s2_bins_form: pass 2 as one launch), else the one-pass sort
+ *   max_big       oversized pass-2 bins the chunked kernels take (0: their launches are skipped);  zero_in_sort: pass 2 clears the buckets
+ *   fold9         the carry-free fold, else the 8 x 32 finisher;  wide_reduce: row / column sums in front of the 8 x 32 fold
+ *   pair, joined, add_only, fold_only: two outputs from one column; the columns' sorted lists form one; a range that stops at its
+ *                 buckets; the fold of buckets summed by such ranges
+ * H2_ERR_ARGS when `out` is NULL or no registered commit has been enqueued on that stream (the query creates nothing). */
+#define H2_COMMIT_CALLER_DIRECT 1
+#define H2_COMMIT_CALLER_HOST_RANGE 2
+#define H2_COMMIT_CALLER_HOST_PIPELINED 3
+#define H2_COMMIT_CALLER_BATCH_COLUMNS 4
+#define H2_COMMIT_CALLER_BATCH_FORK 5
+#define H2_COMMIT_CALLER_PAIR_TWO_PASS 6
+#define H2_COMMIT_CALLER_PAIR_SUBDIGIT 7
+typedef struct h2_commit_plan {
+    uint32_t caller, caller_count, cols_first, cols_last;
+    uint32_t empty, lanes;
+    uint32_t c, W, m, K, T, lane_div;
+    uint32_t use_sort2, s2_lowb, s2_nh, s2_side, s2_s1_scalars, s2_bins_form, max_big, zero_in_sort;
+    uint32_t fold9, wide_reduce, pair, joined, add_only, fold_only;
+} h2_commit_plan_t;
+int h2_commit_last_plan(void *stream, h2_commit_plan_t *out);
 /* ENVIRONMENT.  libhalo2_mi355x.so reads ONE environment variable, the diagnostic H2_TIMELINE below; it never changes a result (it does
  * change the form of a large generic multiexp, see above).  Every A/B switch and sweep knob of the experiments behind DESIGN_LOG.md is compiled out of this library (csrc/common.h,
  * ab_env()) and lives only in the laboratory build of the same sources (`make -C halo2_amd/csrc ab` -> build/ab/libhalo2_mi355x_ab.so)

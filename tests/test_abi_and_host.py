@@ -56,6 +56,9 @@ def test_argument_validation_without_gpu():
     assert lib.h2_ntt(3, p(z4), 2, p(z4[0]), 1) == _lib.H2_ERR_ARGS                  # bad field
     assert lib.h2_bases_free(123456) == _lib.H2_ERR_HANDLE
     assert lib.h2_msm_last_path(None, None, None, None, None) == _lib.H2_ERR_ARGS    # no generic multiexp on that stream yet
+    # (a stream value nothing was ever enqueued on: the query only looks it up, and stream NULL may hold a host commit's record)
+    assert lib.h2_commit_last_plan(C.c_void_p(0x1000), C.byref(_lib.CommitPlan())) == _lib.H2_ERR_ARGS and lib.h2_commit_last_plan(None, None) == _lib.H2_ERR_ARGS
+    assert C.sizeof(_lib.CommitPlan) == 4 * len(_lib.CommitPlan._fields_) == 104      # h2_commit_plan_t: 26 x uint32_t, no padding
     # round-2 entries: the opening argument's policies are host logic; bad handles / curves are refused before any device work
     assert lib.h2_ipa_default_switch_rounds(20, 1) == 6 and lib.h2_ipa_default_switch_rounds(16, 1) == 2 and lib.h2_ipa_default_switch_rounds(24, 1) == 5
     assert lib.h2_ipa_default_switch_rounds(19, 1) == 5 and lib.h2_ipa_default_switch_rounds(21, 1) == 6 and lib.h2_ipa_default_switch_rounds(22, 1) == 5
