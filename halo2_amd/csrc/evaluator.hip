@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(kEvalThreads) ev_run(const u32 *__restrict__ p
             ++depth;
             if (op == EV_POLY) {
                 const int shift = (int)program[++pc];
-                const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| < len
+                const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| <= len
                 top = fe_load(polys[arg] + 8 * j);
             } else if (op == EV_CONST) {
                 top = (basis != 0 || i == 0) ? fe_load(consts + 8 * (size_t)arg) : fe_zero();
@@ -116,7 +116,8 @@ extern "C" int h2_evaluate_device(int field, int basis, const uint32_t *program,
             case EV_POLY: {
                 if (arg >= n_polys || pc + 1 >= n_words || !d_polys[arg]) return H2_ERR_ARGS;
                 const long long shift = (int)program[++pc];
-                if (shift <= -(long long)len || shift >= (long long)len) return H2_ERR_ARGS;
+                // |shift| == len is the identity; beyond it the reference panics (poly.rs:251, :256: assert!(k <= self.len()))
+                if (shift < -(long long)len || shift > (long long)len) return H2_ERR_ARGS;
                 if (basis == 0 && shift != 0) return H2_ERR_ARGS;      // "Can't rotate polynomials in the standard basis" (:519)
                 ++depth;
                 break;

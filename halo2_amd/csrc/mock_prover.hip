@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ p
                     ++depth;
                     if (op == MP_POLY) {
                         const int shift = (int)programs[++pc];
-                        const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| < len
+                        const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| <= len
                         top = fe_load(polys[arg] + 8 * j);
                         ptop = is_advice[arg] && j >= usable;                                             // dev.rs:529-533
                     } else {
@@ -269,7 +269,7 @@ bool program_ok(const uint32_t *prog, size_t begin, size_t end, size_t n_consts,
             case MP_POLY: {
                 if (arg >= n_polys || pc + 1 >= end || !d_polys[arg]) return false;
                 const long long shift = (int)prog[++pc];
-                if (shift <= -(long long)len || shift >= (long long)len) return false;
+                if (shift < -(long long)len || shift > (long long)len) return false;      // as h2_evaluate_device: |shift| <= len
                 ++depth;
                 break;
             }

@@ -151,6 +151,7 @@ class Evaluator:
             if self.basis == COEFF and leaf.rotation != 0:
                 raise ValueError("Can't rotate polynomials in the standard basis")          # evaluator.rs:519
             step = 1 if self.basis != EXTENDED else 1 << (domain.extended_k - domain.k)
+            # h2_evaluate_device takes |shift| <= len (a rotation by the whole length is the identity, as in the reference) and refuses more
             words += [_POLY | leaf.index << 8, (leaf.rotation * step) & 0xFFFFFFFF]
         elif k == "constant":
             words.append(_CONST | const_index(ast.args[0]) << 8)

@@ -437,7 +437,9 @@ int h2_selector_combine_device(int field, const uint32_t *bits, const uint32_t *
  * polynomials, evaluated element by element in a single kernel.  The tree arrives flattened in post-order as 32-bit
  * words `op | operand << 8`:
  *   H2_EV_POLY   operand = polynomial index; the NEXT word is the signed element shift (rotation * 1 for the Lagrange
- *                basis, * 2^(extended_k - k) for the extended basis; must be 0 in the coefficient basis, evaluator.rs:519)
+ *                basis, * 2^(extended_k - k) for the extended basis; must be 0 in the coefficient basis, evaluator.rs:519).
+ *                |shift| <= 2^log_len: the read wraps modulo the length, a shift of exactly the length is the identity as in
+ *                the reference (Polynomial::get_chunk_of_rotated_helper asserts k <= len), a larger one is H2_ERR_ARGS
  *   H2_EV_CONST  operand = constant index (Ast::ConstantTerm)      H2_EV_LINEAR  operand = constant index (Ast::LinearTerm:
  *                value consts[c] * omega^i; the caller folds ZETA into the constant for the extended basis, :590-600)
  *   H2_EV_ADD, H2_EV_MUL (element-wise; Lagrange and extended bases, as in the reference: evaluator.rs:370-418), H2_EV_SCALE operand = constant index,
@@ -479,7 +481,8 @@ int h2_permute_expression_pair_device(int field, const void *d_input, const void
  * with the poison tracking of dev.rs:104-156.  poly_is_advice[i] != 0 marks a registered vector as an advice column: its cell is
  * Poison where the row it is read at (after rotation, modulo the length) is >= usable_rows.  Negation (a SCALE) and ADD propagate
  * poison; MUL and SCALE turn Poison into Real(0) when the other factor is Real(0) / the constant 0.  H2_EV_MULADD b is
- * SCALE b of the accumulator, then ADD.  H2_EV_LINEAR is refused (a lowered gate has no such term).
+ * SCALE b of the accumulator, then ADD.  H2_EV_LINEAR is refused (a lowered gate has no such term); everything else is validated as
+ * h2_evaluate_device validates a Lagrange-basis program (|shift| <= 2^log_len, stack depth <= 9).
  *   d_nonzero_bits, d_poison_bits: n_programs planes each; bit set where the program gives Real(x != 0) / Poison
  *   d_counts: 2 * n_programs uint32: set bits of program p's non-zero plane at [2p], of its poison plane at [2p + 1]
  *   d_values: null, or n_programs device vectors of 2^log_len elements that receive program p's value (Montgomery; 0 where poisoned) */

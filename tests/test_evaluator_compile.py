@@ -1,6 +1,6 @@
 """CPU-only: the host half of `poly::Evaluator` (halo2_amd/evaluator.py) -- the compiler from `Ast` trees to the post-order
-bytecode `h2_evaluate_device` runs.  A reference interpreter of that bytecode on Python integers (the documented semantics of
-the H2_EV_* opcodes, include/halo2_mi355x.h) is run on the compiled programs of random trees and compared with the oracle's
+bytecode `h2_evaluate_device` runs.  A reference interpreter of that bytecode on Python integers (tests/evaluator_model.py: the documented
+semantics of the H2_EV_* opcodes, include/halo2_mi355x.h) is run on the compiled programs of random trees and compared with the oracle's
 tree-walking restatement of `Evaluator::evaluate` (oracle/evaluator.py); the stack depth the compiler promises is checked on
 the way.  The kernel itself is compared with the same oracle in the GPU suite."""
 import random
@@ -10,40 +10,9 @@ import pytest
 
 import halo2_amd as h
 from halo2_amd import evaluator as hev
+from evaluator_model import interpret as _interpret
 from halo2_amd.evaluator import COEFF, EXTENDED, LAGRANGE, Ast, AstLeaf, Evaluator
 from oracle import evaluator as oev
-
-
-def _interpret(words, consts, polys, basis, n, m, omega):
-    """The bytecode's semantics on integers; returns (values, maximum stack depth)."""
-    stack, depth, i = [], 0, 0
-    while i < len(words):
-        op, arg = words[i] & 0xFF, words[i] >> 8
-        i += 1
-        if op == hev._POLY:
-            shift = words[i] if words[i] < (1 << 31) else words[i] - (1 << 32)
-            i += 1
-            stack.append([polys[arg][(r + shift) % n] for r in range(n)])
-        elif op == hev._CONST:
-            stack.append([consts[arg] if (basis != COEFF or r == 0) else 0 for r in range(n)])
-        elif op == hev._LINEAR:
-            if basis == COEFF:
-                stack.append([consts[arg] if r == 1 else 0 for r in range(n)])
-            else:
-                stack.append([consts[arg] * pow(omega, r, m) % m for r in range(n)])
-        elif op in (hev._ADD, hev._MUL):
-            b, a = stack.pop(), stack.pop()
-            stack.append([(x + y) % m if op == hev._ADD else x * y % m for x, y in zip(a, b)])
-        elif op == hev._SCALE:
-            stack.append([x * consts[arg] % m for x in stack.pop()])
-        elif op == hev._MULADD:
-            term, acc = stack.pop(), stack.pop()
-            stack.append([(x * consts[arg] + y) % m for x, y in zip(acc, term)])
-        else:
-            raise AssertionError(f"unknown opcode {op}")
-        depth = max(depth, len(stack))
-    assert len(stack) == 1
-    return stack[0], depth
 
 
 def _random_tree(rnd, ev, n_polys, basis, m, depth):

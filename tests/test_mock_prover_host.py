@@ -83,9 +83,10 @@ def test_entry_points_refuse_bad_arguments():
     assert _check_expressions(polys=[FAKE, None]) == E                                   # a registered polynomial the program reads is null
     assert _check_expressions(values=[None]) == E
     assert _check_expressions(offsets=[0, 0]) == E and _check_expressions(offsets=[0, 4, 4], n_programs=2) == E
-    # programs h2_evaluate_device refuses too: operand out of range, stack underflow, leftovers, a rotation as large as the vector,
-    # an unknown opcode, a stack deeper than nine -- and the LINEAR node, which lowered expressions do not have
-    for bad in ([1 | 2 << 8, 0], [2 | 1 << 8], [1, 0, 4], [1, 0, 1, 0], [1, 16], [1, (-16) & 0xFFFFFFFF], [9], [1], [3 | 0 << 8],
+    # programs h2_evaluate_device refuses too: operand out of range, stack underflow, leftovers, a rotation larger than the vector (one of
+    # exactly its length is the identity, as in the reference), an unknown opcode, a stack deeper than nine -- and the LINEAR node, which
+    # lowered expressions do not have
+    for bad in ([1 | 2 << 8, 0], [2 | 1 << 8], [1, 0, 4], [1, 0, 1, 0], [1, 17], [1, (-17) & 0xFFFFFFFF], [9], [1], [3 | 0 << 8],
                 [1, 0, 6 | 1 << 8], [1, 0, 1, 0, 7 | 1 << 8], [2] * 10 + [4] * 9):
         assert _check_expressions(prog=bad, offsets=[0, len(bad)]) == E, bad
     assert _check_expressions(prog=[1, 0, 1, 0, 4, 9], offsets=[0, 5, 6], n_programs=2) == E     # the second of two programs is bad
@@ -106,6 +107,8 @@ def test_entry_points_fail_loudly_without_a_device():
         pytest.skip("a GPU is present")
     assert _check_expressions() == _lib.H2_ERR_NODEV
     assert _check_expressions(values=[FAKE]) == _lib.H2_ERR_NODEV
+    for whole in ([1, 16], [1, (-16) & 0xFFFFFFFF]):                                      # |shift| == len passes the validation
+        assert _check_expressions(prog=whole, offsets=[0, 2]) == _lib.H2_ERR_NODEV
     assert _check_lookup() == _lib.H2_ERR_NODEV
     assert _check_permutation() == _lib.H2_ERR_NODEV
 
