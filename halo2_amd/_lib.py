@@ -40,6 +40,16 @@ class CommitPlan(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class DebugCounters(C.Structure):
+    """h2_debug_counters_t: what h2_debug_counters fills (every field a uint64_t, in the header's order)"""
+    _fields_ = [(name, C.c_uint64) for name in (
+        "devbuf_epoch", "host_msm_plain", "host_msm_captured", "host_msm_replayed", "host_msm_graphs_dropped",
+        "ipa_table_registered", "ipa_table_refilled", "ipa_table_freed", "twiddle_built", "twiddle_hits")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 # every symbol include/halo2_mi355x.h declares: name -> (argtypes, restype)
 SIGNATURES = {
     "h2_device_count": ([], C.c_int),
@@ -70,6 +80,7 @@ SIGNATURES = {
                                 C.POINTER(vp), vp], C.c_int),
     "h2_msm_last_path": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_int)], C.c_int),
     "h2_commit_last_plan": ([vp, C.POINTER(CommitPlan)], C.c_int),
+    "h2_debug_counters": ([C.POINTER(DebugCounters)], C.c_int),
     "h2_msm_batch_device": ([C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_int, C.c_int,
                              C.POINTER(vp), vp], C.c_int),
     "h2_ntt_device": ([C.c_int, vp, C.c_uint, u64p, C.c_int, vp], C.c_int),

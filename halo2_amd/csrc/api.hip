@@ -50,6 +50,10 @@ static std::atomic<unsigned long> g_devbuf_epoch{0};
 unsigned long devbuf_epoch() { return g_devbuf_epoch.load(std::memory_order_acquire); }
 void devbuf_epoch_bump() { g_devbuf_epoch.fetch_add(1, std::memory_order_acq_rel); }
 
+// h2_debug_counters: one relaxed increment where a unit decides what it does with state it kept (no lock, nothing read back by the library)
+static std::atomic<uint64_t> g_debug_counts[DBG_COUNTERS];
+void debug_count(DebugCounter which) { g_debug_counts[which].fetch_add(1, std::memory_order_relaxed); }
+
 // ---- event profiler ---------------------------------------------------------------------------
 struct ProfState {
     std::mutex mu;
@@ -183,6 +187,22 @@ extern "C" int h2_init(int device) {
 }
 
 extern "C" const char *h2_last_error(void) { return h2::g_err; }
+
+extern "C" int h2_debug_counters(h2_debug_counters_t *out) {
+    if (!out) return H2_ERR_ARGS;
+    auto get = [](h2::DebugCounter which) { return h2::g_debug_counts[which].load(std::memory_order_relaxed); };
+    out->devbuf_epoch = h2::devbuf_epoch();
+    out->host_msm_plain = get(h2::DBG_HOST_MSM_PLAIN);
+    out->host_msm_captured = get(h2::DBG_HOST_MSM_CAPTURED);
+    out->host_msm_replayed = get(h2::DBG_HOST_MSM_REPLAYED);
+    out->host_msm_graphs_dropped = get(h2::DBG_HOST_MSM_GRAPHS_DROPPED);
+    out->ipa_table_registered = get(h2::DBG_IPA_TABLE_REGISTERED);
+    out->ipa_table_refilled = get(h2::DBG_IPA_TABLE_REFILLED);
+    out->ipa_table_freed = get(h2::DBG_IPA_TABLE_FREED);
+    out->twiddle_built = get(h2::DBG_TWIDDLE_BUILT);
+    out->twiddle_hits = get(h2::DBG_TWIDDLE_HITS);
+    return H2_OK;
+}
 
 extern "C" int h2_trim(void) {
     int rc = h2::ensure_device();

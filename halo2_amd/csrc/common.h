@@ -50,6 +50,12 @@ inline const char *ab_env(const char *) { return nullptr; }
 // only while the count it was captured under still stands (msm.hip, the range pipeline of h2_msm)
 unsigned long devbuf_epoch();
 void devbuf_epoch_bump();
+// h2_debug_counters (api.hip): process-wide monotone counts of what the units do with the state they keep between calls
+enum DebugCounter {
+    DBG_HOST_MSM_PLAIN, DBG_HOST_MSM_CAPTURED, DBG_HOST_MSM_REPLAYED, DBG_HOST_MSM_GRAPHS_DROPPED,
+    DBG_IPA_TABLE_REGISTERED, DBG_IPA_TABLE_REFILLED, DBG_IPA_TABLE_FREED, DBG_TWIDDLE_BUILT, DBG_TWIDDLE_HITS, DBG_COUNTERS
+};
+void debug_count(DebugCounter which);
 struct DevBuf {
     void *ptr = nullptr;
     size_t cap = 0;

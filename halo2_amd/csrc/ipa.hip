@@ -47,7 +47,10 @@ struct IpaContext {
         std::unique_lock<std::mutex> rl(rounds_mu, std::try_to_lock);
         if (!rl.owns_lock()) return;
         for (DevBuf *b : {&rounds, &gprime, &rstab}) b->release();
-        if (gp_handle) (void)h2_bases_free(gp_handle);
+        if (gp_handle) {
+            (void)h2_bases_free(gp_handle);
+            debug_count(DBG_IPA_TABLE_FREED);
+        }
         gp_handle = 0;
         if (rounds_host) (void)hipHostFree(rounds_host);
         rounds_host = nullptr;
@@ -362,9 +365,11 @@ static int collapsed_table(IpaContext &cx, int curve, unsigned k, unsigned J, h2
     if (cx.gp_handle && (!keep_gp_table() || cx.gp_curve != curve || cx.gp_n != nj + tail)) {
         (void)h2_bases_free(cx.gp_handle);
         cx.gp_handle = 0;
+        debug_count(DBG_IPA_TABLE_FREED);
     }
     if (cx.gp_handle) {
         if ((rc = bases_refill_device(cx.gp_handle, d_g, nj + tail, H2_FORM_MONTGOMERY)) != H2_OK) return rc;
+        debug_count(DBG_IPA_TABLE_REFILLED);
     } else {
         // rounds over a small table are sub-digit paired commits, which read an ENDOMORPHISM table as well: 8 x 16 doublings in its chain instead
         // of 15 x 16 -- the chain is what the table costs (0.77 ms of 240 dependent doublings at 2^14 points).  H2_IPA_GLV_TABLE=0: the plain table (A/B).
@@ -373,6 +378,7 @@ static int collapsed_table(IpaContext &cx, int curve, unsigned k, unsigned J, h2
         if ((rc = bases_register_device_internal(curve, d_g, nj + tail, H2_FORM_MONTGOMERY, &cx.gp_handle, glv)) != H2_OK) return rc;
         cx.gp_curve = curve;
         cx.gp_n = nj + tail;
+        debug_count(DBG_IPA_TABLE_REGISTERED);
     }
     *hj = cx.gp_handle;
     return H2_OK;
@@ -385,6 +391,7 @@ static void collapsed_table_retain(IpaContext &cx) {
     if (keep_gp_table() && cx.gp_n <= ((size_t)1 << 17) + 4) return;
     (void)h2_bases_free(cx.gp_handle);
     cx.gp_handle = 0;
+    debug_count(DBG_IPA_TABLE_FREED);
 }
 
 // The round loop of `commitment::create_proof` (poly/commitment/prover.rs:104-142) as ONE call: per round the inner products,

@@ -38,7 +38,8 @@ struct HostMsmPipe {
     int warm = 0;                                       // calls seen with `shape`: the first runs plain launches (allocations, attributes), the second captures
     hipGraphExec_t g_sort = nullptr, g_final = nullptr;
     std::vector<hipGraphExec_t> g_acc, g_fold;
-    void drop_graphs() {
+    void drop_graphs(bool usable = true) {      // usable: a set that calls could replay (h2_debug_counters), not a capture given up half-way
+        if (usable && g_sort) debug_count(DBG_HOST_MSM_GRAPHS_DROPPED);
         if (g_sort) (void)hipGraphExecDestroy(g_sort);
         if (g_final) (void)hipGraphExecDestroy(g_final);
         for (auto g : g_acc) if (g) (void)hipGraphExecDestroy(g);
@@ -178,6 +179,7 @@ static int msm_host_chunked(MsmContext &cx, int curve, const uint64_t *scalars, 
         hp.warm = 0;
     }
     const bool may_graph = graphs_on && !prof_enabled() && !timeline_on();
+    const bool had_graphs = hp.g_sort != nullptr;
     if (may_graph && hp.warm >= 1 && !hp.g_sort) {
         // second call with this shape: every workspace exists, every attribute is set -- capture the launch sequences (nothing executes)
         hp.g_acc.assign(Q, nullptr);
@@ -189,7 +191,7 @@ static int msm_host_chunked(MsmContext &cx, int curve, const uint64_t *scalars, 
         }
         if (rc == H2_OK) rc = capture_graph(hp.light, &hp.g_final, final_step);
         if (rc != H2_OK || devbuf_epoch() != want.epoch) {     // (a capture that had to allocate is not replayable: stay with plain launches)
-            hp.drop_graphs();
+            hp.drop_graphs(false);
             hp.shape.epoch = devbuf_epoch();
             if (rc != H2_OK) return rc;
         }
@@ -298,6 +300,8 @@ static int msm_host_chunked(MsmContext &cx, int curve, const uint64_t *scalars, 
         return rc;
     }
     hp.warm++;
+    debug_count(replay ? DBG_HOST_MSM_REPLAYED : DBG_HOST_MSM_PLAIN);
+    if (replay && !had_graphs) debug_count(DBG_HOST_MSM_CAPTURED);
     return H2_OK;
 }
 namespace h2 {

@@ -94,6 +94,7 @@ static int get_twiddles(NttContext &cx, int field, int L, const u64 omega_m[4], 
         out = it->second;
         // order this stream behind the build
         H2_HIP(hipStreamWaitEvent(st, out->ready, 0));
+        debug_count(DBG_TWIDDLE_HITS);
         return H2_OK;
     }
     const size_t count = tw_count(L);
@@ -119,6 +120,7 @@ static int get_twiddles(NttContext &cx, int field, int L, const u64 omega_m[4], 
     H2_HIP(hipEventRecord(ent->ready, st));
     cx.cache[key] = ent;
     cx.lru.push_front(key);
+    debug_count(DBG_TWIDDLE_BUILT);
     cx.cache_bytes += tw_bytes(L, flavour);
     while (cx.cache_bytes > kTwCacheBytes && cx.lru.size() > 1) {
         TwKey old = cx.lru.back();

@@ -607,6 +607,26 @@ typedef struct h2_commit_plan {
     uint32_t fold9, wide_reduce, pair, joined, add_only, fold_only;
 } h2_commit_plan_t;
 int h2_commit_last_plan(void *stream, h2_commit_plan_t *out);
+/* What the library did with the state it keeps BETWEEN calls, as process-wide counters that only rise (every device and stream together).
+ * Host-side bookkeeping: no device work, no synchronisation, no effect on any result; a test reads them before and after a call to prove
+ * which arm the call took.
+ *   devbuf_epoch             (re)allocations and releases of the grow-only workspaces of every unit (what a captured graph is keyed by)
+ *   host_msm_plain           h2_msm calls through the range pipeline (from 2^19 host points) that enqueued plain launches
+ *   host_msm_captured        ... that captured the launch graphs of their shape (such a call replays them as well)
+ *   host_msm_replayed        ... that replayed captured graphs
+ *   host_msm_graphs_dropped  sets of captured graphs destroyed that a call could have replayed: another shape, a moved buffer, h2_trim
+ *   ipa_table_registered     the opening argument's table of collapsed generators: registered anew,
+ *   ipa_table_refilled       refilled in place (curve and size repeat on the stream),
+ *   ipa_table_freed          freed (another curve or size, above 2^17 points at the end of the call, h2_trim)
+ *   twiddle_built            twiddle tables built into the NTT's cache (the curve-point FFT shares it); twiddle_hits: look-ups it answered
+ * H2_ERR_ARGS when `out` is NULL. */
+typedef struct h2_debug_counters {
+    uint64_t devbuf_epoch;
+    uint64_t host_msm_plain, host_msm_captured, host_msm_replayed, host_msm_graphs_dropped;
+    uint64_t ipa_table_registered, ipa_table_refilled, ipa_table_freed;
+    uint64_t twiddle_built, twiddle_hits;
+} h2_debug_counters_t;
+int h2_debug_counters(h2_debug_counters_t *out);
 /* ENVIRONMENT.  libhalo2_mi355x.so reads ONE environment variable, the diagnostic H2_TIMELINE below; it never changes a result (it does
  * change the form of a large generic multiexp, see above).  Every A/B switch and sweep knob of the experiments behind DESIGN_LOG.md is compiled out of this library (csrc/common.h,
  * ab_env()) and lives only in the laboratory build of the same sources (`make -C halo2_amd/csrc ab` -> build/ab/libhalo2_mi355x_ab.so)

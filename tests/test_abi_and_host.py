@@ -59,6 +59,15 @@ def test_argument_validation_without_gpu():
     # (a stream value nothing was ever enqueued on: the query only looks it up, and stream NULL may hold a host commit's record)
     assert lib.h2_commit_last_plan(C.c_void_p(0x1000), C.byref(_lib.CommitPlan())) == _lib.H2_ERR_ARGS and lib.h2_commit_last_plan(None, None) == _lib.H2_ERR_ARGS
     assert C.sizeof(_lib.CommitPlan) == 4 * len(_lib.CommitPlan._fields_) == 104      # h2_commit_plan_t: 26 x uint32_t, no padding
+    # h2_debug_counters: host bookkeeping that answers without a device; ten uint64_t in the header's order, nothing counted yet by an argument check
+    assert lib.h2_debug_counters(None) == _lib.H2_ERR_ARGS
+    counters = _lib.DebugCounters()
+    assert lib.h2_debug_counters(C.byref(counters)) == _lib.H2_OK
+    assert C.sizeof(_lib.DebugCounters) == 8 * len(_lib.DebugCounters._fields_) == 80
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "halo2_mi355x.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct h2_debug_counters \{(.*?)\} h2_debug_counters_t;", header, flags=re.S).group(1)
+    assert re.findall(r"\b(?!uint64_t\b)([a-z_0-9]+)\s*[,;]", body) == [name for name, _ in _lib.DebugCounters._fields_]
+    assert set(re.findall(r"\b([a-z]\w*)\b", re.sub(r"\b[a-z_0-9]+\s*[,;]", "", body))) == {"uint64_t"}
     # round-2 entries: the opening argument's policies are host logic; bad handles / curves are refused before any device work
     assert lib.h2_ipa_default_switch_rounds(20, 1) == 6 and lib.h2_ipa_default_switch_rounds(16, 1) == 2 and lib.h2_ipa_default_switch_rounds(24, 1) == 5
     assert lib.h2_ipa_default_switch_rounds(19, 1) == 5 and lib.h2_ipa_default_switch_rounds(21, 1) == 6 and lib.h2_ipa_default_switch_rounds(22, 1) == 5
