@@ -40,161 +40,6 @@ namespace h2 {
 
 namespace {
 
-constexpr u32 kLaneDiv = 16;      // entries per lane the accumulates aim at (full-size columns)
-
-struct Group {
-    u32 w0 = 0, ns = 0;     // window slices [w0, w0 + ns)
-    u32 tb = 0;             // its buckets: ns * NB
-    GroupSort gs;           // pass 1
-    Sort2 p2;               // what the pass-2 kernels read (lowb, lb, nh; no side array)
-    size_t cap = 0;         // pass-2 stage of a bin's workgroup, in entries
-    size_t emax = 0;        // most entries it can hold: ns * digit columns
-    size_t plan_words = 0;
-    u32 B1 = 0;             // pass-1 workgroups
-    u32 T = 0;              // lanes of its accumulate
-    size_t ent_off = 0;     // its sorted list inside cx.entries (entries)
-    size_t starts_off = 0;  // its boundary array inside cx.starts (words): tb + 2 of them
-    size_t bucket_off = 0;  // its first bucket slot
-};
-
-// Pass-1 bins such that an average bin is ~16 K entries (what a pass-2 workgroup stages in LDS with room to spare), the low key bits
-// riding in the tagged entry above the column index.
-bool group_geometry(u32 cols, u32 nb, Group &g) {
-    int lb = 0;
-    while (((u64)(cols - 1) >> lb) != 0) ++lb;
-    g.tb = g.ns * nb;
-    g.emax = (size_t)g.ns * cols;
-    for (int lowb = 12; lowb >= 1; --lowb) {
-        if (lowb + lb > 31) continue;
-        const size_t nbk = (size_t)1 << lowb;
-        const u32 nh = (u32)(((size_t)g.tb + nbk - 1) >> lowb);
-        if (nh > 4096) break;
-        const size_t avg = g.emax / nh;
-        const size_t cap_max = nbk * 8 + 64 < kLdsCap ? (kLdsCap - nbk * 8) / 4 : 0;
-        const size_t cap = std::min(cap_max, std::max<size_t>(4096, avg * 5 / 4 + 1024));
-        if (avg > 20000 || avg > cap * 9 / 10) continue;
-        // digit columns per pass-1 workgroup: 4096 (two workgroups per CU) -- 8192 where that still leaves >= 512 workgroups: every workgroup
-        // writes and re-reads a histogram row of nh words and copies its entries out in runs of S ns / nh, so large problems want large S
-        u32 S = 4096;
-        while (S > 512 && ((size_t)nh * 3 + 1 + (size_t)S * g.ns) * 4 > kLdsCap / 2) S /= 2;
-        if (S == 4096 && cols / 8192 >= 512 && ((size_t)nh * 3 + 1 + (size_t)8192 * g.ns) * 4 <= kLdsCap) S = 8192;
-        if (((size_t)nh * 3 + 1 + (size_t)S * g.ns) * 4 > kLdsCap) continue;
-        memset(&g.gs, 0, sizeof g.gs);
-        g.gs.cols = cols;
-        g.gs.row = (cols + 7) & ~7u;
-        g.gs.w0 = g.w0;
-        g.gs.ns = g.ns;
-        g.gs.nb = nb;
-        g.gs.lowb = lowb;
-        g.gs.lb = lb;
-        g.gs.nh = nh;
-        g.gs.S = S;
-        g.gs.run_lanes = 16;
-        memset(&g.p2, 0, sizeof g.p2);
-        g.p2.lowb = lowb;
-        g.p2.lb = lb;
-        g.p2.nh = nh;
-        g.p2.nb = nb;
-        g.p2.pair_shift = -1;
-        g.p2.extra_col = 0xFFFFFFFFu;
-        g.cap = cap;
-        g.B1 = (cols + S - 1) / S;
-        g.plan_words = ((size_t)nh * 2 + 1 + 64 + (((size_t)kMaxBig * (kBigChunks + 1)) << lowb) + 3) & ~(size_t)3;
-        return true;
-    }
-    return false;
-}
-
-// What one grouped call decides before it reserves or enqueues anything: the form, the groups and the sizes its reservations follow from.
-struct GroupedPlan {
-    bool throughput;        // one group on the caller's stream (another stream's generic multiexp is in flight), else the latency form
-    bool lds_fence;         // the chain links are fenced onto CUs without an accumulate workgroup by LDS requests
-    int G;
-    Group grp[MsmContext::kMaxGroups];
-    size_t head_slots, hist_words, tagged_words, plan_words;
-    u32 wideS, wideNR;      // the bucket matrix of a slice (fold9_rowcol / fold9_planes)
-};
-
-// H2_ERR_BATCH_SHAPE when the shape is not the grouped form's own (the header has the limits).  The laboratory build's switches of the grouped
-// form are read here, once (the shipped library: every one at its default).
-int grouped_plan(const MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, GroupedPlan &gp) {
-    static const bool on = [] { const char *e = ab_env("H2_GENERIC_GROUPED"); return !(e && atoi(e) == 0); }();       // 0: round 5's slice split (A/B)
-    static const int form_env = [] { const char *e = ab_env("H2_GG_FORM"); return e ? atoi(e) : 0; }();        // 1: latency form always, 2: throughput form always (A/B)
-    static const int spare_env = [] { const char *e = ab_env("H2_GG_SPARE"); return e ? atoi(e) : -1; }();     // CUs left without an accumulate workgroup
-    static const std::vector<int> env_sizes = [] {                                                             // H2_GENERIC_GROUPS="a,b,c"
-        std::vector<int> v;
-        if (const char *e = ab_env("H2_GENERIC_GROUPS"))
-            for (const char *p = e; *p;) {
-                v.push_back(atoi(p));
-                while (*p && *p != ',') ++p;
-                if (*p == ',') ++p;
-            }
-        return v;
-    }();
-    // (no upper bound on scalars_n here: group_geometry below declines every size beyond the layouts' limits, see the header)
-    if (!on || scalars_n < ((size_t)1 << 18) + 1 || sh.c < 8 || sh.c > kMaxC || sh.W < 3 || sh.W > 16 || sh.NB < 128) return H2_ERR_BATCH_SHAPE;
-    const u32 cols = 2 * (u32)scalars_n, W = (u32)sh.W, NB = sh.NB;
-    // (from 2^22 points on the whole sort in front of a single group costs more than the grouping loses: 837 against 900 M scalar-mults/s on three streams)
-    gp.throughput = form_env == 2 || (form_env != 1 && scalars_n < ((size_t)1 << 22) && msm_other_generic_in_flight(&cx));
-    // ---- the groups, upper slices first (H2_GENERIC_GROUPS="a,b,c": laboratory build only)
-    int sizes[MsmContext::kMaxGroups] = {0, 0, 0, 0}, sum = 0;
-    int &G = gp.G = 0;
-    for (int v : env_sizes) sum += v;
-    if (!env_sizes.empty() && env_sizes.size() <= (size_t)MsmContext::kMaxGroups && sum == (int)W && *std::min_element(env_sizes.begin(), env_sizes.end()) >= 1) {
-        for (int v : env_sizes) sizes[G++] = v;
-    } else if (gp.throughput) {
-        // independent calls on other streams are in flight: their sorts and folds hide beside this call's accumulate anyway, every accumulate
-        // launch that starts beside them runs ragged, and side streams of several calls would share hardware queues: ONE group, everything on
-        // the caller's stream (2^20: 1.16-1.22 ms per call on three streams against 1.26-1.46 for any grouping; 2^22: 862 M/s)
-        sizes[0] = (int)W;
-        G = 1;
-    } else {
-        // a call alone: 5 + 2 + 2 of nine slices -- the first group's sort is all that stands in front of the first addition, the last
-        // (smallest) group's fold all that stands behind the last
-        const int last = std::max(1, (int)W * 2 / 9), mid = last, top = (int)W - last - mid;
-        sizes[0] = top; sizes[1] = mid; sizes[2] = last;
-        G = 3;
-    }
-    Group *grp = gp.grp;
-    u32 hi = W;
-    size_t ent = 0, sts = 0, bkt = 0;
-    for (int g = 0; g < G; ++g) {
-        grp[g].ns = (u32)sizes[g];
-        grp[g].w0 = hi - (u32)sizes[g];
-        hi = grp[g].w0;
-        if (!group_geometry(cols, NB, grp[g])) return H2_ERR_BATCH_SHAPE;
-        grp[g].ent_off = ent;
-        grp[g].starts_off = sts;
-        grp[g].bucket_off = bkt;
-        ent += grp[g].emax;
-        sts += (size_t)grp[g].tb + 2;
-        bkt += grp[g].tb;
-    }
-    if (ent >= ((size_t)1 << 31)) return H2_ERR_BATCH_SHAPE;
-    const double fraction = a.lane_fraction > 0.0 ? a.lane_fraction : g_lane_fraction.load();
-    // The latency form leaves one CU per XCD without an accumulate workgroup and FENCES the chain kernels onto them: every accumulate workgroup asks
-    // for 64 KiB of LDS it never touches, every link of the Horner chain for 100 KiB -- so a chain wave (one wave at raised priority issuing
-    // dependent multiply-adds back to back: it takes ~90 % of its SIMD) can only land on a CU that holds no accumulate workgroup, instead of
-    // starving two accumulate waves for its whole 130-180 us while every other lane of the launch waits for them (measured: the second group's
-    // accumulate 494 -> 429 us; profiles/r06_generic_grouped.txt).  H2_GG_SPARE: laboratory build only.
-    gp.lds_fence = !gp.throughput && G > 1;
-    const u32 spare = spare_env >= 0 ? (u32)spare_env : (gp.lds_fence ? std::max(1u, lanes / 512u / 32u) : 0u);      // one CU in 32: 8 of an MI355X's 256 (one per XCD)
-    // (signed: a small fraction -- or few CUs -- must not wrap below the spare CUs' share and hand the accumulate every lane there is)
-    const long long want_lanes = (long long)((u32)(lanes * fraction) / 512u * 512u) - 512LL * std::min(spare, 64u);
-    const u32 usable = (u32)std::max<long long>(512, want_lanes);
-    gp.head_slots = gp.hist_words = gp.tagged_words = gp.plan_words = 0;
-    for (int g = 0; g < G; ++g) {
-        grp[g].T = (u32)std::min<size_t>(usable, std::max<size_t>(512, (grp[g].emax / kLaneDiv + 511) / 512 * 512));
-        gp.head_slots += grp[g].T;
-        gp.hist_words = std::max(gp.hist_words, (size_t)grp[g].B1 * grp[g].gs.nh);
-        gp.tagged_words = std::max(gp.tagged_words, grp[g].emax);
-        gp.plan_words = std::max(gp.plan_words, grp[g].plan_words);
-    }
-    gp.wideS = 1u << ((sh.c - 1) / 2);
-    gp.wideNR = NB / gp.wideS;
-    return H2_OK;
-}
-
 // every workspace, attribute, stream and event of the call before anything is enqueued (a reservation that grows frees and synchronises)
 int grouped_reserve(MsmContext &cx, const GroupedPlan &gp, u32 m, u32 W, u32 NB, hipStream_t st) {
     const int G = gp.G;
@@ -244,9 +89,14 @@ int grouped_reserve(MsmContext &cx, const GroupedPlan &gp, u32 m, u32 W, u32 NB,
 
 template <int FB, int FS>
 int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, size_t scalars_n, u32 lanes, hipStream_t st) {
+    // the plan (msm_plan.h).  Whether another stream's generic multiexp is in flight is asked for the calls whose form it decides, and for no
+    // other: the query takes host time and clears the pending flag of every context it finds completed.
+    const MsmKnobs kn = msm_knobs(a.lane_fraction);
+    if (!grouped_takes(sh, scalars_n, kn)) return H2_ERR_BATCH_SHAPE;
+    const bool other_in_flight = grouped_asks_in_flight(scalars_n, kn) && msm_other_generic_in_flight(&cx);
     GroupedPlan gp;
     int rc;
-    if ((rc = grouped_plan(cx, a, sh, scalars_n, lanes, gp)) != H2_OK) return rc;
+    if ((rc = grouped_plan(sh, scalars_n, lanes, other_in_flight, kn, gp)) != H2_OK) return rc;
     const int G = gp.G;
     const Group *grp = gp.grp;
     const u32 m = (u32)scalars_n, cols = 2 * m, W = (u32)sh.W, NB = sh.NB, c = (u32)sh.c, row = (cols + 7) & ~7u;
@@ -300,11 +150,11 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     }
     auto sort_group = [&](int g, hipStream_t s_) {
         const Group &q = grp[g];
-        u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + q.gs.nh, *big = bin_start + q.gs.nh + 1;
+        u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + q.gs.nh, *big = bin_count + group_big_offset(q.gs.nh);
         u32 *starts = cx.starts.as<u32>() + q.starts_off, *entries = cx.entries.as<u32>() + q.ent_off, *heavy = cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2);
         hipLaunchKernelGGL(msm_d1_count, dim3(q.B1), dim3(512), q.gs.nh * 4, s_, (const uint16_t *)digits, q.gs, hist1);
         hipLaunchKernelGGL(msm_s1_prefix, dim3((q.gs.nh + 15) / 16), dim3(1024), 0, s_, hist1, bin_count, q.B1, q.gs.nh, heavy, big, starts + q.tb + 1, cs);
-        hipLaunchKernelGGL(msm_d1_scatter, dim3(q.B1), dim3(512), ((size_t)q.gs.nh * 3 + 1 + (size_t)q.gs.S * q.ns) * 4, s_, (const uint16_t *)digits, q.gs,
+        hipLaunchKernelGGL(msm_d1_scatter, dim3(q.B1), dim3(512), d1_stage_bytes(q.gs.nh, q.gs.S, q.ns), s_, (const uint16_t *)digits, q.gs,
                            (const u32 *)hist1, (const u32 *)bin_count, bin_start, tagged);
         // pass 2: a workgroup per bin; it also clears the group's raw bucket slots.  A bin beyond its stage (the carry slice of the split
         // is ONE bucket; columns of repeated scalars) goes to the chunked msm_s2_big_* kernels, which return at once when the list is empty

@@ -21,38 +21,18 @@
 #include "curve9_wide.cuh"
 #include "glv.cuh"
 #include "host_field.h"
+#include "msm_plan.h"      // the planning constants and structures, msm_plan / grouped_plan and the geometries: plain C++
 namespace h2 {
 
 extern std::atomic<double> g_lane_fraction;      // h2_set_option("msm_lane_fraction")
 extern std::atomic<size_t> g_pipe_chunk;         // h2_set_option("host_commit_chunk"): sweeps only
-static constexpr int kMaxC = 16;          // generic path (and the 16-bit digit codes of the one-pass sort)
-static constexpr int kMaxCShared = 20;    // registered path: one bucket slice, two-pass sort, 32-bit digit codes
 static constexpr u32 kZeroCode = 0xFFFFu;
 static constexpr u32 kZero32 = 0xFFFFFFFFu;
-static constexpr u32 kS1Scalars = 2048;   // scalars per workgroup of the two-pass sort's first pass
-static constexpr u32 kS2Chunk = 16384;    // entries per workgroup of its second pass
-static constexpr size_t kLdsCap = 160 * 1024 - 512;
 
-// two-pass sort geometries (msm_launch.hip)
-bool sort2_geometry(u32 stride, int c, int *lowb_out, int *lb_out, int *side_out = nullptr, u32 *s1_out = nullptr);
-bool pair_geometry(size_t m, int c, u32 stride, int *lowb_out, int *lb_out, u32 *nh_out, u32 *s1_out);
-
-static constexpr int kSeg = 4;     // buckets per reduce segment when the fold is latency-bound (few segments), else 2 kSeg
-static constexpr u32 kScanBlock = 1024;
-
-struct MsmShape {
-    int c, W;
-    u32 NB;          // buckets per slice = 2^(c-1)
-    u32 slices;      // generic: W; registered (precomputed table): 1
-    size_t m;        // digit columns per window = points used + (blind ? 1 : 0)
-    size_t items;    // digit codes per slice: generic m, registered W*m
-    u32 B, chunk;    // chunks per slice, codes per chunk
-    u32 total_buckets;
-};
-
-inline bool glv_applies(size_t n) { return n <= ((size_t)1 << 28); }      // the endomorphism split keeps 2n below 2^31
-int choose_c(size_t n, bool shared_buckets);
-MsmShape make_shape(size_t m, int c, bool shared_buckets, bool glv = false);
+// msm_launch.hip: the laboratory's switches (read once; H2_MSM_C at every call, as a test sets it around one registration) and the lane
+// fraction of this call (`lane_fraction` if positive, else h2_set_option's); the window width under them
+MsmKnobs msm_knobs(double lane_fraction = 0.0);
+inline int choose_c(size_t n, bool shared_buckets) { return choose_c(n, shared_buckets, msm_knobs()); }
 
 __device__ __forceinline__ u32 limb_at(const fe &s, int idx) {
     u32 v = 0;
@@ -69,68 +49,6 @@ __device__ __forceinline__ u32 limb_at(const fe &s, int idx) {
 #endif
 #define H2_LATENCY_STAGE() __builtin_amdgcn_s_setprio(H2_TAIL_PRIO)
 
-// ---- two-pass sort for the registered (one bucket slice) path ------------------------------------------------------
-// A counting sort straight into 2^15 buckets writes 16.8 M 4-byte entries to 16.8 M unrelated places: every workgroup
-// keeps 32768 cache lines open, nothing combines in L2, and the pass runs at random-scatter speed (0.2 ms,
-// bench/ubench_scatter.hip) on top of 32 MiB of per-chunk histograms.  Split the bucket id instead:
-//   pass 1  partition by the top HIB bits (~512 bins): a workgroup keeps one open line per bin, so its 4-byte writes
-//           combine in its XCD's L2; the low LOWB bits of the bucket ride in the unused bits of the entry;
-//           the digits are recomputed from the scalars (same 32 B per scalar as a digit buffer would cost to read);
-//   pass 2  chunks of 16 K entries of the pass-1 output span one or two bins = 64..128 buckets: counting sort inside
-//           that window, a few hundred bytes per bucket per chunk.
-// Per-chunk histograms shrink from 32 MiB to ~2.4 MiB.  Entry order inside a bucket is irrelevant to the sum.
-struct Sort2 {
-    u32 m;            // scalars incl. the optional blind
-    int c, W, mont;
-    u32 stride, extra_col;
-    int lowb, lb;     // low bucket bits carried in the entry at bit `lb`
-    u32 nh;           // pass-1 bins = NB >> lowb
-    u32 B1;           // pass-1 workgroups (kS1Scalars scalars each)
-    u32 K2, B2;       // pass-2 chunk size and worst-case chunk count
-    u32 lds_window;   // widest pass-2 window (buckets) whose counters fit LDS; wider ones count in HBM
-    u32 s1_scalars;   // scalars per pass-1 workgroup (a multiple of 1024)
-    u32 run_lanes;    // lanes that copy one bin's run out of the pass-1 stage (a power of two <= 64)
-    u32 nb;           // buckets per slice; generic path: sort key = window * nb + bucket, entry = digit column
-    int side;         // 1: the low bucket bits of a tagged entry live in the 16-bit side array, not in the entry
-    u32 col0;         // registered path: scalar i sits in table column col0 + i (a column RANGE of the table: the chunks of a pipelined host commit)
-    int pair_shift;   // >= 0: registered PAIR commit -- column i < pair_n feeds output (i >> pair_shift) & 1, a tail column
-    u32 pair_n;       //       i >= pair_n feeds output (i - pair_n) & 1; sort key = side * nb + bucket (two bucket slices)
-};
-
-// one GROUP of window slices of a large generic multiexp, sorted on its own (msm_generic.hip; kernels msm_d1_* in msm_sort.hip)
-struct GroupSort {
-    u32 cols;         // digit columns = 2 x scalars (column i: k1 / P_i, column m + i: k2 / phi(P_i))
-    u32 row;          // digit row stride: cols rounded up to 8
-    u32 w0, ns;       // the group's window slices [w0, w0 + ns)
-    u32 nb;           // buckets per slice; sort key = (w - w0) nb + bucket
-    int lowb, lb;     // the low `lowb` key bits ride in the tagged entry at bit `lb` (above the column index)
-    u32 nh;           // pass-1 bins = ceil(ns nb >> lowb)
-    u32 S;            // digit columns per pass-1 workgroup (a multiple of 8)
-    u32 run_lanes;    // lanes that copy one bin's run out of the pass-1 stage
-};
-
-// ---- column-batched launches ------------------------------------------------------------------------------------------------------
-// The column commits of a prover phase are independent multiexps over ONE registered table (plonk/prover.rs:93-101, 301-313;
-// vanishing/prover.rs:96-108).  A batched commit (h2_commit_batch_device) runs every stage ONCE for K columns: blockIdx.z is the
-// column, the per-column work areas lie a fixed stride apart, the scalar / blind / output pointers ride in the kernel arguments.
-// The sort and fold stages are chains of short latency-bound launches when they serve one column; with K columns per launch they
-// become throughput kernels, and the accumulate's K x 512 workgroups refill the chip as they retire instead of as whole launches.
-static constexpr int kMaxCols = 8;
-struct ColIn {                      // pass 1 of the sort
-    const u32 *scalars[kMaxCols];
-    const u32 *blinds[kMaxCols];    // null entries: no blind term
-};
-struct ColOut {                     // fold9_planes
-    u32 *out[kMaxCols];
-};
-struct ColStride {                  // 32-bit words between the areas of consecutive columns (all zero for a single column)
-    u32 hist, plan, items, starts, heavy, hscratch, heads, buckets, lines, planes, ctr;
-    u32 entries;      // sorted entries: `items` apart, or 0 when the columns are JOINED (below)
-    u32 lowprio;      // != 0: the fold kernels keep wave priority 0 (they have slack and must not stretch an accumulate that shares their SIMDs)
-    u32 joined;       // != 0: the pass-1 bin count nh.  The columns' sorted entries then form ONE list (column z's behind those of the
-                      // columns before it) with ONE boundary array over K x total_buckets buckets (bucket b of column z at
-                      // z * total_buckets + b), which msm_accumulate and fold9_finish walk as if it were a single commit
-};
 #define H2_COLZ(ptr, stride) ((ptr) + (size_t)blockIdx.z * (stride))
 // joined columns: the entries of the columns before this one (each column's total sits behind its pass-1 bin starts, at [nh])
 __device__ __forceinline__ u32 col_entry_base(const u32 *__restrict__ bin_start_col0, const ColStride &cs) {
@@ -159,9 +77,6 @@ __device__ __forceinline__ u32 wave0_excl_scan(u32 *v, u32 n) {
     return __shfl(incl, 63, 64);
 }
 
-static constexpr u32 kMaxBig = 32, kBigChunks = 64;      // big bins sorted by the chunked kernels (msm_s2_big_*); workgroups per big bin
-static constexpr u32 kS2StageWindow = 3072;
-
 // lanes actually used for M sorted entries: the launch is sized for the worst case (no zero digits); sparse or tiny
 // columns use fewer lanes so that a lane's range keeps >= `div` entries
 // (16 entries for full-size columns; 8 for small ones, which are latency-bound: more, shorter lanes -- `div`)
@@ -179,8 +94,6 @@ __device__ __forceinline__ u32 upper_bucket(const u32 *__restrict__ arr, u32 n, 
 
 // finisher constants: buckets owning more than kHeavy range heads are parked on a list and summed by whole workgroups
 static constexpr u32 kHeavy = 64;
-static constexpr u32 kMaxHeavy = 512;   // heavy buckets handed to the workgroup path; any beyond that are summed in place
-static constexpr u32 kHeavyBlocks = 32;
 static constexpr u32 kHeavyRows = 16;     // workgroup rows of the heavy-bucket launches: they walk the list (at most kMaxHeavy long, usually empty)
 // ---- the levels after that: trees, on quads of lanes ---------------------------------------------------------------------------
 // Past the per-bucket stage every sum is a TREE (a line of the bucket matrix, the heads of a heavy bucket, a bit plane of the
@@ -278,7 +191,7 @@ struct MsmContext {
     // serial with them), gstream[0] and [2] everything that runs beside them (the bases' conversion, the later groups' sorts, the groups' folds and
     // links of the Horner chain) -- three streams created back to back, so that they sit on different hardware queues whatever queue the CALLER's stream shares
     // with whom; gev: fork, conversion done, per group sorted / accumulated / chained, then begin / end (the caller's stream only waits on those)
-    static constexpr int kMaxGroups = 4;
+    static constexpr int kMaxGroups = h2::kMaxGroups;
     hipStream_t gstream[1 + kMaxGroups] = {};
     hipEvent_t gev[4 + 3 * kMaxGroups] = {};
     // recorded behind every grouped multiexp of this context; other contexts ask it whether a generic multiexp is in flight on ANOTHER stream
@@ -308,78 +221,6 @@ MsmContext &msm_ctx(hipStream_t st = nullptr);          // msm_launch.hip
 // h2_commit_last_plan for calls that ran on the library's own streams: the record of `from`'s context, with the caller form filled in, becomes
 // that of `to`'s (each context's mutex taken in turn, never both)
 void msm_hand_last_plan(hipStream_t from, hipStream_t to, u32 caller, u32 count, u32 cols_first = 0, u32 cols_last = 0);
-
-struct MsmArgs {
-    const void *d_scalars;       // n_used scalars
-    const void *d_extra_scalar;  // blind or null
-    const void *d_bases;         // generic: n_used affine points; registered: table [W][stride]
-    const void *d_extra_base;    // generic + blind: w's buffer; else null
-    size_t n_used;
-    bool table;                  // registered (precomputed) shape
-    int c;                       // window bits (fixed by the table when `table`)
-    u32 stride;                  // table row stride (n_registered + 1)
-    u32 extra_col;               // table column of the blind's base; 0xFFFFFFFF when unused
-    int form, out_kind;
-    void *d_out;
-    double lane_fraction = 0.0;  // 0 = the process-wide option; the batch entry point narrows its commits
-    int pair_shift = -1;         // >= 0 (registered only): two outputs from one column, see Sort2::pair_shift; d_out holds both
-    u32 pair_n = 0;
-    u32 col0 = 0;                // registered only: the scalars are table columns [col0, col0 + n_used)
-    // A commit assembled from RANGES (the chunks of a pipelined host transfer): each range runs sort + accumulate + finish and
-    // adds its finished buckets into `add_into` (XYZZ, reference Montgomery form, [NB]) instead of folding them; one fold-only
-    // call (`fold_from`) then reduces the summed buckets: the ranges share ONE fold instead of paying one each.
-    u32 *add_into = nullptr;
-    const u32 *fold_from = nullptr;
-    // Column-batched commit (registered tables, wide windows): ncols independent columns of n_used scalars each run through ONE
-    // launch set, blockIdx.z = column (ColIn / ColOut / ColStride above).  Host arrays of device pointers; col_blinds may be null.
-    // msm_launch answers H2_ERR_BATCH_SHAPE before launching anything when the shape does not take the batched form.
-    // phase: 0 the whole multiexp; 1 stop after the sort (nothing has read d_bases yet); 2 resume after it (same arguments, same stream).
-    // h2_msm uses 1 / 2 to run the sort -- which needs the scalars only -- while the bases are still crossing PCIe.  Its range
-    // pipeline cuts finer: 3 = resume after the sort and stop after the accumulate (the full-chip part); 4 = the fold alone, behind a
-    // phase-3 call of the same arguments (possibly on ANOTHER stream, ordered by the caller's events).  slice_sums_only (generic
-    // path with window slices on the carry-free fold): the fold stops at the per-slice sums in cx.ssums (XYZZ, 32 words per slice) --
-    // the caller runs ONE Horner step over the sums of several ranges (msm_combine_ranges) instead of one chain of ~128 doublings
-    // per range; H2_ERR_BATCH_SHAPE, before anything is launched, when the shape does not take that form.
-    int phase = 0;
-    bool slice_sums_only = false;
-    int ncols = 1;
-    const void *const *col_scalars = nullptr;
-    const void *const *col_blinds = nullptr;
-    void *const *col_outs = nullptr;
-};
-static constexpr int H2_ERR_BATCH_SHAPE = -1000;     // internal: never leaves the library
-
-// What one call of msm_launch decides before it enqueues or reserves anything (msm_plan, msm_launch.hip): the shape, which sort / accumulate /
-// fold forms the call takes, their geometries and the sizes its reservations follow from.  Plain data: no pointer into a context.
-struct MsmPlan {
-    MsmShape sh;
-    size_t m, scalars_n;  // digit columns (twice the scalars under the endomorphism split); scalars (+ blind) before the split
-    size_t all_items;     // W * m: the most entries the sorted list can hold (per column)
-    bool fold_only;       // a.fold_from: nothing but the fold of buckets summed elsewhere
-    bool add_only;        // a.add_into: a range of a chunked commit stops at its finished buckets
-    bool glv;             // generic path: k = k1 + k2 lambda, two half-length digit columns per scalar
-    bool m9;              // the accumulate runs on the carry-free layer (registered tables; generic bases converted per call)
-    bool pair;            // registered pair commit: two bucket slices, two outputs
-    u32 K;                // columns of a batched commit (1: a single multiexp)
-    bool joined;          // ... whose sorted lists form ONE list (ColStride::joined)
-    u32 tb, nblocks;      // total buckets; scan blocks over them
-    u32 T, lane_div;      // lanes of the accumulate; entries per lane it aims at
-    size_t head_slots;    // range heads parked in cx.seg9, in front of the K x tb bucket slots
-    bool use_sort2;       // two-pass sort (S2 filled), else the one-pass sort
-    Sort2 S2;
-    bool s2_bins_form;    // pass 2 in its one-launch form (a workgroup per pass-1 bin) with an LDS stage of s2_cap_entries
-    size_t s2_cap_entries, plan_words;
-    u32 max_big;          // oversized pass-2 bins handed to the chunked msm_s2_big_* kernels (0: none, their launches are skipped)
-    bool zero_in_sort;    // the one-launch pass 2 also clears the raw bucket slots
-    bool fold9;           // the fold on the carry-free layer (fold9_* kernels), else the 8 x 32 finisher and fold
-    bool wide_reduce;     // more than 2^15 buckets a slice on the 8 x 32 fold: row / column sums first
-    u32 wideS, wideNR;    // the bucket matrix of a slice: wideS columns x wideNR rows
-    bool try_grouped;     // a whole large generic multiexp: msm_generic_grouped is asked first
-    int split_k;          // != 0: slice split, the lower group's slice count
-    ColIn ci;             // column-batched commit: the per-column pointers and the distances between the per-column work areas
-    ColOut co;
-    ColStride cs;
-};
 
 // Launched from more than one place (msm_launch.hip, msm_generic.hip), defined beside the kernels they launch.
 // msm_fold.hip: the carry-free fold of a contiguous GROUP of slices [slice0, slice0 + nslices) down to its slice sums -- finish (range heads into

@@ -39,126 +39,31 @@ namespace h2 {
 std::atomic<double> g_lane_fraction{1.0};
 std::atomic<size_t> g_pipe_chunk{0};   // h2_set_option("host_commit_chunk"): sweeps only
 
-// Two-pass sort geometry for a table of `stride` columns and window width c: the low `lowb` bucket bits ride in the
-// entry above the table index (`lb` bits); the remaining bucket_bits - lowb bits select the pass-1 bin.
-bool sort2_geometry(u32 stride, int c, int *lowb_out, int *lb_out, int *side_out, u32 *s1_out) {
-    const int W = 255 / c + 1, bucket_bits = c - 1;
-    const uint64_t top = (uint64_t)W * stride - 1;
-    if (top >= ((uint64_t)1 << 31)) return false;
-    int lb = 0;
-    while ((top >> lb) != 0) ++lb;
-    // 512 pass-1 bins whenever the low bucket bits have somewhere to ride: in the entry's spare bits above the table index, or
-    // -- windows of 18 bits and more at 2^20 points, where those are too few -- in a 16-bit SIDE array next to the tagged list
-    // (pass 1 writes 6 bytes per entry instead of 4; without it c = 20 meant 4096 bins and 6-entry runs)
-    int lowb = std::min(31 - lb, bucket_bits - 9), side = 0;
-    // ... only where the entry's own spare bits would leave more than 1024 bins: at 17-bit windows over 2^20 points (1024 bins
-    // without it) the side array buys nothing and costs 50 % more tagged traffic (measured: 1027 against 1026-1038 M/s)
-    if (bucket_bits - lowb > 10 && bucket_bits - 9 <= 14 && W <= 64) {
-        lowb = bucket_bits - 9;
-        side = 1;
-    }
-    if (lowb < 1 || bucket_bits - lowb > 12) return false;
-    const size_t nh = (size_t)1 << (bucket_bits - lowb);
-    // pass-1 stage in LDS: 2048 scalars' digits per workgroup, 1024 where narrower windows mean more digits per scalar (13-bit tables:
-    // 20 digits) -- only for callers that ask (s1_out); the others keep the fixed 2048 they were measured with
-    u32 s1 = kS1Scalars;
-    if (s1_out && (nh * 3 + 1 + (size_t)s1 * W) * 4 > kLdsCap) s1 = 1024;
-    if ((nh * 3 + 1 + (size_t)s1 * W) * 4 > kLdsCap) return false;
-    if (s1_out) *s1_out = s1;
-    *lowb_out = lowb;
-    *lb_out = lb;
-    if (side_out) *side_out = side;
-    return true;
+// The laboratory's switches of the plans (msm_plan.h), read once per process (ab_env: a constant null in the product, where the defaults
+// hold) -- except H2_MSM_C, read at every call as it always was: a test sets it around one registration.
+static MsmKnobs msm_read_switches() {
+    MsmKnobs k;
+    if (const char *e = ab_env("H2_MSM_DIV")) { const int v = atoi(e); k.lane_div = (u32)(v >= 1 && v <= 64 ? v : 0); }
+    if (const char *e = ab_env("H2_BATCH_JOIN")) k.batch_join = e[0] != '0';
+    if (const char *e = ab_env("H2_GENERIC_SPLIT")) k.generic_split = atoi(e);
+    if (const char *e = ab_env("H2_GENERIC_GROUPED")) k.grouped = atoi(e) != 0;         // 0: round 5's slice split (A/B)
+    if (const char *e = ab_env("H2_GG_FORM")) k.gg_form = atoi(e);                      // 1: latency form always, 2: throughput form always (A/B)
+    if (const char *e = ab_env("H2_GG_SPARE")) k.gg_spare = atoi(e);                    // CUs left without an accumulate workgroup
+    if (const char *e = ab_env("H2_GENERIC_GROUPS"))                                    // "a,b,c"
+        for (const char *p = e; *p;) {
+            if (k.ngroups < kMaxGroups) k.groups[k.ngroups] = atoi(p);
+            ++k.ngroups;
+            while (*p && *p != ',') ++p;
+            if (*p == ',') ++p;
+        }
+    return k;
 }
-// The paired commit (h2_commit_pair_device): two bucket slices, key = side * NB + bucket.  Pass 1 stages s1 scalars' digits per
-// workgroup in LDS: 2048 for 16 windows, 1024 when narrower windows (smaller tables: more digits per scalar) would not fit.
-bool pair_geometry(size_t m, int c, u32 stride, int *lowb_out, int *lb_out, u32 *nh_out, u32 *s1_out) {
-    if (c > kMaxC || c < 2 || m < 8192) return false;
-    const int W = 255 / c + 1;
-    const u32 tb = 2u << (c - 1);
-    const uint64_t top = (uint64_t)W * stride - 1;
-    if (top >= ((uint64_t)1 << 31)) return false;
-    int lb = 0, kb = 0;
-    while ((top >> lb) != 0) ++lb;
-    while (((u64)(tb - 1) >> kb) != 0) ++kb;
-    const int lowb = std::min(31 - lb, std::max(1, kb - 9));
-    if (lowb < 1) return false;
-    const u32 nh = (tb + (1u << lowb) - 1) >> lowb;
-    if (nh > 4096) return false;
-    u32 s1 = kS1Scalars;
-    while (s1 >= 1024 && ((size_t)nh * 3 + 1 + (size_t)s1 * W) * 4 > kLdsCap) s1 /= 2;
-    if (s1 < 1024) return false;
-    *lowb_out = lowb;
-    *lb_out = lb;
-    *nh_out = nh;
-    *s1_out = s1;
-    return true;
-}
-
-// window width: minimise mixed adds + reduce work.  `shared_buckets`: registered bases (one slice).
-// The generic path always splits scalars with the endomorphism (glv.cuh): the window Horner it halves (0.35 ms) and the
-// smaller fold (9 slices instead of 16) outweigh the extra bucket additions (2n x 9 windows against n x 16, and the
-// on-the-fly phi) at every size measured, 2.76 against 3.09 ms even at 2^20.  The size cap only keeps 2n below 2^31.
-
-int choose_c(size_t n, bool shared_buckets) {
-    auto feasible = [&](int c) {
-        if (c <= kMaxC) return true;
-        int lowb, lb;
-        return shared_buckets && n + 1 < ((size_t)1 << 31) && sort2_geometry((u32)n + 1, c, &lowb, &lb);
-    };
-    if (const char *e = ab_env("H2_MSM_C")) {   // tuning sweeps only; the only way to windows beyond 16 bits (see below)
-        int v = atoi(e);
-        if (v >= 4 && v <= kMaxCShared && feasible(v)) return v;
-    }
-    // Windows of 17..20 bits (registered path) are implemented and parity-tested but not chosen: at n = 2^20, c = 20 cuts
-    // the accumulate from 1.29 to 1.07 ms (13 windows instead of 16) and loses more than that in the sort (4096 pass-1
-    // bins: 6-entry runs) and in the fold over 2^19 buckets (0.49 vs 0.27 ms).  DESIGN.md section 8.
-    const bool glv = !shared_buckets && glv_applies(n);
-    // With the split, magnitudes have 128 bits, so the TOP window of width c holds 128 - c floor(127 / c) significant
-    // bits: 2 for c = 14, 8 for c = 12 or 15 -- every entry of that window then lands in a few hundred buckets, which are
-    // summed by the (slow) heavy-bucket path.  c = 10, 13 and 16 fill their top window (8 of 10, 11 of 13, 16 of 16 bits).
-    // Small multiexps are pure latency (a chain of ~128 doublings plus the per-slice folds); measured over c = 4..14
-    // (bench/tools/c_sweep_small.py): 0.67-0.72 ms at c = 10 up to 2^12 points, c = 13 up to 2^19 (2^18: 1.08 against 1.20 ms at
-    // c = 16, 2^19: 1.43 against 1.52; 2^20: equal, and the accumulate is shorter with 16), c = 16 beyond.
-    // (round 3, with the fold on the carry-free layer, bench/tools/generic_ms.py: 2^12 at 13 / 10 bits 0.461 / 0.474 ms; 2^18 at 16 / 13
-    // bits 0.846 / 0.851; 2^19 1.11 / 1.165: 10 bits up to 2^11, 13 up to 2^18, 16 beyond)
-    if (glv) return n <= 2048 ? 10 : n <= 262144 ? 13 : 16;
-    // Registered tables: a commit below ~2^17 points is a chain of latency-bound kernels, not bucket arithmetic, and the widths
-    // whose top window is nearly empty (255 mod c small: 12, 14) send that window through the heavy-bucket path.  Measured, one
-    // commit alone (bench/tools/c_sweep_registered.py): 8 bits up to 2^9 points (0.21-0.27 ms), 10 up to 2^10 (0.32), 13 up to
-    // 2^13 (0.35-0.39; 12 bits at 2^12: 0.59; a paired commit at 2^13: 0.39 against 0.44 with 16), 16 from 2^14 on (0.41-0.49;
-    // the cost model below picked 13-14 bits there: 2^15 0.48 -> 0.42).  Re-measured in round 3 with the fold on the carry-free
-    // layer (bench/tools/lone_commit_ms.py, H2_MSM_C): 2^14 / 2^15 / 2^16 at 16 bits 0.24 / 0.27 / 0.27 ms, at 14 bits 0.32 / 0.37 /
-    // 0.42, at 13 bits 0.37 / 0.54 / 0.59; 2^13 at 16 / 13 bits 0.244 / 0.294; 2^12 0.254 / 0.236; 2^11 0.263 / 0.222; 2^10 0.248 / 0.200
-    // (10 bits: 0.258); 2^9 0.251 / 0.196 (8 bits: 0.256); 2^8 at 13 / 8 bits 0.204 / 0.196: 8 bits up to 2^8, 13 up to 2^12, 16 beyond.
-    if (shared_buckets) return n <= 384 ? 8 : n <= 6144 ? 13 : 16;
-    double best = 1e300;
-    int bc = 4;
-    for (int c = 4; c <= kMaxC; ++c) {
-        // with the endomorphism split: 2n half-length scalars, 130 / c + 1 windows
-        int W = glv ? 130 / c + 1 : 255 / c + 1;
-        double pairs = glv ? 2.0 * (double)n : (double)n;
-        double buckets = (double)(1u << (c - 1)) * (shared_buckets ? 1 : W);
-        double cost = (double)W * pairs * 10.5 + buckets * 60.0;
-        if (cost < best) { best = cost; bc = c; }
-    }
-    return bc;
-}
-
-// m: digit columns (generic path with the endomorphism split: 2 x scalars, `glv` picks the shorter window count)
-MsmShape make_shape(size_t m, int c, bool shared_buckets, bool glv) {
-    MsmShape s;
-    s.c = c;
-    s.W = glv ? 130 / c + 1 : 255 / c + 1;
-    s.NB = 1u << (c - 1);
-    s.slices = shared_buckets ? 1 : (u32)s.W;
-    s.m = m;
-    s.items = shared_buckets ? (size_t)s.W * m : m;
-    u32 B = (u32)((s.items + 65535) / 65536);
-    s.B = B < 1 ? 1 : B;
-    s.chunk = (u32)((s.items + s.B - 1) / s.B);
-    s.total_buckets = s.slices * s.NB;
-    return s;
+MsmKnobs msm_knobs(double lane_fraction) {
+    static const MsmKnobs read = msm_read_switches();
+    MsmKnobs k = read;
+    if (const char *e = ab_env("H2_MSM_C")) k.force_c = atoi(e);
+    k.lane_fraction = lane_fraction > 0.0 ? lane_fraction : g_lane_fraction.load();
+    return k;
 }
 
 // ---- small helpers -----------------------------------------------------------------------------
@@ -289,187 +194,6 @@ void msm_release_workspaces() {
     }
 }
 
-// The accumulate runs on the carry-free layer for registered tables (stored in M9 form: h2_bases_register) and for the generic path's endomorphism
-// split (bases converted per call); only a generic call with a blind term keeps the 8 x 32 layer.
-static bool msm_glv(const MsmArgs &a) { return !a.table && !a.d_extra_scalar && glv_applies(a.n_used); }
-static bool msm_m9(const MsmArgs &a) { return a.table || msm_glv(a); }
-
-// the fields every two-pass shape fills the same way (`scalars` per pass-1 launch, pass-2 windows over `window` buckets); the arms of msm_plan
-// set what differs: stride, extra_col, side, col0, the pair fields
-static void sort2_fill(Sort2 &S2, const MsmArgs &a, const MsmShape &sh, size_t scalars, size_t all_items, int lowb, int lb, u32 nh, u32 s1, u32 window) {
-    S2.m = (u32)scalars; S2.c = sh.c; S2.W = sh.W; S2.mont = a.form == H2_FORM_MONTGOMERY;
-    S2.extra_col = 0xFFFFFFFFu;
-    S2.lowb = lowb; S2.lb = lb; S2.nh = nh;
-    S2.s1_scalars = s1; S2.nb = sh.NB; S2.B1 = (u32)((scalars + s1 - 1) / s1);
-    S2.K2 = kS2Chunk; S2.B2 = (u32)((all_items + kS2Chunk - 1) / kS2Chunk);
-    S2.lds_window = std::min<u32>(window, 32768u);
-}
-// Every decision of one call, before anything is enqueued or reserved: no HIP call, no context.  `lanes`: the lanes of this call's accumulate
-// kernel the chip holds at once; `instrumented` (h2_profile_enable, H2_TIMELINE=1) keeps a call off the grouped form and the slice split.
-// H2_ERR_ARGS / H2_ERR_BATCH_SHAPE when the shape takes no form (or not the batched / slice-sums form it asks for).
-static int msm_plan(const MsmArgs &a, u32 lanes, bool instrumented, MsmPlan *plan) {
-    MsmPlan &p = *plan;
-    memset(&p, 0, sizeof p);
-    size_t m = a.n_used + (a.d_extra_scalar ? 1 : 0);
-    p.fold_only = a.fold_from != nullptr;
-    p.add_only = a.add_into && !p.fold_only;
-    // generic path: every scalar is split k = k1 + k2 lambda (glv.cuh) into two half-length digit columns, i for P_i and
-    // n + i for phi(P_i): as many bucket additions (2n x 9 windows against n x 16), half the doublings in the final Horner
-    const bool glv = p.glv = msm_glv(a);
-    const bool m9 = p.m9 = msm_m9(a);
-    const size_t scalars_n = p.scalars_n = m;
-    if (glv) m *= 2;
-    if (p.fold_only && m < 1) m = 1;                   // only the bucket geometry (c) matters to the fold
-    p.m = m;
-    MsmShape &sh = p.sh;
-    sh = make_shape(m, a.c, a.table, glv);
-    const u32 K = p.K = a.ncols > 1 ? (u32)a.ncols : 1u;
-    if (K > 1 && (K > (u32)kMaxCols || !a.table || a.pair_shift >= 0 || a.add_into || p.fold_only || !a.col_scalars || !a.col_outs || a.n_used == 0))
-        return H2_ERR_BATCH_SHAPE;
-    p.pair = a.table && a.pair_shift >= 0;
-    if (p.pair) {                     // one bucket slice per output
-        sh.slices = 2;
-        sh.total_buckets = 2 * sh.NB;
-    }
-    const u32 tb = p.tb = sh.total_buckets;
-    const size_t all_items = p.all_items = (size_t)sh.W * m;
-    if (all_items >= ((size_t)1 << 31)) return H2_ERR_ARGS;  // entry = table index | sign << 31
-    p.nblocks = (tb + kScanBlock - 1) / kScanBlock;
-    // one round of resident lanes; small problems use fewer lanes so a range keeps >= 16 entries
-    // a lane fraction < 1 (h2_set_option) leaves wave slots free so that the latency-bound sort / reduce kernels
-    // of a commit running on ANOTHER stream can overlap this kernel (independent column commits)
-    const double fraction = a.lane_fraction > 0.0 ? a.lane_fraction : g_lane_fraction.load();
-    const u32 usable = std::max(256u, (u32)(lanes * fraction) / 256u * 256u);
-    // entries per lane of the accumulate: 16 for full-size columns; small commits are chains of latency-bound kernels and run
-    // shorter with more, shorter lanes (one registered commit at 2^11 .. 2^15 points: 3-7 % faster at 8; H2_MSM_DIV: sweeps only)
-    static const u32 env_div = [] { const char *e = ab_env("H2_MSM_DIV"); int v = e ? atoi(e) : 0; return (u32)(v >= 1 && v <= 64 ? v : 0); }();
-    p.lane_div = env_div ? env_div : (all_items < ((size_t)1 << 20) ? 8u : 16u);
-    // Column-batched commits are JOINED (ColStride::joined) unless H2_BATCH_JOIN=0: the K sorted lists form one, which ONE launch of
-    // msm_accumulate cuts into equal ranges -- the chip is tiled exactly as by a single commit (a launch per column leaves its last
-    // round of workgroups ragged, and K of them next to each other share CUs unevenly), and the finisher meets T range heads per
-    // batch instead of per column.
-    static const bool join_env = [] { const char *e = ab_env("H2_BATCH_JOIN"); return !(e && e[0] == '0'); }();
-    const bool joined = p.joined = K > 1 && join_env;
-    const u32 T = p.T = (u32)std::min<size_t>(usable, std::max<size_t>(256, ((joined ? K : 1) * all_items / p.lane_div + 255) / 256 * 256));
-    p.head_slots = joined ? (size_t)T : (size_t)T * K;
-    // two-pass sort (registered path): always for windows beyond 16 bits, else for large bucket counts
-    Sort2 &S2 = p.S2;
-    S2.pair_shift = -1; S2.run_lanes = 16;
-    if (p.pair) {
-        // key = side * NB + bucket over both slices (the generic path's multi-slice geometry), entry = table index
-        int lb = 0, lowb = 0;
-        u32 nh = 0, s1 = 0;
-        if (!pair_geometry(m, sh.c, a.stride, &lowb, &lb, &nh, &s1)) return H2_ERR_ARGS;
-        p.use_sort2 = true;
-        sort2_fill(S2, a, sh, m, all_items, lowb, lb, nh, s1, tb);
-        S2.stride = a.stride; S2.pair_shift = a.pair_shift; S2.pair_n = a.pair_n;
-    } else if (a.table && (sh.c > kMaxC || (sh.NB >= 4096 && (m >= 8192 || K > 1)))) {
-        // (a column-batched commit exists in the two-pass form only, so it takes it from 13-bit tables on whatever the column length:
-        // eight 2^12-point columns in one launch set are 0.3 ms against 0.9 ms for eight chains of one-pass sorts)
-        int lowb = 0, lb = 0, side = 0;
-        u32 s1 = kS1Scalars;
-        if (sort2_geometry(a.stride, sh.c, &lowb, &lb, &side, &s1)) {
-            p.use_sort2 = true;
-            sort2_fill(S2, a, sh, m, all_items, lowb, lb, sh.NB >> lowb, s1, sh.NB);
-            S2.stride = a.stride; S2.side = side; S2.col0 = a.col0;
-            if (a.d_extra_scalar) S2.extra_col = a.extra_col;
-        }
-    } else if (glv && scalars_n >= 65536) {
-        // generic path, large: sort key = window * NB + bucket over all slices, entry = digit column (< 2 * scalars)
-        int lb = 0, kb = 0;
-        while (((u64)(m - 1) >> lb) != 0) ++lb;
-        while (((u64)(tb - 1) >> kb) != 0) ++kb;
-        // bins of ~16 K entries (kb - 11 bucket bits per bin: 1152 bins for 9 slices of 2^15 buckets), so that pass 2 is the
-        // one-launch form with a bin per workgroup in LDS (9 bits = the chunked pass 2 of round 2).
-        // Up to 2^19 scalars only: the carry slice of the split (the window above the top of a 128-bit half) puts ~n / 2 entries
-        // into ONE bucket, and a bin that large was scattered by a single workgroup (2^19: sort 0.28 -> 0.16 ms; 2^20: 0.30 -> 0.61).
-        // With the oversized-bin kernels (msm_s2_big_*) that bin is chunked over 64 workgroups: 2^20 takes the one-launch form with
-        // 10 bits (1.83 -> 1.71 ms on one box; 11 bits 1.80, 12 bits 1.83); from 2^21 the forms are equal within 1 %.
-        const int bin_bits = scalars_n <= ((size_t)1 << 19) ? 11 : scalars_n <= ((size_t)1 << 20) ? 10 : 9;
-        const int lowb = std::min(31 - lb, std::max(1, kb - bin_bits));
-        const u32 nh = (tb + (1u << lowb) - 1) >> lowb;
-        const u32 s1 = 1024;
-        const bool fits = ((size_t)nh * 3 + 1 + (size_t)s1 * 2 * sh.W) * 4 <= kLdsCap;
-        if (lowb >= 1 && nh <= 4096 && fits) {
-            p.use_sort2 = true;
-            sort2_fill(S2, a, sh, scalars_n, all_items, lowb, lb, nh, s1, tb);
-        }
-    }
-    if (sh.c > kMaxC && !p.use_sort2) return H2_ERR_ARGS;   // choose_c only picks wide windows the two-pass sort can take
-    if (K > 1 && !p.use_sort2) return H2_ERR_BATCH_SHAPE;
-    p.wide_reduce = sh.NB > 32768u;                       // implies the registered path (one slice)
-    // the fold on the carry-free layer (fold9_* kernels: registered tables from 16-bit windows, paired commits, and the window
-    // slices of a large generic multiexp); a range of a chunked commit hands finished buckets on in the reference's form
-    // (add_into), so it keeps the 8 x 32 finisher
-    p.fold9 = sh.NB >= 128 && sh.slices <= 16 && m9 && !a.add_into && !p.fold_only;      // (16: arrival counters of fold9_planes)
-    if (K > 1 && !p.fold9) return H2_ERR_BATCH_SHAPE;
-    if (a.slice_sums_only && !(p.fold9 && glv)) return H2_ERR_BATCH_SHAPE;
-    // The grouped form (round 6, msm_generic.hip; generic multiexps beyond 2^18 points): the endomorphism split once, the window slices
-    // sorted / accumulated / folded in groups, upper slices first.  It answers H2_ERR_BATCH_SHAPE before enqueueing anything when the shape
-    // is not its own; round 5's slice split below then still applies (and is the A/B arm, H2_GENERIC_GROUPED=0 in the laboratory build).
-    p.try_grouped = glv && p.fold9 && a.phase == 0 && !a.slice_sums_only && K == 1 && !instrumented;
-    // Slice split (round 5; generic multiexps from 2^19 points): the sorted list is ordered by (slice, bucket), so the upper slices
-    // [split_k, slices) and the lower ones [0, split_k) are two contiguous halves of it.  They are accumulated one after the other on
-    // `st`; as soon as the UPPER group is in its buckets its fold and its Horner chain -- (slices - 1) c ~ 128 dependent doublings, 0.25 ms
-    // on one quad of lanes, which used to follow the whole accumulate -- run on a side stream beside the lower group's accumulate and
-    // fold.  What is left behind the accumulate: the lower group's fold, (split_k - 1) c doublings and one addition.  The bases'
-    // conversion to M9 form runs on the side stream beside the sort.  H2_GENERIC_SPLIT=0: off (A/B); = k: force the lower group's size.
-    static const int split_env = [] { const char *e = ab_env("H2_GENERIC_SPLIT"); return e ? atoi(e) : -1; }();
-    if (p.try_grouped && sh.slices >= 6 && split_env != 0) {
-        if (split_env > 0) p.split_k = std::min<int>(split_env, (int)sh.slices - 2);
-        else if (scalars_n >= ((size_t)1 << 19)) p.split_k = 3;
-    }
-    if (p.split_k) p.head_slots = 2 * (size_t)T;             // each group's T range heads
-    // pass 2 of the two-pass sort in its one-launch form (a workgroup per pass-1 bin; the chunked form otherwise)?  Decided here, before
-    // anything is launched, because a column-batched commit exists in that form only.
-    if (p.use_sort2) {
-        const size_t nbk = (size_t)1 << S2.lowb;
-        // LDS stage: the average bin + 25 % (two workgroups per CU where that fits: 2^20 scalars at 17 bits, 15 K-entry bins), at
-        // most what one workgroup can have; a bin beyond its stage takes the direct-scatter branch.
-        const size_t cap_max = nbk * 8 + 64 < kLdsCap ? (kLdsCap - nbk * 8) / 4 : 0;
-        p.s2_cap_entries = std::min(cap_max, std::max<size_t>(4096, all_items / S2.nh * 5 / 4 + 1024));
-        const size_t nbins = ((size_t)tb + nbk - 1) >> S2.lowb;
-        p.s2_bins_form = S2.lowb <= 12 && nbins == S2.nh && p.s2_cap_entries && all_items / S2.nh <= p.s2_cap_entries * 9 / 10;
-        p.plan_words = (size_t)S2.nh * 2 + 1 + (size_t)S2.B2 * 2 + 1 +
-                       std::max<size_t>(((size_t)S2.nh + S2.B2 + 1) << S2.lowb, 64 + (((size_t)kMaxBig * (kBigChunks + 1)) << S2.lowb));
-        p.plan_words = (p.plan_words + 3) & ~(size_t)3;
-    }
-    if (K > 1 && !p.s2_bins_form) return H2_ERR_BATCH_SHAPE;
-    if (p.wide_reduce || p.fold9) {
-        p.wideS = 1u << ((sh.c - 1) / 2);
-        p.wideNR = sh.NB / p.wideS;
-    }
-    // the one-launch pass 2 also clears the raw bucket slots (its workgroups own disjoint bucket ranges)
-    p.zero_in_sort = m9 && p.use_sort2 && p.s2_bins_form && !p.fold_only;
-    // oversized pass-2 bins (degenerate columns) go to the chunked msm_s2_big_* kernels only where a bin can be large enough for
-    // that to matter: below 3 * 2^20 entries per column (2^18 scalars) the bin's own workgroup streams it (<= 2^17 entries: tens of
-    // microseconds, and only for such columns), and every commit saves three launches that would find an empty list
-    p.max_big = all_items >= ((size_t)3 << 20) ? kMaxBig : 0u;
-    // column-batched commit: the per-column pointers and the distances between the per-column work areas (32-bit words)
-    if (K > 1) {
-        for (u32 k = 0; k < K; ++k) {
-            p.ci.scalars[k] = (const u32 *)a.col_scalars[k];
-            p.ci.blinds[k] = a.col_blinds ? (const u32 *)a.col_blinds[k] : nullptr;
-            p.co.out[k] = (u32 *)a.col_outs[k];
-            if (!p.ci.scalars[k] || !p.co.out[k] || (a.d_extra_scalar && !p.ci.blinds[k])) return H2_ERR_ARGS;
-        }
-        ColStride &cs = p.cs;
-        cs.hist = (u32)((size_t)S2.B1 * S2.nh);
-        cs.plan = (u32)p.plan_words;
-        cs.items = (u32)all_items;
-        cs.entries = joined ? 0u : (u32)all_items;
-        cs.joined = joined ? S2.nh : 0u;
-        cs.starts = joined ? tb : tb + 2;
-        cs.heavy = kMaxHeavy + 2;
-        cs.hscratch = kMaxHeavy * kHeavyBlocks * 36;
-        cs.heads = T * 36;
-        cs.buckets = tb * 36;
-        cs.lines = sh.slices * (p.wideS + p.wideNR) * 36;
-        cs.planes = sh.slices * 32 * 36;
-        cs.ctr = 16;
-    }
-    return H2_OK;
-}
 // ---- context set-up: the LDS attributes of the sort kernels, once per (device, stream) context (the attribute is per device), and how many
 // lanes of this call's accumulate kernel the chip holds at once
 template <int FB> static int msm_context_setup(MsmContext &cx, bool m9, u32 *lanes_out) {
@@ -551,11 +275,12 @@ template <int FB> static int msm_empty(MsmContext &cx, const MsmArgs &a, hipStre
     H2_HIP(hipGetLastError());
     return H2_OK;
 }
-// where the two-pass sort keeps its tables inside cx.plan: bin counts, bin starts, then the chunked pass 2's plan and histograms
+// where the two-pass sort keeps its tables inside cx.plan (sort2_layout, msm_plan.h)
 struct Sort2Areas { u32 *bin_count, *bin_start, *hlo, *woff, *hist2; };
 static Sort2Areas sort2_areas(MsmContext &cx, const Sort2 &S2) {
-    u32 *bin_count = cx.plan.as<u32>(), *bin_start = bin_count + S2.nh, *hlo = bin_start + S2.nh + 1, *woff = hlo + S2.B2;
-    return {bin_count, bin_start, hlo, woff, woff + S2.B2 + 1};
+    const Sort2Layout l = sort2_layout(S2.nh, S2.B2, S2.lowb);
+    u32 *plan = cx.plan.as<u32>();
+    return {plan + l.bin_count, plan + l.bin_start, plan + l.hlo, plan + l.woff, plan + l.hist2};
 }
 // bucket counts (cx.counts) -> bucket starts (cx.starts): the three-kernel exclusive scan both sorts end their counting with
 static void scan_bucket_starts(MsmContext &cx, const MsmPlan &p, hipStream_t st) {
@@ -572,7 +297,7 @@ template <int FS> static void sort2_pass1(MsmContext &cx, const MsmPlan &p, cons
     const u32 K = p.K, tb = p.tb;
     const Sort2Areas w = sort2_areas(cx, S2);
     u32 *hist1 = cx.hist.as<u32>();
-    const size_t lds1 = ((size_t)S2.nh * 3 + 1 + (size_t)S2.s1_scalars * (p.glv ? 2 : 1) * p.sh.W) * 4;
+    const size_t lds1 = s1_stage_bytes(S2.nh, S2.s1_scalars, (size_t)(p.glv ? 2 : 1) * p.sh.W);
     // 512 lanes per pass-1 workgroup: msm_s1_scatter takes 72 registers a lane, and 16 waves of it do not fit beside the two
     // msm_accumulate waves a SIMD already holds (2 x 168 of 512 registers) -- with 1024 lanes the sort of the NEXT commit on
     // another stream sat out the whole accumulate (416 us on average in a 3-stream trace against 57 us alone); LDS is free
@@ -602,13 +327,13 @@ static int sort2_pass2_chunked(MsmContext &cx, const MsmPlan &p, hipStream_t st)
     const u32 *tagged = cx.tagged.as<u32>();
     const uint16_t *tagged_low = cx.tagged_low.as<uint16_t>();
     hipLaunchKernelGGL(msm_s2_plan, dim3(1), dim3(kScanBlock), 0, st, w.bin_start, S2, w.hlo, w.woff);
-    const size_t hist2_words = ((size_t)S2.nh + S2.B2 + 1) << S2.lowb;
+    const size_t hist2_words = sort2_layout(S2.nh, S2.B2, S2.lowb).hist2_words;
     if (tb > S2.lds_window) H2_HIP(hipMemsetAsync(w.hist2, 0, hist2_words * 4, st));   // the HBM-counted windows start from zero
-    const size_t lds2 = ((size_t)S2.lds_window + S2.nh + 1) * 4;
+    const size_t lds2 = s2_count_bytes(S2.lds_window, S2.nh);
     hipLaunchKernelGGL(msm_s2_count, dim3(S2.B2), dim3(1024), lds2, st, tagged, tagged_low, w.bin_start, w.hlo, w.woff, S2, w.hist2);
     hipLaunchKernelGGL(msm_s2_prefix, dim3((tb + 255) / 256), dim3(256), 0, st, w.hist2, w.bin_start, w.hlo, w.woff, S2, cx.counts.as<u32>(), tb);
     scan_bucket_starts(cx, p, st);
-    const size_t lds2s = std::max<size_t>(lds2, ((size_t)kS2StageWindow * 3 + 1 + S2.nh + kS2Chunk) * 4 + (size_t)kS2Chunk * 2);
+    const size_t lds2s = s2_scatter_bytes(S2.lds_window, S2.nh);
     hipLaunchKernelGGL(msm_s2_scatter, dim3(S2.B2), dim3(1024), lds2s, st, tagged, tagged_low, w.bin_start, w.hlo, w.woff, S2, w.hist2,
                        cx.starts.as<u32>(), cx.entries.as<u32>());
     return H2_OK;
@@ -783,40 +508,18 @@ template <int FB> static int slice_split_accumulate_fold(MsmContext &cx, const M
                        (const u32 *)(ssums + 32 * (size_t)sh.slices));
     return H2_OK;
 }
-// h2_commit_last_plan: the plan of a call over a registered table as plain integers (the caller holds cx.mu)
-static void record_plan(MsmContext &cx, const MsmPlan &p, u32 lanes) {
-    h2_commit_plan_t &r = cx.last_plan;
-    r = {};
-    r.caller = H2_COMMIT_CALLER_DIRECT;
-    r.caller_count = 1;
-    r.lanes = lanes;
-    r.c = (u32)p.sh.c; r.W = (u32)p.sh.W; r.m = (u32)p.m; r.K = p.K; r.T = p.T; r.lane_div = p.lane_div;
-    r.use_sort2 = p.use_sort2;
-    if (p.use_sort2) { r.s2_lowb = (u32)p.S2.lowb; r.s2_nh = p.S2.nh; r.s2_side = (u32)p.S2.side; r.s2_s1_scalars = p.S2.s1_scalars; }
-    r.s2_bins_form = p.s2_bins_form; r.max_big = p.max_big; r.zero_in_sort = p.zero_in_sort;
-    r.fold9 = p.fold9; r.wide_reduce = p.wide_reduce; r.pair = p.pair; r.joined = p.joined; r.add_only = p.add_only; r.fold_only = p.fold_only;
-}
-static void record_empty(MsmContext &cx, const MsmArgs &a, u32 kind) {
-    h2_commit_plan_t &r = cx.last_plan;
-    r = {};
-    r.caller = H2_COMMIT_CALLER_DIRECT;
-    r.caller_count = 1;
-    r.empty = kind;
-    r.c = (u32)a.c;
-    r.add_only = a.add_into != nullptr;
-}
 // One multiexp, or one phase of it (MsmArgs::phase): 1 = the sort; 2 = accumulate + fold behind a phase-1 sort; 3 = the accumulate; 4 = the fold.
 // The fold-only call (fold_from) is the 8 x 32 fold alone.
 template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a, hipStream_t st) {
     const bool empty = a.n_used + (a.d_extra_scalar ? 1 : 0) == 0;
-    if (empty && a.table && !a.fold_from) record_empty(cx, a, a.add_into ? 2u : 1u);
+    if (empty && a.table && !a.fold_from) cx.last_plan = empty_summary(a, a.add_into ? 2u : 1u);      // (h2_commit_last_plan; the caller holds cx.mu)
     if (empty && a.add_into) return H2_OK;           // an empty range adds nothing
     if (empty && !a.fold_from) return msm_empty<FB>(cx, a, st);
     int rc;
     u32 lanes = 0;
     if ((rc = msm_context_setup<FB>(cx, msm_m9(a), &lanes)) != H2_OK) return rc;
     MsmPlan p;
-    if ((rc = msm_plan(a, lanes, prof_enabled() || timeline_on(), &p)) != H2_OK) return rc;
+    if ((rc = msm_plan(a, lanes, prof_enabled() || timeline_on(), msm_knobs(a.lane_fraction), &p)) != H2_OK) return rc;
     if (p.try_grouped) {
         rc = msm_generic_grouped<FB, FS>(cx, a, p.sh, p.scalars_n, lanes, st);
         if (rc != H2_ERR_BATCH_SHAPE) return rc;
@@ -827,7 +530,7 @@ template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a
         cx.last.acc_lanes = p.T;
         cx.last.c = p.sh.c;
     }
-    if (a.table) record_plan(cx, p, lanes);                    // (h2_commit_last_plan)
+    if (a.table) cx.last_plan = plan_summary(p, lanes);        // (h2_commit_last_plan)
     if ((rc = msm_reserve(cx, p, st)) != H2_OK) return rc;
     // which stages this call runs (phases >= 2 resume behind a sort the phase-1 call enqueued and timed)
     const bool sorts = !p.fold_only && a.phase < 2, accumulates = !p.fold_only && a.phase != 1 && a.phase != 4, folds = a.phase != 1 && a.phase != 3;
@@ -882,11 +585,7 @@ using namespace h2;
 
 extern "C" int h2_msm_window_bits(size_t n) { return choose_c(n ? n : 1, false); }
 extern "C" int h2_commit_window_bits(size_t n) { return choose_c(n ? n : 1, true); }
-extern "C" int h2_commit_pair_supported(size_t n) {
-    int lowb, lb;
-    u32 nh, s1;
-    return n >= 8 && n <= (1u << 26) && pair_geometry(n, choose_c(n, true), (u32)n + 1, &lowb, &lb, &nh, &s1) ? 1 : 0;
-}
+extern "C" int h2_commit_pair_supported(size_t n) { return pair_supported(n, msm_knobs()) ? 1 : 0; }
 
 // copies up to `cap` {clock, tag} pairs recorded under H2_TIMELINE=1 (measurement aid, see the header)
 extern "C" int h2_debug_timeline(unsigned long long *out, unsigned cap) {
@@ -1003,12 +702,6 @@ extern "C" int h2_bases_set_blind_base(h2_bases_t g, const uint64_t *w_xy, int f
     return set_blind_base_host(*b, w_xy, form);
 }
 
-// Two commits from ONE column over a registered basis: column i < n - 4 belongs to output (i >> pair_shift) & 1, the last four
-// columns to outputs 0, 1, 0, 1.  The shape of a round of the opening argument written over the original generators
-// (poly/commitment/prover.rs:107-114; opening.py): L_j and R_j have disjoint supports in g (the low / high half of every
-// 2^(k-j) block), so their scalars share one column, and the basis g || u || u || w || w carries the [value z] U and
-// [rand] W terms of each.  One sort, one bucket accumulation into two slices, one fold: ~1.5 ms per round at k = 20 against
-// 2.0 ms for two half-empty commits.  d_out receives output 0 then output 1.
 // ---- batched commits: the columns of one prover phase (plonk/prover.rs:93-101, 301-313; vanishing/prover.rs:96-108)
 // are independent; spread them over internal streams so one column's latency-bound sort / reduce kernels run beside
 // another's accumulate, then join on the caller's stream.  Measured at 2^20 (ms per commit):
@@ -1020,7 +713,34 @@ struct BatchStreams {
     std::mutex mu;
     std::vector<hipStream_t> s;
     std::vector<hipEvent_t> done;
-    hipEvent_t fork = nullptr;
+    hipEvent_t fork_ev = nullptr;
+    // at least `want` streams, each with its `done` event, and the fork event
+    int ensure(size_t want) {
+        while (s.size() < want) {
+            hipStream_t st;
+            hipEvent_t ev;
+            H2_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            H2_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            s.push_back(st);
+            done.push_back(ev);
+        }
+        if (!fork_ev) H2_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+        return H2_OK;
+    }
+    // the first k streams wait for what `user` holds now
+    int fork(hipStream_t user, size_t k) {
+        H2_HIP(hipEventRecord(fork_ev, user));
+        for (size_t i = 0; i < k; ++i) H2_HIP(hipStreamWaitEvent(s[i], fork_ev, 0));
+        return H2_OK;
+    }
+    // ... and `user` for what they hold now
+    int join(hipStream_t user, size_t k) {
+        for (size_t i = 0; i < k; ++i) {
+            H2_HIP(hipEventRecord(done[i], s[i]));
+            H2_HIP(hipStreamWaitEvent(user, done[i], 0));
+        }
+        return H2_OK;
+    }
 };
 BatchStreams &batch_streams() {
     static BatchStreams b[16];
@@ -1040,15 +760,7 @@ extern "C" int h2_commit_batch_device(h2_bases_t g, const void *const *d_scalars
     std::lock_guard<std::mutex> lk(bs.mu);
     const size_t want = std::min<size_t>(3, count);
     const double fraction = 0.0;  // the process-wide option
-    while (bs.s.size() < want) {
-        hipStream_t st;
-        hipEvent_t ev;
-        H2_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        H2_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        bs.s.push_back(st);
-        bs.done.push_back(ev);
-    }
-    if (!bs.fork) H2_HIP(hipEventCreateWithFlags(&bs.fork, hipEventDisableTiming));
+    if ((rc = bs.ensure(want)) != H2_OK) return rc;
     hipStream_t user = (hipStream_t)stream;
     if (d_blinds) {  // a presented w is checked (and installed if it differs) ONCE, on the caller's stream, before forking
         auto b = find_bases(g);
@@ -1086,10 +798,7 @@ extern "C" int h2_commit_batch_device(h2_bases_t g, const void *const *d_scalars
             if (!d_scalars[i] || !d_outs[i] || (d_blinds && !d_blinds[i])) return H2_ERR_ARGS;
         const size_t groups = (count + batch_cols - 1) / batch_cols;
         const bool forked = groups > 1;
-        if (forked) {
-            H2_HIP(hipEventRecord(bs.fork, user));
-            for (size_t i = 0; i < 2; ++i) H2_HIP(hipStreamWaitEvent(bs.s[i], bs.fork, 0));
-        }
+        if (forked && bs.fork(user, 2) != H2_OK) return H2_ERR_HIP;
         bool taken = true;
         size_t first = 0;
         for (size_t gidx = 0; gidx < groups && rc == H2_OK; ++gidx) {
@@ -1113,24 +822,16 @@ extern "C" int h2_commit_batch_device(h2_bases_t g, const void *const *d_scalars
             }
             first += gsize;
         }
-        if (forked)
-            for (size_t i = 0; i < 2; ++i) {
-                H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
-                H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
-            }
+        if (forked && bs.join(user, 2) != H2_OK) return H2_ERR_HIP;
         if (taken && rc == H2_OK)          // h2_commit_last_plan on the caller's stream: the last group's plan and the groups it came in
             msm_hand_last_plan(forked ? bs.s[(groups - 1) & 1] : user, user, H2_COMMIT_CALLER_BATCH_COLUMNS, (u32)groups,
                                (u32)(count / groups + (count % groups ? 1 : 0)), (u32)(count / groups));
         if (taken || rc != H2_OK) return rc;
     }
-    H2_HIP(hipEventRecord(bs.fork, user));
-    for (size_t i = 0; i < want; ++i) H2_HIP(hipStreamWaitEvent(bs.s[i], bs.fork, 0));
+    if (bs.fork(user, want) != H2_OK) return H2_ERR_HIP;
     for (size_t i = 0; i < count && rc == H2_OK; ++i)
         rc = commit_device_impl(g, d_scalars[i], n, nullptr, d_blinds ? d_blinds[i] : nullptr, form, out_kind, d_outs[i], bs.s[i % want], true, fraction);
-    for (size_t i = 0; i < want; ++i) {
-        H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
-        H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
-    }
+    if (bs.join(user, want) != H2_OK) return H2_ERR_HIP;
     if (rc == H2_OK) msm_hand_last_plan(bs.s[(count - 1) % want], user, H2_COMMIT_CALLER_BATCH_FORK, (u32)count);
     return rc;
 }
@@ -1147,25 +848,13 @@ extern "C" int h2_msm_batch_device(int curve, const void *const *d_scalars, cons
     BatchStreams &bs = batch_streams();
     std::lock_guard<std::mutex> lk(bs.mu);
     const size_t want = std::min<size_t>(3, count);
-    while (bs.s.size() < want) {
-        hipStream_t st;
-        hipEvent_t ev;
-        H2_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        H2_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        bs.s.push_back(st);
-        bs.done.push_back(ev);
-    }
-    if (!bs.fork) H2_HIP(hipEventCreateWithFlags(&bs.fork, hipEventDisableTiming));
+    if ((rc = bs.ensure(want)) != H2_OK) return rc;
     hipStream_t user = (hipStream_t)stream;
-    H2_HIP(hipEventRecord(bs.fork, user));
-    for (size_t i = 0; i < want; ++i) H2_HIP(hipStreamWaitEvent(bs.s[i], bs.fork, 0));
+    if (bs.fork(user, want) != H2_OK) return H2_ERR_HIP;
     size_t ran = 0;
     for (size_t i = 0; i < count && rc == H2_OK; ++i, ++ran)
         rc = h2_msm_device(curve, d_scalars[i], d_bases_xy[i], n[i], form, out_kind, d_outs[i], bs.s[i % want]);
-    for (size_t i = 0; i < want; ++i) {
-        H2_HIP(hipEventRecord(bs.done[i], bs.s[i]));
-        H2_HIP(hipStreamWaitEvent(user, bs.done[i], 0));
-    }
+    if (bs.join(user, want) != H2_OK) return H2_ERR_HIP;
     if (rc == H2_OK && ran) {         // h2_msm_last_path on the caller's stream: the form of the last multiexp of the batch
         MsmContext::LastPath lp;
         {

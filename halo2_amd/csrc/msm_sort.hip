@@ -1018,7 +1018,7 @@ void sort2_pass2_bins(hipStream_t st, const u32 *tagged, const uint16_t *tagged_
                       u32 *starts, u32 *entries, u32 *big, u32 max_big, u32 *zero9, u32 cols, const ColStride &cs) {
     const size_t nbk = (size_t)1 << S2.lowb;
     u32 *gcnt = big + 64;
-    hipLaunchKernelGGL(msm_s2_bins, dim3(S2.nh, 1, cols), dim3(1024), (nbk * 2 + cap_entries) * 4, st, tagged, tagged_low, bin_start, S2, tb, (u32)cap_entries, starts,
+    hipLaunchKernelGGL(msm_s2_bins, dim3(S2.nh, 1, cols), dim3(1024), s2_bins_bytes(S2.lowb, cap_entries), st, tagged, tagged_low, bin_start, S2, tb, (u32)cap_entries, starts,
                        entries, big, max_big, zero9, cs);
     if (!max_big) return;
     // the oversized-bin kernels return at once when the list is empty (the common case).  256-lane workgroups: a 1024-lane

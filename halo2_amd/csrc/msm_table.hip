@@ -294,29 +294,14 @@ extern "C" int h2_bases_register(int curve, const uint64_t *bases_xy, size_t n, 
     return bases_register_impl(curve, bases_xy, false, n, form, handle);
 }
 
-// Window width for a table that only serves independent column commits (Params::g, g_lagrange): from 2^18 points on 17 bits --
-// 255 = 15 x 17, so a scalar leaves 15 digits instead of 16 (the top window of a scalar below q never exceeds 2^16, half the
-// window, so the signed recode carries nothing out of it): the accumulate is ~6 % shorter, the sort and
-// the fold (2^16 buckets) ~0.07 ms longer, which independent commits hide (953-966 against 925-939 M scalar-mults/s, one box,
-// one lone commit unchanged).  The paired commit and the collapsed-generator read-out of the opening argument take 16-bit
-// tables, which is what h2_bases_register keeps building.
+// Window width for a table that only serves independent column commits (column_window_bits, msm_plan.h)
 extern "C" int h2_commit_column_window_bits(size_t n) {
-    const int c = choose_c(n ? n : 1, true);
-    int lowb, lb;
-    if (const char *e = ab_env("H2_COLUMN_C")) {          // sweeps only (bench.py, bench/tools): the width column tables are built with
-        const int v = atoi(e);
-        if (v >= 4 && v <= kMaxCShared && (v <= kMaxC || (n + 1 < ((size_t)1 << 31) && sort2_geometry((u32)n + 1, v, &lowb, &lb)))) return v;
-    }
-    return c == 16 && n >= ((size_t)1 << 18) && n + 1 < ((size_t)1 << 31) && sort2_geometry((u32)n + 1, 17, &lowb, &lb) ? 17 : c;
+    const char *e = ab_env("H2_COLUMN_C");          // sweeps only (bench.py, bench/tools): the width column tables are built with
+    return column_window_bits(n, e ? atoi(e) : 0, msm_knobs());
 }
 
 extern "C" int h2_bases_register_ex(int curve, const uint64_t *bases_xy, size_t n, int form, int window_bits, h2_bases_t *handle) {
-    if (window_bits) {
-        int lowb, lb;
-        if (window_bits < 4 || window_bits > kMaxCShared ||
-            (window_bits > kMaxC && !(n + 1 < ((size_t)1 << 31) && sort2_geometry((u32)n + 1, window_bits, &lowb, &lb))))
-            return H2_ERR_ARGS;
-    }
+    if (window_bits && !register_width_ok(n, window_bits)) return H2_ERR_ARGS;
     return bases_register_impl(curve, bases_xy, false, n, form, handle, window_bits);
 }
 

@@ -1,6 +1,6 @@
 """What a commit over a registered basis decides before it launches anything, replicated on the host (a helper: nothing here is collected).
 
-`plan()` follows msm_plan (csrc/msm_launch.hip) for calls with a table; `expected()` wraps it in the caller forms of h2_commit,
+`plan()` follows msm_plan (csrc/msm_plan.h) for calls with a table; `expected()` wraps it in the caller forms of h2_commit,
 h2_commit_device, h2_commit_range_device, h2_commit_batch_device and h2_commit_pair_device and returns, field by field, what
 h2_commit_last_plan must answer.  The lanes of the accumulate kernel the device holds at once are an input (the GPU test takes them from the
 device's first answer); LANES_MI355X is what the CPU coverage test enumerates with.
@@ -34,7 +34,7 @@ def windows(c):
 
 
 def sort2_geometry(stride, c, want_s1=False):
-    """(lowb, lb, side, s1) or None: sort2_geometry of csrc/msm_launch.hip; want_s1 = the caller passes s1_out (msm_plan does, the
+    """(lowb, lb, side, s1) or None: sort2_geometry of csrc/msm_plan.h; want_s1 = the caller passes s1_out (msm_plan does, the
     registration check does not)"""
     W, bucket_bits = windows(c), c - 1
     top = W * stride - 1

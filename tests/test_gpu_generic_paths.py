@@ -3,11 +3,11 @@ the edges of its dispatch, with the form each call took read back through h2_msm
 
   ONE_PASS            below 65536 scalars (window bits 10 up to 2048 scalars, 13 above)
   TWO_PASS            65536 .. 2^18 scalars; every size from 65536 under h2_profile_enable (and H2_TIMELINE=1)
-  GROUPED_LATENCY     a lone call from 2^18 + 1 scalars (16-bit windows, 5 + 2 + 2 slices) while its layout fits: group_geometry below
+  GROUPED_LATENCY     a lone call from 2^18 + 1 scalars (16-bit windows, 5 + 2 + 2 slices) while its layout fits: group_geometry
   GROUPED_THROUGHPUT  another stream's call in flight, below 2^22 scalars, while the one-group layout fits
   SLICE_SPLIT         the sizes the grouped form declines (round 5's split of the window slices)
 
-The size limits of the grouped form come from a host replica of csrc/msm_generic.hip's group_geometry; the device's answer at each limit
+The size limits of the grouped form come from a host replica of group_geometry (csrc/msm_plan.h; the replica is tests/generic_plans.py); the device's answer at each limit
 checks the replica.  Bases repeat with an odd period (BASE_PERIOD) so that 5 M-point inputs cost one 2^20-point generation per curve; a
 column index that lost its high bits would still pick another base."""
 import ctypes as C
@@ -29,59 +29,7 @@ PATH = {k: int(v) for k, v in re.findall(r"#define H2_MSM_PATH_([A-Z_]+) (\d+)",
 ONE_PASS, TWO_PASS, SLICE_SPLIT = PATH["ONE_PASS"], PATH["TWO_PASS"], PATH["SLICE_SPLIT"]
 LATENCY, THROUGHPUT = PATH["GROUPED_LATENCY"], PATH["GROUPED_THROUGHPUT"]
 
-# ---- host replica of group_geometry (csrc/msm_generic.hip) and its constants (csrc/msm_internal.cuh)
-LDS_CAP = 160 * 1024 - 512          # kLdsCap
-NB16 = 1 << 15                      # buckets per window slice at 16-bit windows
-LATENCY_SLICES = (5, 2, 2)          # a lone call: nine slices, upper first
-THROUGHPUT_SLICES = (9,)
-
-
-def group_geometry(cols, ns, nb=NB16):
-    """(lowb, nh, S) of a group of `ns` window slices over `cols` digit columns, or None where msm_generic.hip's group_geometry fails."""
-    lb = (cols - 1).bit_length()
-    tb, emax = ns * nb, ns * cols
-    for lowb in range(12, 0, -1):
-        if lowb + lb > 31:
-            continue
-        nbk = 1 << lowb
-        nh = (tb + nbk - 1) >> lowb
-        if nh > 4096:
-            break
-        avg = emax // nh
-        cap_max = (LDS_CAP - nbk * 8) // 4 if nbk * 8 + 64 < LDS_CAP else 0
-        cap = min(cap_max, max(4096, avg * 5 // 4 + 1024))
-        if avg > 20000 or avg > cap * 9 // 10:
-            continue
-        S = 4096
-        while S > 512 and (nh * 3 + 1 + S * ns) * 4 > LDS_CAP // 2:
-            S //= 2
-        if S == 4096 and cols // 8192 >= 512 and (nh * 3 + 1 + 8192 * ns) * 4 <= LDS_CAP:
-            S = 8192
-        if (nh * 3 + 1 + S * ns) * 4 > LDS_CAP:
-            continue
-        return lowb, nh, S
-    return None
-
-
-def layout(n, slices):
-    g = [group_geometry(2 * n, ns) for ns in slices]
-    return None if None in g else g
-
-
-def _first(pred, lo, hi):
-    """smallest n in (lo, hi] with pred(n), pred monotone and false at lo"""
-    assert not pred(lo) and pred(hi)
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (lo, mid) if pred(mid) else (mid, hi)
-    return hi
-
-
-LATENCY_MAX = _first(lambda n: layout(n, LATENCY_SLICES) is None, 1 << 20, 1 << 24) - 1
-THROUGHPUT_MAX = _first(lambda n: layout(n, THROUGHPUT_SLICES) is None, 1 << 19, 1 << 23) - 1
-_low = lambda n: layout(n, LATENCY_SLICES)[0][0]                       # pass-1 low key bits of the latency layout's first group
-LOWB_7 = _first(lambda n: _low(n) <= 7, (1 << 18) + 1, LATENCY_MAX)     # 8 -> 7
-LOWB_6 = _first(lambda n: _low(n) <= 6, LOWB_7, LATENCY_MAX)            # 7 -> 6
+from generic_plans import LATENCY_MAX, LOWB_6, LOWB_7, THROUGHPUT_MAX, _low      # the host replica of group_geometry and the limits it gives
 
 
 def test_replica_limits_match_the_documented_ones():
