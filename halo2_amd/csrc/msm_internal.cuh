@@ -22,24 +22,16 @@
 #include "glv.cuh"
 #include "host_field.h"
 #include "msm_plan.h"      // the planning constants and structures, msm_plan / grouped_plan and the geometries: plain C++
+#include "msm_digits.h"    // the window digits of a scalar and their codes (kZeroCode, kZero32): plain C++
 namespace h2 {
 
 extern std::atomic<double> g_lane_fraction;      // h2_set_option("msm_lane_fraction")
 extern std::atomic<size_t> g_pipe_chunk;         // h2_set_option("host_commit_chunk"): sweeps only
-static constexpr u32 kZeroCode = 0xFFFFu;
-static constexpr u32 kZero32 = 0xFFFFFFFFu;
 
 // msm_launch.hip: the laboratory's switches (read once; H2_MSM_C at every call, as a test sets it around one registration) and the lane
 // fraction of this call (`lane_fraction` if positive, else h2_set_option's); the window width under them
 MsmKnobs msm_knobs(double lane_fraction = 0.0);
 inline int choose_c(size_t n, bool shared_buckets) { return choose_c(n, shared_buckets, msm_knobs()); }
-
-__device__ __forceinline__ u32 limb_at(const fe &s, int idx) {
-    u32 v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) v = (idx == i) ? s.v[i] : v;
-    return v;
-}
 
 // The sort and tail stages are short dependent chains; when another stream's msm_accumulate shares the SIMDs they
 // must win issue arbitration or they stretch 3-4x and the stream they belong to feeds the chip late (timeline in
@@ -304,20 +296,20 @@ int bases_register_device_internal(int curve, const void *d_bases_xy, size_t n, 
 #endif
 
 // ---- kernels defined in msm_sort.hip -------------------------------------------------------------------------------------------
+// A templated kernel's instances are listed ONCE, beside its declaration, as H2_INSTANCES_<kernel>(X): expanded here as `extern template`
+// and at the foot of msm_sort.hip as the explicit instantiations (the signature comes from the declaration).
+#define H2_EXTERN_KERNEL(...) extern template __global__ decltype(__VA_ARGS__) __VA_ARGS__;
+#define H2_INSTANTIATE_KERNEL(...) template __global__ decltype(__VA_ARGS__) __VA_ARGS__;
 template <int FS>
 __global__ void __launch_bounds__(256) msm_recode(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar,
                                                   uint16_t *__restrict__ digits, u32 m, int c, int W, int mont);
-extern template __global__ void msm_recode<FP>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar,
-                                                  uint16_t *__restrict__ digits, u32 m, int c, int W, int mont);
-extern template __global__ void msm_recode<FQ>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar,
-                                                  uint16_t *__restrict__ digits, u32 m, int c, int W, int mont);
+#define H2_INSTANCES_msm_recode(X) X(msm_recode<FP>) X(msm_recode<FQ>)
+H2_INSTANCES_msm_recode(H2_EXTERN_KERNEL)
 template <int FS>
 __global__ void __launch_bounds__(256) msm_recode_glv(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, int c, int W,
                                                       int mont);
-extern template __global__ void msm_recode_glv<FP>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, int c, int W,
-                                                      int mont);
-extern template __global__ void msm_recode_glv<FQ>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, int c, int W,
-                                                      int mont);
+#define H2_INSTANCES_msm_recode_glv(X) X(msm_recode_glv<FP>) X(msm_recode_glv<FQ>)
+H2_INSTANCES_msm_recode_glv(H2_EXTERN_KERNEL)
 __global__ void __launch_bounds__(1024) msm_count(const uint16_t *__restrict__ digits, u32 *__restrict__ hist,
                                                   size_t items, u32 chunk, u32 NB);
 __global__ void __launch_bounds__(256) msm_chunk_prefix(u32 *__restrict__ hist, u32 *__restrict__ counts, u32 NB,
@@ -335,35 +327,15 @@ __global__ void __launch_bounds__(1024) msm_scatter(const uint16_t *__restrict__
 template <int FS, bool GLV>
 __global__ void __launch_bounds__(1024) msm_s1_count(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
                                                      u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_count<FP, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_count<FP, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_count<FQ, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_count<FQ, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
+#define H2_INSTANCES_msm_s1_count(X) X(msm_s1_count<FP, false>) X(msm_s1_count<FP, true>) X(msm_s1_count<FQ, false>) X(msm_s1_count<FQ, true>)
+H2_INSTANCES_msm_s1_count(H2_EXTERN_KERNEL)
 template <int FS, bool GLV>
 __global__ void __launch_bounds__(1024) msm_s1_scatter(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
                                                        const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
                                                        u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
                                                        ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_scatter<FP, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_scatter<FP, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_scatter<FQ, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-extern template __global__ void msm_s1_scatter<FQ, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
+#define H2_INSTANCES_msm_s1_scatter(X) X(msm_s1_scatter<FP, false>) X(msm_s1_scatter<FP, true>) X(msm_s1_scatter<FQ, false>) X(msm_s1_scatter<FQ, true>)
+H2_INSTANCES_msm_s1_scatter(H2_EXTERN_KERNEL)
 __global__ void __launch_bounds__(1024) msm_s1_prefix(u32 *__restrict__ hist1, u32 *__restrict__ bin_count, u32 B1, u32 nh, u32 *__restrict__ z2,
                                                       u32 *__restrict__ z1, u32 *__restrict__ sentinel, ColStride cs);
 __global__ void __launch_bounds__(kScanBlock) msm_s2_plan(const u32 *__restrict__ bin_start, Sort2 P, u32 *__restrict__ hlo,
@@ -387,8 +359,8 @@ __global__ void __launch_bounds__(256) msm_s2_prefix(u32 *__restrict__ hist2, co
                                                      const u32 *__restrict__ woff, Sort2 P, u32 *__restrict__ counts, u32 NB);
 template <int FS>
 __global__ void __launch_bounds__(256) msm_glv_digits(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
-extern template __global__ void msm_glv_digits<FP>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
-extern template __global__ void msm_glv_digits<FQ>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
+#define H2_INSTANCES_msm_glv_digits(X) X(msm_glv_digits<FP>) X(msm_glv_digits<FQ>)
+H2_INSTANCES_msm_glv_digits(H2_EXTERN_KERNEL)
 __global__ void __launch_bounds__(512) msm_d1_count(const uint16_t *__restrict__ digits, GroupSort P, u32 *__restrict__ hist1);
 __global__ void __launch_bounds__(512) msm_d1_scatter(const uint16_t *__restrict__ digits, GroupSort P, const u32 *__restrict__ hist1,
                                                       const u32 *__restrict__ bin_count, u32 *__restrict__ bin_start, u32 *__restrict__ tagged);

@@ -15,22 +15,8 @@ __global__ void __launch_bounds__(256) msm_recode(const u32 *__restrict__ scalar
     if (i >= m) return;
     fe s = (extra_scalar && i == m - 1) ? fe_load(extra_scalar) : fe_load(scalars + 8 * (size_t)i);
     if (mont) s = fe_from_mont<FS>(s);
-    u32 carry = 0;
-    const u32 mask = (1u << c) - 1, half = 1u << (c - 1);
-    for (int w = 0; w < W; ++w) {
-        int bit = w * c, word = bit >> 5, sh = bit & 31;
-        u64 two = (u64)limb_at(s, word) | ((u64)limb_at(s, word + 1) << 32);  // limb_at(.., 8) = 0
-        u32 raw = ((u32)(two >> sh) & mask) + carry;
-        u32 code;
-        if (raw > half) {
-            carry = 1;
-            code = ((1u << c) - raw - 1) | 0x8000u;   // d = raw - 2^c <= 0: |d| - 1 (d = 0 wraps to 0xFFFF)
-        } else {
-            carry = 0;
-            code = raw ? raw - 1 : kZeroCode;
-        }
-        digits[(size_t)w * m + i] = (uint16_t)code;
-    }
+    // the run-time width whatever c is: this kernel serves small problems
+    for_each_digit_runtime(s.v, c, W, [&](int w, u32 code) { digits[(size_t)w * m + i] = (uint16_t)narrow_code(code); });
 }
 
 // ---- recode with the endomorphism split (generic path): scalar i yields two columns of signed digits, column i for k1
@@ -46,31 +32,10 @@ __global__ void __launch_bounds__(256) msm_recode_glv(const u32 *__restrict__ sc
     if (mont) s = fe_from_mont<FS>(s);
     u32 mag[2][5], neg[2];
     glv_split<FS>(s, mag[0], neg[0], mag[1], neg[1]);
-    const u32 mask = (1u << c) - 1, half = 1u << (c - 1);
     const size_t M = 2 * (size_t)m;
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-        u32 carry = 0;
-        for (int w = 0; w < W; ++w) {
-            const int bit = w * c, word = bit >> 5, sh = bit & 31;
-            u32 lo = 0, hi = 0;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                lo = (word == q) ? mag[part][q] : lo;
-                hi = (word + 1 == q) ? mag[part][q] : hi;
-            }
-            const u64 two = (u64)lo | ((u64)hi << 32);
-            const u32 raw = ((u32)(two >> sh) & mask) + carry;
-            // digits of |k_part| in [-half + 1, half] (or [-half, half - 1] when the part is negative, so that after the
-            // sign flip every digit is again in the encodable set: the code has no room for -half)
-            const bool up = neg[part] ? raw >= half : raw > half;
-            carry = up;
-            const u32 digit_mag = up ? (1u << c) - raw : raw;     // 0 when raw = 0 or raw = 2^c
-            const u32 negative = (up ? 1u : 0u) ^ neg[part];
-            const u32 code = digit_mag ? ((digit_mag - 1) | (negative ? 0x8000u : 0u)) : kZeroCode;
-            digits[(size_t)w * M + (size_t)part * m + i] = (uint16_t)code;
-        }
-    }
+    for_each_glv_digit(mag, neg, c, W, [&](int part, int w, u32 digit_mag, u32 negative) {
+        digits[(size_t)w * M + (size_t)part * m + i] = (uint16_t)digit_code16(digit_mag, negative);
+    });
 }
 
 // ---- count: LDS histogram per (slice, chunk) ---------------------------------------------------
@@ -193,46 +158,6 @@ __global__ void __launch_bounds__(1024) msm_scatter(const uint16_t *__restrict__
     }
 }
 
-// signed window digits of one scalar (same recoding as msm_recode, 32-bit codes so that windows may exceed 16 bits),
-// handed to f(w, code): code = kZero32 for digit 0, else (|d| - 1) | (d < 0) << 31
-template <int C, typename Fn> __device__ __forceinline__ void for_each_digit_static(const fe &s, Fn f) {
-    constexpr int W = 255 / C + 1;
-    constexpr u32 mask = (1u << C) - 1, half = 1u << (C - 1), full = 1u << C;
-    u32 carry = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        constexpr int dummy = 0;
-        (void)dummy;
-        const int bit = w * C, word = bit >> 5, sh = bit & 31;     // compile-time after unrolling: plain register picks
-        u32 v = s.v[word] >> sh;
-        if (sh + C > 32 && word + 1 < 8) v |= s.v[word + 1] << (32 - sh);
-        const u32 raw = (v & mask) + carry;
-        carry = raw > half;
-        const u32 code = carry ? (raw == full ? kZero32 : ((full - raw - 1) | 0x80000000u)) : (raw ? raw - 1 : kZero32);   // raw = 2^C: digit 0, carry out
-        f(w, code);
-    }
-}
-template <typename Fn> __device__ __forceinline__ void for_each_digit(const fe &s, int c, int W, Fn f) {
-    // compile-time widths: the limb picks become plain register selects (the generic loop below indexes the limbs dynamically: at
-    // c = 17 the pass-1 kernels took 29 + 78 us against 16 + 53 us for the unrolled c = 20)
-    if (c == 16) { for_each_digit_static<16>(s, f); return; }
-    if (c == 17) { for_each_digit_static<17>(s, f); return; }
-    if (c == 18) { for_each_digit_static<18>(s, f); return; }
-    if (c == 19) { for_each_digit_static<19>(s, f); return; }
-    if (c == 20) { for_each_digit_static<20>(s, f); return; }
-    if (c == 13) { for_each_digit_static<13>(s, f); return; }
-    u32 carry = 0;
-    const u32 mask = (1u << c) - 1, half = 1u << (c - 1), full = 1u << c;
-    for (int w = 0; w < W; ++w) {
-        int bit = w * c, word = bit >> 5, sh = bit & 31;
-        u64 two = (u64)limb_at(s, word) | ((u64)limb_at(s, word + 1) << 32);
-        const u32 raw = ((u32)(two >> sh) & mask) + carry;
-        carry = raw > half;
-        const u32 code = carry ? (raw == full ? kZero32 : ((full - raw - 1) | 0x80000000u)) : (raw ? raw - 1 : kZero32);
-        f(w, code);
-    }
-}
-
 // every non-zero window digit of scalar i as f(sort key, entry base index, sign << 31).
 // Registered path: key = bucket (one slice), base = w * stride + column.  Generic path (GLV): the scalar is split
 // (glv.cuh), key = w * nb + bucket (slice-major), base = digit column (i for k1 / P_i, m + i for k2 / phi(P_i)).
@@ -243,13 +168,16 @@ __device__ __forceinline__ void emit_entries(const fe &s, u32 i, const Sort2 &P,
         if (i == P.m - 1 && P.extra_col != 0xFFFFFFFFu) col = P.extra_col;
         u32 side_key = 0;
         if (P.pair_shift >= 0) side_key = (i < P.pair_n ? (i >> P.pair_shift) & 1u : (i - P.pair_n) & 1u) * P.nb;
-        for_each_digit(s, P.c, P.W, [&](int w, u32 code) {
+        for_each_digit(s.v, P.c, P.W, [&](int w, u32 code) {
             if (code != kZero32) f(side_key + (code & 0x7FFFFFFFu), (u32)w * P.stride + col, code & 0x80000000u, (u32)w);
         });
         return;
     }
     u32 mag[2][5], neg[2];
     glv_split<FS>(s, mag[0], neg[0], mag[1], neg[1]);
+    // msm_digits.h's for_each_glv_digit, written out: in front of the shared cutter the compiler allocates glv_split with twenty more register
+    // moves per scalar, and msm_s1_count<., true> measured 0.8 - 1.6 % slower (profiles/msm_sort_digits_ab.txt).  The CPU test of the header
+    // does not reach this copy: it is checked only through whole multiexps on a device (the generic two-pass tests).
     const int c = P.c;
     const u32 mask = (1u << c) - 1, half = 1u << (c - 1);
 #pragma unroll
@@ -264,7 +192,7 @@ __device__ __forceinline__ void emit_entries(const fe &s, u32 i, const Sort2 &P,
                 hi = (word + 1 == q) ? mag[part][q] : hi;
             }
             const u32 raw = ((u32)(((u64)lo | ((u64)hi << 32)) >> sh) & mask) + carry;
-            const bool up = neg[part] ? raw >= half : raw > half;      // same digit set as msm_recode_glv
+            const bool up = neg[part] ? raw >= half : raw > half;      // the rule of for_each_glv_digit
             carry = up;
             const u32 digit_mag = up ? (1u << c) - raw : raw;
             if (digit_mag) f((u32)w * P.nb + digit_mag - 1, (u32)part * P.m + i, (((up ? 1u : 0u) ^ neg[part]) << 31), (u32)w);
@@ -484,6 +412,20 @@ __device__ __forceinline__ u32 rel_bin(const u32 *bounds, u32 nbins, u32 p) {
 __device__ __forceinline__ u32 s2_low(const Sort2 &P, const uint16_t *__restrict__ low, u32 p, u32 e, u32 lowmask) {
     return P.side ? (u32)low[p] : (e >> P.lb) & lowmask;
 }
+// bucket of tagged entry p relative to its chunk's window (chunked pass 2): the entry's bin among the chunk's, then the low bits
+__device__ __forceinline__ u32 s2_key(const Sort2 &P, const u32 *bounds, u32 nbins, const uint16_t *__restrict__ low, u32 p, u32 e, u32 lowmask) {
+    return (rel_bin(bounds, nbins, p) << P.lowb) | s2_low(P, low, p, e, lowmask);
+}
+// four consecutive tagged entries [base, base + 4) below `end` and their low bucket bits: four loads in flight per lane instead of one.
+// Returns how many are valid (the others read as 0).
+__device__ __forceinline__ u32 s2_read4(const Sort2 &P, const u32 *__restrict__ tagged, const uint16_t *__restrict__ low, u32 base, u32 end, u32 lowmask,
+                                        u32 e[4], u32 k[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = base + j < end ? tagged[base + j] : 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) k[j] = base + j < end ? s2_low(P, low, base + j, e[j], lowmask) : 0u;
+    return min(4u, end - base);
+}
 
 // pass 2, COUNT over one chunk of the tagged list: hist2[woff[c] + (bucket - window base)]
 __global__ void __launch_bounds__(1024) msm_s2_count(const u32 *__restrict__ tagged, const uint16_t *__restrict__ tagged_low, const u32 *__restrict__ bin_start,
@@ -502,7 +444,7 @@ __global__ void __launch_bounds__(1024) msm_s2_count(const u32 *__restrict__ tag
         const u32 *gb = bin_start + h0 + 1;
         for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
             const u32 e = tagged[p];
-            atomicAdd(&hist2[wo + ((rel_bin(gb, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask))], 1u);
+            atomicAdd(&hist2[wo + s2_key(P, gb, nbins, tagged_low, p, e, lowmask)], 1u);
         }
         return;
     }
@@ -512,7 +454,7 @@ __global__ void __launch_bounds__(1024) msm_s2_count(const u32 *__restrict__ tag
     __syncthreads();
     for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
         const u32 e = tagged[p];
-        atomicAdd(&sh[(rel_bin(bounds, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask)], 1u);
+        atomicAdd(&sh[s2_key(P, bounds, nbins, tagged_low, p, e, lowmask)], 1u);
     }
     __syncthreads();
     for (u32 k = threadIdx.x; k < wsize; k += blockDim.x) hist2[wo + k] = sh[k];
@@ -537,7 +479,7 @@ __global__ void __launch_bounds__(1024) msm_s2_scatter(const u32 *__restrict__ t
         const u32 *gb = bin_start + h0 + 1;
         for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
             const u32 e = tagged[p];
-            const u32 k = (rel_bin(gb, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask);
+            const u32 k = s2_key(P, gb, nbins, tagged_low, p, e, lowmask);
             entries[starts[(h0 << P.lowb) + k] + atomicAdd(&hist2[wo + k], 1u)] = e & strip;
         }
         return;
@@ -549,7 +491,7 @@ __global__ void __launch_bounds__(1024) msm_s2_scatter(const u32 *__restrict__ t
         __syncthreads();
         for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
             const u32 e = tagged[p];
-            const u32 pos = atomicAdd(&sh[(rel_bin(bounds, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask)], 1u);
+            const u32 pos = atomicAdd(&sh[s2_key(P, bounds, nbins, tagged_low, p, e, lowmask)], 1u);
             entries[pos] = e & strip;
         }
         return;
@@ -568,7 +510,7 @@ __global__ void __launch_bounds__(1024) msm_s2_scatter(const u32 *__restrict__ t
     __syncthreads();
     for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
         const u32 e = tagged[p];
-        atomicAdd(&lstart[(rel_bin(bounds, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask)], 1u);
+        atomicAdd(&lstart[s2_key(P, bounds, nbins, tagged_low, p, e, lowmask)], 1u);
     }
     __syncthreads();
     if (threadIdx.x < 64) {
@@ -580,7 +522,7 @@ __global__ void __launch_bounds__(1024) msm_s2_scatter(const u32 *__restrict__ t
     __syncthreads();
     for (u32 p = (u32)p0 + threadIdx.x; p < p1; p += blockDim.x) {
         const u32 e = tagged[p];                                 // second read of the chunk comes from L2
-        const u32 k = (rel_bin(bounds, nbins, p) << P.lowb) | s2_low(P, tagged_low, p, e, lowmask);
+        const u32 k = s2_key(P, bounds, nbins, tagged_low, p, e, lowmask);
         const u32 pos = atomicAdd(&cursor[k], 1u);
         stage[pos] = e & strip;
         kid[pos] = (uint16_t)k;
@@ -685,13 +627,9 @@ __global__ void __launch_bounds__(1024) msm_s2_bins(const u32 *__restrict__ tagg
     // every scalar equal, or half of them 1 -- holds up to 2^20 entries and is streamed by this one workgroup, twice)
     const u32 step = blockDim.x * 4;
     for (u32 base = p0 + threadIdx.x * 4; base < p1; base += step) {
-        u32 e[4], k[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = base + j < p1 ? tagged[base + j] : 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k[j] = base + j < p1 ? s2_low(P, tagged_low, base + j, e[j], lowmask) : 0u;
-        u32 pos[4];
-        lds_ticket4(cnt, k, min(4u, p1 - base), pos);
+        u32 e[4], k[4], pos[4];
+        const u32 nvalid = s2_read4(P, tagged, tagged_low, base, p1, lowmask, e, k);
+        lds_ticket4(cnt, k, nvalid, pos);
     }
     __syncthreads();
     if (threadIdx.x < 64) (void)wave0_excl_scan(cnt, nbk);              // cnt[k] = entries of the bin before bucket k
@@ -705,13 +643,9 @@ __global__ void __launch_bounds__(1024) msm_s2_bins(const u32 *__restrict__ tagg
     const bool fits = E <= cap;
     for (u32 base = p0 + threadIdx.x * 4; base < p1; base += step) {    // second read of the bin: L2 (a bin beyond the stage that found no
                                                                         // slot on the big-bin list: scattered by this workgroup alone)
-        u32 e[4], k[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = base + j < p1 ? tagged[base + j] : 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k[j] = base + j < p1 ? s2_low(P, tagged_low, base + j, e[j], lowmask) : 0u;
-        u32 pos[4];
-        lds_ticket4(cursor, k, min(4u, p1 - base), pos);
+        u32 e[4], k[4], pos[4];
+        const u32 nvalid = s2_read4(P, tagged, tagged_low, base, p1, lowmask, e, k);
+        lds_ticket4(cursor, k, nvalid, pos);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (base + j < p1) {
@@ -748,11 +682,8 @@ __global__ void __launch_bounds__(1024) msm_s2_big_count(const u32 *__restrict__
     __syncthreads();
     for (u32 base = a + threadIdx.x * 4; base < b; base += blockDim.x * 4) {
         u32 e[4], k[4], pos[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = base + j < b ? tagged[base + j] : 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k[j] = base + j < b ? s2_low(P, tagged_low, base + j, e[j], lowmask) : 0u;
-        lds_ticket4(sh, k, min(4u, b - base), pos);
+        const u32 nvalid = s2_read4(P, tagged, tagged_low, base, b, lowmask, e, k);
+        lds_ticket4(sh, k, nvalid, pos);
     }
     __syncthreads();
     u32 *dst = gcnt + ((size_t)s * kBigChunks + c) * nbk;
@@ -820,11 +751,8 @@ __global__ void __launch_bounds__(1024) msm_s2_big_scatter(const u32 *__restrict
     __syncthreads();
     for (u32 base = a + threadIdx.x * 4; base < b; base += blockDim.x * 4) {
         u32 e[4], k[4], pos[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = base + j < b ? tagged[base + j] : 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k[j] = base + j < b ? s2_low(P, tagged_low, base + j, e[j], lowmask) : 0u;
-        lds_ticket4(sh, k, min(4u, b - base), pos);
+        const u32 nvalid = s2_read4(P, tagged, tagged_low, base, b, lowmask, e, k);
+        lds_ticket4(sh, k, nvalid, pos);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (base + j < b) entries[cb + p0 + pos[j]] = e[j] & strip;
@@ -872,26 +800,9 @@ __global__ void __launch_bounds__(256) msm_glv_digits(const u32 *__restrict__ sc
     if (mont) s = fe_redc<FS>(s);
     u32 mag[2][5], neg[2];
     glv_split<FS>(s, mag[0], neg[0], mag[1], neg[1]);
-    const u32 mask = (1u << c) - 1, half = 1u << (c - 1);
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-        u32 carry = 0;
-        for (int w = 0; w < W; ++w) {
-            const int bit = w * c, word = bit >> 5, sh = bit & 31;
-            u32 lo = 0, hi = 0;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                lo = (word == q) ? mag[part][q] : lo;
-                hi = (word + 1 == q) ? mag[part][q] : hi;
-            }
-            const u32 raw = ((u32)(((u64)lo | ((u64)hi << 32)) >> sh) & mask) + carry;
-            const bool up = neg[part] ? raw >= half : raw > half;      // same digit set as msm_recode_glv / emit_entries
-            carry = up;
-            const u32 digit_mag = up ? (1u << c) - raw : raw;
-            const u32 negative = (up ? 1u : 0u) ^ neg[part];
-            digits[(size_t)w * row + (size_t)part * m + i] = (uint16_t)(digit_mag ? ((digit_mag - 1) | (negative ? 0x8000u : 0u)) : kZeroCode);
-        }
-    }
+    for_each_glv_digit(mag, neg, c, W, [&](int part, int w, u32 digit_mag, u32 negative) {
+        digits[(size_t)w * row + (size_t)part * m + i] = (uint16_t)digit_code16(digit_mag, negative);
+    });
 }
 
 // pass 1 of a group, COUNT: workgroup `blk` owns digit columns [blk S, (blk + 1) S) of the group's ns rows; hist1[blk][h] = its entries per bin
@@ -976,42 +887,12 @@ __global__ void __launch_bounds__(512) msm_d1_scatter(const uint16_t *__restrict
     }
 }
 
-// ---- explicit instantiations (both curves): the host side lives in msm_launch.hip / msm_generic.hip ----
-template __global__ void msm_recode<FP>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar,
-                                                  uint16_t *__restrict__ digits, u32 m, int c, int W, int mont);
-template __global__ void msm_recode<FQ>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar,
-                                                  uint16_t *__restrict__ digits, u32 m, int c, int W, int mont);
-template __global__ void msm_recode_glv<FP>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, int c, int W,
-                                                      int mont);
-template __global__ void msm_recode_glv<FQ>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, int c, int W,
-                                                      int mont);
-template __global__ void msm_s1_count<FP, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-template __global__ void msm_s1_count<FP, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-template __global__ void msm_s1_count<FQ, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-template __global__ void msm_s1_count<FQ, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                     u32 *__restrict__ hist1, ColIn ci, ColStride cs);
-template __global__ void msm_s1_scatter<FP, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-template __global__ void msm_s1_scatter<FP, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-template __global__ void msm_s1_scatter<FQ, false>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-template __global__ void msm_s1_scatter<FQ, true>(const u32 *__restrict__ scalars, const u32 *__restrict__ extra_scalar, Sort2 P,
-                                                       const u32 *__restrict__ hist1, const u32 *__restrict__ bin_count,
-                                                       u32 *__restrict__ bin_start, u32 *__restrict__ tagged, uint16_t *__restrict__ tagged_low,
-                                                       ColIn ci, ColStride cs);
-
-template __global__ void msm_glv_digits<FP>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
-template __global__ void msm_glv_digits<FQ>(const u32 *__restrict__ scalars, uint16_t *__restrict__ digits, u32 m, u32 row, int c, int W, int mont);
+// ---- explicit instantiations (the lists beside the declarations in msm_internal.cuh): the host side lives in msm_launch.hip / msm_generic.hip ----
+H2_INSTANCES_msm_recode(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_recode_glv(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_s1_count(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_s1_scatter(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_glv_digits(H2_INSTANTIATE_KERNEL)
 
 // ---- host: the one-launch pass 2 and its oversized-bin followers, for every caller (declared in msm_internal.cuh)
 void sort2_pass2_bins(hipStream_t st, const u32 *tagged, const uint16_t *tagged_low, const u32 *bin_start, const Sort2 &S2, u32 tb, size_t cap_entries,
