@@ -119,6 +119,11 @@ struct ScratchContext {
 };
 
 inline unsigned grid_of(size_t n, unsigned lanes) { return (unsigned)((n + lanes - 1) / lanes); }   // workgroups of `lanes` for n lanes
+inline int ceil_log2(size_t n) {                                                                    // the least l with 2^l >= n
+    int l = 0;
+    while (((size_t)1 << l) < n) ++l;
+    return l;
+}
 
 // The two-pass scheme of the witness traces (the head of sinsemilla.hip): pass A stores `per_lane` Fp products of denominators for
 // each of `count` lanes, h2_batch_invert_device inverts them in place, pass B finds the inverses where the products were.  The lanes

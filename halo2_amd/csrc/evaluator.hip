@@ -17,25 +17,11 @@
 #include <vector>
 
 #include "common.h"
+#include "evaluator.cuh"
 #include "field.cuh"
 #include "host_field.h"
 
 namespace h2 {
-
-enum : u32 { EV_POLY = 1, EV_CONST = 2, EV_LINEAR = 3, EV_ADD = 4, EV_MUL = 5, EV_SCALE = 6, EV_MULADD = 7 };
-constexpr int kEvalDepth = 8;      // stack slots below the register-resident top
-constexpr int kEvalThreads = 256;
-
-__device__ __forceinline__ void ev_spill(u32 *lds, int level, const fe &v) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) lds[(level * 8 + w) * kEvalThreads + threadIdx.x] = v.v[w];
-}
-__device__ __forceinline__ fe ev_fill(const u32 *lds, int level) {
-    fe v;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) v.v[w] = lds[(level * 8 + w) * kEvalThreads + threadIdx.x];
-    return v;
-}
 
 // basis: 0 coefficient, 1 Lagrange, 2 extended Lagrange.  tw: omega^0 .. omega^(len/2 - 1) (Montgomery) or null when the
 // program has no LINEAR node.
@@ -106,50 +92,9 @@ extern "C" int h2_evaluate_device(int field, int basis, const uint32_t *program,
     if ((field != H2_FP && field != H2_FQ) || basis < 0 || basis > 2 || !program || n_words == 0 || n_words > (1u << 20) || !d_out ||
         log_len > 30 || (n_consts && !consts) || (n_polys && !d_polys))
         return H2_ERR_ARGS;
-    // validate the program: operands in range, stack discipline, rotations and products only where the reference allows them
     const size_t len = (size_t)1 << log_len;
-    int depth = 0, max_depth = 0;
     bool has_linear = false;
-    for (size_t pc = 0; pc < n_words; ++pc) {
-        const uint32_t op = program[pc] & 0xFFu, arg = program[pc] >> 8;
-        switch (op) {
-            case EV_POLY: {
-                if (arg >= n_polys || pc + 1 >= n_words || !d_polys[arg]) return H2_ERR_ARGS;
-                const long long shift = (int)program[++pc];
-                // |shift| == len is the identity; beyond it the reference panics (poly.rs:251, :256: assert!(k <= self.len()))
-                if (shift < -(long long)len || shift > (long long)len) return H2_ERR_ARGS;
-                if (basis == 0 && shift != 0) return H2_ERR_ARGS;      // "Can't rotate polynomials in the standard basis" (:519)
-                ++depth;
-                break;
-            }
-            case EV_LINEAR:
-                has_linear = true;
-                [[fallthrough]];
-            case EV_CONST:
-                if (arg >= n_consts) return H2_ERR_ARGS;
-                ++depth;
-                break;
-            case EV_SCALE:
-                if (arg >= n_consts || depth < 1) return H2_ERR_ARGS;
-                break;
-            case EV_MUL:
-                // Mul exists for Ast<_, _, LagrangeCoeff> and Ast<_, _, ExtendedLagrangeCoeff> (evaluator.rs:370-418)
-                if (basis == 0) return H2_ERR_ARGS;
-                [[fallthrough]];
-            case EV_ADD:
-                if (depth < 2) return H2_ERR_ARGS;
-                --depth;
-                break;
-            case EV_MULADD:
-                if (arg >= n_consts || depth < 2) return H2_ERR_ARGS;
-                --depth;
-                break;
-            default:
-                return H2_ERR_ARGS;
-        }
-        max_depth = std::max(max_depth, depth);
-    }
-    if (depth != 1 || max_depth > kEvalDepth + 1) return H2_ERR_ARGS;
+    if (!ev_program_ok(program, 0, n_words, n_consts, d_polys, n_polys, len, basis, &has_linear)) return H2_ERR_ARGS;
     if (has_linear && basis != 0 && !omega) return H2_ERR_ARGS;
     int rc = ensure_device();
     if (rc != H2_OK) return rc;
@@ -169,12 +114,8 @@ extern "C" int h2_evaluate_device(int field, int basis, const uint32_t *program,
     if (n_polys) H2_HIP(hipMemcpyAsync(cx.ptrs.ptr, d_polys, n_polys * 8, hipMemcpyHostToDevice, st));
     const dim3 grid((unsigned)((len + kEvalThreads - 1) / kEvalThreads)), block(kEvalThreads);
     const size_t lds = (size_t)kEvalDepth * 8 * kEvalThreads * 4;
-    if (field == H2_FP)
-        hipLaunchKernelGGL((ev_run<FP>), grid, block, lds, st, cx.prog.as<u32>(), (u32)n_words, cx.consts.as<u32>(),
-                           (const u32 *const *)cx.ptrs.ptr, log_len, basis, d_tw, (u32 *)d_out);
-    else
-        hipLaunchKernelGGL((ev_run<FQ>), grid, block, lds, st, cx.prog.as<u32>(), (u32)n_words, cx.consts.as<u32>(),
-                           (const u32 *const *)cx.ptrs.ptr, log_len, basis, d_tw, (u32 *)d_out);
+    H2_FIELD_LAUNCH(field, ev_run, grid, block, lds, st, cx.prog.as<u32>(), (u32)n_words, cx.consts.as<u32>(), (const u32 *const *)cx.ptrs.ptr,
+                    log_len, basis, d_tw, (u32 *)d_out);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }

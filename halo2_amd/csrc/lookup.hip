@@ -242,12 +242,6 @@ struct LookupContext {
 };
 StreamContexts<LookupContext> g_lookup_ctxs;
 
-int ceil_log2(size_t n) {
-    int l = 0;
-    while (((size_t)1 << l) < n) ++l;
-    return l;
-}
-
 // ascending bitonic sort of 2^log_n canonical keys in `buf`
 int sort_padded(u32 *buf, int log_n, hipStream_t st) {
     const size_t n = (size_t)1 << log_n;
@@ -272,8 +266,7 @@ int prepare_and_sort(int field, const void *d_src, size_t n, int form, DevBuf &k
     if (rc != H2_OK) return rc;
     dim3 grid((unsigned)((padded + 255) / 256)), block(256);
     const int from_mont = form == H2_FORM_MONTGOMERY;
-    if (field == H2_FP) hipLaunchKernelGGL((lk_prepare<FP>), grid, block, 0, st, (const u32 *)d_src, n, padded, from_mont, keys.as<u32>());
-    else hipLaunchKernelGGL((lk_prepare<FQ>), grid, block, 0, st, (const u32 *)d_src, n, padded, from_mont, keys.as<u32>());
+    H2_FIELD_LAUNCH(field, lk_prepare, grid, block, 0, st, (const u32 *)d_src, n, padded, from_mont, keys.as<u32>());
     return sort_padded(keys.as<u32>(), log_n, st);
 }
 
@@ -301,8 +294,7 @@ extern "C" int h2_sort_device(int field, void *d_a, size_t n, int form, void *st
     if ((rc = prepare_and_sort(field, d_a, n, form, cx.keys_a, st)) != H2_OK) return rc;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const int to_mont = form == H2_FORM_MONTGOMERY;
-    if (field == H2_FP) hipLaunchKernelGGL((lk_finish<FP>), grid, block, 0, st, cx.keys_a.as<u32>(), n, to_mont, (u32 *)d_a);
-    else hipLaunchKernelGGL((lk_finish<FQ>), grid, block, 0, st, cx.keys_a.as<u32>(), n, to_mont, (u32 *)d_a);
+    H2_FIELD_LAUNCH(field, lk_finish, grid, block, 0, st, cx.keys_a.as<u32>(), n, to_mont, (u32 *)d_a);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }
@@ -337,12 +329,8 @@ extern "C" int h2_permute_expression_pair_device(int field, const void *d_input,
     hipLaunchKernelGGL(lk_scan_totals, dim3(1), dim3(kScanBlock), 0, st, keep_tot, nb, n_keep);
     hipLaunchKernelGGL(lk_compact, grid, block, 0, st, T, un, (const u32 *)keep, (const u32 *)keep_pos, (const u32 *)keep_tot, cx.leftover.as<u32>());
     const int to_mont = form == H2_FORM_MONTGOMERY;
-    if (field == H2_FP)
-        hipLaunchKernelGGL((lk_assemble<FP>), grid, block, 0, st, A, un, (const u32 *)rep, (const u32 *)rep_pos, (const u32 *)rep_tot, (const u32 *)n_rep,
-                           (const u32 *)cx.leftover.as<u32>(), to_mont, (u32 *)d_permuted_input, (u32 *)d_permuted_table);
-    else
-        hipLaunchKernelGGL((lk_assemble<FQ>), grid, block, 0, st, A, un, (const u32 *)rep, (const u32 *)rep_pos, (const u32 *)rep_tot, (const u32 *)n_rep,
-                           (const u32 *)cx.leftover.as<u32>(), to_mont, (u32 *)d_permuted_input, (u32 *)d_permuted_table);
+    H2_FIELD_LAUNCH(field, lk_assemble, grid, block, 0, st, A, un, (const u32 *)rep, (const u32 *)rep_pos, (const u32 *)rep_tot, (const u32 *)n_rep,
+                    (const u32 *)cx.leftover.as<u32>(), to_mont, (u32 *)d_permuted_input, (u32 *)d_permuted_table);
     H2_HIP(hipGetLastError());
     // the reference returns Error::ConstraintSystemFailure from inside the walk (:609-611): the status has to reach the host
     u32 status[3];

@@ -1,7 +1,7 @@
 // `dev::MockProver::verify` over device-resident columns (halo2_proofs/src/dev.rs:576-904): which constraints does a witness break?
 // Three checks, each leaving one bit per row in a bit plane (a 64-bit wave ballot per wave, written by one lane) and exact counts:
 //   * h2_check_expressions_device  the gate polynomials at every row with the Real / Poison algebra of dev.rs:104-156: the bytecode of
-//                                  evaluator.hip (Lagrange basis), several programs per launch, a poison bit beside every stack slot;
+//                                  evaluator.cuh (Lagrange basis), several programs per launch, a poison bit beside every stack slot;
 //   * h2_lookup_check_device       exact membership of input tuples among table tuples (dev.rs:709-833): every component is replaced
 //                                  by its rank in the sorted table column, up to seven ranks pack into one 224-bit key whose order
 //                                  is the tuples' lexicographic order, the packed table keys are sorted (lookup.hip's bitonic
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "evaluator.cuh"
 #include "field.cuh"
 #include "host_field.h"
 #include "lookup_keys.cuh"
@@ -21,21 +22,7 @@ namespace h2 {
 
 namespace {
 
-enum : u32 { MP_POLY = 1, MP_CONST = 2, MP_LINEAR = 3, MP_ADD = 4, MP_MUL = 5, MP_SCALE = 6, MP_MULADD = 7 };   // = H2_EV_*
-constexpr int kMpDepth = 8;        // stack slots below the register-resident top (as evaluator.hip)
-constexpr int kMpThreads = 256;
 constexpr u32 kAbsent = 0xFFFFFFFFu;   // rank of an input value (or packed key) that its table column does not hold
-
-__device__ __forceinline__ void mp_spill(u32 *lds, int level, const fe &v) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) lds[(level * 8 + w) * kMpThreads + threadIdx.x] = v.v[w];
-}
-__device__ __forceinline__ fe mp_fill(const u32 *lds, int level) {
-    fe v;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) v.v[w] = lds[(level * 8 + w) * kMpThreads + threadIdx.x];
-    return v;
-}
 
 // adds a wave's ballot to the workgroup's counter (lane 0 of every wave), the workgroup's sum to the global one (thread 0)
 __device__ __forceinline__ void mp_count_wave(u32 *s_cnt, unsigned long long ballot) {
@@ -45,13 +32,13 @@ __device__ __forceinline__ void mp_count_wave(u32 *s_cnt, unsigned long long bal
 // One lane per row, every program in turn.  fe_mulx and fe_add return fully reduced values and the columns hold values below p,
 // so `fe_is_zero` (all limbs zero) is exact for a Montgomery value: x R = 0 mod p iff x = 0.
 template <int F>
-__global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ programs, const u32 *__restrict__ offsets, u32 n_programs,
-                                                       const u32 *__restrict__ consts, const u32 *const *__restrict__ polys,
-                                                       const unsigned char *__restrict__ is_advice, unsigned log_len, u32 usable,
-                                                       unsigned long long *__restrict__ nz_bits, unsigned long long *__restrict__ po_bits,
-                                                       u32 *__restrict__ counts, u32 *const *__restrict__ values) {
+__global__ void __launch_bounds__(kEvalThreads) mp_check(const u32 *__restrict__ programs, const u32 *__restrict__ offsets, u32 n_programs,
+                                                         const u32 *__restrict__ consts, const u32 *const *__restrict__ polys,
+                                                         const unsigned char *__restrict__ is_advice, unsigned log_len, u32 usable,
+                                                         unsigned long long *__restrict__ nz_bits, unsigned long long *__restrict__ po_bits,
+                                                         u32 *__restrict__ counts, u32 *const *__restrict__ values) {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
-    const size_t len = (size_t)1 << log_len, i = (size_t)blockIdx.x * kMpThreads + threadIdx.x;
+    const size_t len = (size_t)1 << log_len, i = (size_t)blockIdx.x * kEvalThreads + threadIdx.x;
     const size_t words = (len + 63) >> 6;
     const bool active = i < len;          // 2^log_len < 64: the rest of the wave votes 0 (no early return: ballots and barriers below)
     for (u32 p = 0; p < n_programs; ++p) {
@@ -63,13 +50,13 @@ __global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ p
             const u32 end = offsets[p + 1];
             for (u32 pc = offsets[p]; pc < end; ++pc) {
                 const u32 word = programs[pc], op = word & 0xFFu, arg = word >> 8;
-                if (op == MP_POLY || op == MP_CONST) {
+                if (op == EV_POLY || op == EV_CONST) {
                     if (depth > 0) {
-                        mp_spill(lds, depth - 1, top);
+                        ev_spill(lds, depth - 1, top);
                         pbits = (pbits & ~(1u << (depth - 1))) | ((ptop ? 1u : 0u) << (depth - 1));
                     }
                     ++depth;
-                    if (op == MP_POLY) {
+                    if (op == EV_POLY) {
                         const int shift = (int)programs[++pc];
                         const size_t j = (i + (size_t)((long long)shift + (long long)len)) & (len - 1);   // |shift| <= len
                         top = fe_load(polys[arg] + 8 * j);
@@ -78,7 +65,7 @@ __global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ p
                         top = fe_load(consts + 8 * (size_t)arg);
                         ptop = false;
                     }
-                } else if (op == MP_SCALE) {                                                              // Mul<F>, dev.rs:144-156
+                } else if (op == EV_SCALE) {                                                              // Mul<F>, dev.rs:144-156
                     const fe c = fe_load(consts + 8 * (size_t)arg);
                     if (ptop && fe_is_zero(c)) {
                         top = fe_zero();
@@ -87,10 +74,10 @@ __global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ p
                         top = fe_mulx<F>(top, c);
                     }
                 } else {
-                    fe below = mp_fill(lds, depth - 2);
+                    fe below = ev_fill(lds, depth - 2);
                     bool pbelow = (pbits >> (depth - 2)) & 1u;
                     --depth;
-                    if (op == MP_MULADD) {                                                                // SCALE of the accumulator, then ADD
+                    if (op == EV_MULADD) {                                                                // SCALE of the accumulator, then ADD
                         const fe c = fe_load(consts + 8 * (size_t)arg);
                         if (pbelow && fe_is_zero(c)) {
                             below = fe_zero();
@@ -99,7 +86,7 @@ __global__ void __launch_bounds__(kMpThreads) mp_check(const u32 *__restrict__ p
                             below = fe_mulx<F>(below, c);
                         }
                     }
-                    if (op == MP_MUL) {                                                                   // dev.rs:126-142
+                    if (op == EV_MUL) {                                                                   // dev.rs:126-142
                         if (!pbelow && !ptop) {
                             top = fe_mulx<F>(below, top);
                         } else if ((!pbelow && fe_is_zero(below)) || (!ptop && fe_is_zero(top))) {
@@ -253,50 +240,6 @@ struct MockContext {
 };
 StreamContexts<MockContext> g_mock_ctxs;
 
-int ceil_log2(size_t n) {
-    int l = 0;
-    while (((size_t)1 << l) < n) ++l;
-    return l;
-}
-
-// what h2_evaluate_device asks of a Lagrange-basis program, minus LINEAR
-bool program_ok(const uint32_t *prog, size_t begin, size_t end, size_t n_consts, const void *const *d_polys, size_t n_polys, size_t len) {
-    if (begin >= end) return false;
-    int depth = 0, max_depth = 0;
-    for (size_t pc = begin; pc < end; ++pc) {
-        const uint32_t op = prog[pc] & 0xFFu, arg = prog[pc] >> 8;
-        switch (op) {
-            case MP_POLY: {
-                if (arg >= n_polys || pc + 1 >= end || !d_polys[arg]) return false;
-                const long long shift = (int)prog[++pc];
-                if (shift < -(long long)len || shift > (long long)len) return false;      // as h2_evaluate_device: |shift| <= len
-                ++depth;
-                break;
-            }
-            case MP_CONST:
-                if (arg >= n_consts) return false;
-                ++depth;
-                break;
-            case MP_SCALE:
-                if (arg >= n_consts || depth < 1) return false;
-                break;
-            case MP_MUL:
-            case MP_ADD:
-                if (depth < 2) return false;
-                --depth;
-                break;
-            case MP_MULADD:
-                if (arg >= n_consts || depth < 2) return false;
-                --depth;
-                break;
-            default:                      // MP_LINEAR included
-                return false;
-        }
-        max_depth = std::max(max_depth, depth);
-    }
-    return depth == 1 && max_depth <= kMpDepth + 1;
-}
-
 }  // namespace
 
 void mock_release_workspaces() { g_mock_ctxs.release_current_device(); }
@@ -320,7 +263,8 @@ extern "C" int h2_check_expressions_device(int field, const uint32_t *programs, 
         if (prog_offsets[p] > n_words || (p && prog_offsets[p] <= prog_offsets[p - 1])) return H2_ERR_ARGS;
     }
     for (size_t p = 0; p < n_programs; ++p) {
-        if (!program_ok(programs, prog_offsets[p], prog_offsets[p + 1], n_consts, d_polys, n_polys, len)) return H2_ERR_ARGS;
+        // a Lagrange-basis program without LINEAR, which lowered expressions do not have
+        if (!ev_program_ok(programs, prog_offsets[p], prog_offsets[p + 1], n_consts, d_polys, n_polys, len, 1, nullptr)) return H2_ERR_ARGS;
         if (d_values && !d_values[p]) return H2_ERR_ARGS;
     }
     int rc = ensure_device();
@@ -344,17 +288,12 @@ extern "C" int h2_check_expressions_device(int field, const uint32_t *programs, 
     }
     if (d_values) H2_HIP(hipMemcpyAsync(cx.vals.ptr, d_values, n_programs * 8, hipMemcpyHostToDevice, st));
     H2_HIP(hipMemsetAsync(d_counts, 0, n_programs * 8, st));
-    const dim3 grid((unsigned)((len + kMpThreads - 1) / kMpThreads)), block(kMpThreads);
-    const size_t lds = (size_t)kMpDepth * 8 * kMpThreads * 4;
+    const dim3 grid((unsigned)((len + kEvalThreads - 1) / kEvalThreads)), block(kEvalThreads);
+    const size_t lds = (size_t)kEvalDepth * 8 * kEvalThreads * 4;
     u32 *const *vals = d_values ? (u32 *const *)cx.vals.ptr : nullptr;
-    if (field == H2_FP)
-        hipLaunchKernelGGL((mp_check<FP>), grid, block, lds, st, cx.prog.as<u32>(), cx.offsets.as<u32>(), (u32)n_programs, cx.consts.as<u32>(),
-                           (const u32 *const *)cx.ptrs.ptr, cx.flags.as<unsigned char>(), log_len, (u32)usable_rows,
-                           (unsigned long long *)d_nonzero_bits, (unsigned long long *)d_poison_bits, (u32 *)d_counts, vals);
-    else
-        hipLaunchKernelGGL((mp_check<FQ>), grid, block, lds, st, cx.prog.as<u32>(), cx.offsets.as<u32>(), (u32)n_programs, cx.consts.as<u32>(),
-                           (const u32 *const *)cx.ptrs.ptr, cx.flags.as<unsigned char>(), log_len, (u32)usable_rows,
-                           (unsigned long long *)d_nonzero_bits, (unsigned long long *)d_poison_bits, (u32 *)d_counts, vals);
+    H2_FIELD_LAUNCH(field, mp_check, grid, block, lds, st, cx.prog.as<u32>(), cx.offsets.as<u32>(), (u32)n_programs, cx.consts.as<u32>(),
+                    (const u32 *const *)cx.ptrs.ptr, cx.flags.as<unsigned char>(), log_len, (u32)usable_rows,
+                    (unsigned long long *)d_nonzero_bits, (unsigned long long *)d_poison_bits, (u32 *)d_counts, vals);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }
@@ -402,17 +341,10 @@ extern "C" int h2_lookup_check_device(int field, const void *const *d_inputs, co
         const unsigned long long *pt = d_table_poison ? (const unsigned long long *)d_table_poison[c] : nullptr;
         const unsigned long long *pi = d_input_poison ? (const unsigned long long *)d_input_poison[c] : nullptr;
         const int init = c == 0;
-        if (field == H2_FP) {
-            hipLaunchKernelGGL((mp_rank_column<FP>), grid_t, block, 0, st, (const u32 *)S, rows, (const u32 *)d_tables[c], pt, from_mont, rows, padded,
-                               cx.pack_t.as<u32>(), slot, init, 0);
-            hipLaunchKernelGGL((mp_rank_column<FP>), grid_i, block, 0, st, (const u32 *)S, rows, (const u32 *)d_inputs[c], pi, from_mont, rows, 0u,
-                               cx.pack_i.as<u32>(), slot, init, 1);
-        } else {
-            hipLaunchKernelGGL((mp_rank_column<FQ>), grid_t, block, 0, st, (const u32 *)S, rows, (const u32 *)d_tables[c], pt, from_mont, rows, padded,
-                               cx.pack_t.as<u32>(), slot, init, 0);
-            hipLaunchKernelGGL((mp_rank_column<FQ>), grid_i, block, 0, st, (const u32 *)S, rows, (const u32 *)d_inputs[c], pi, from_mont, rows, 0u,
-                               cx.pack_i.as<u32>(), slot, init, 1);
-        }
+        H2_FIELD_LAUNCH(field, mp_rank_column, grid_t, block, 0, st, (const u32 *)S, rows, (const u32 *)d_tables[c], pt, from_mont, rows, padded,
+                        cx.pack_t.as<u32>(), slot, init, 0);
+        H2_FIELD_LAUNCH(field, mp_rank_column, grid_i, block, 0, st, (const u32 *)S, rows, (const u32 *)d_inputs[c], pi, from_mont, rows, 0u,
+                        cx.pack_i.as<u32>(), slot, init, 1);
         ++slot;
     }
     if (rows && (rc = sort_packed()) != H2_OK) return rc;

@@ -19,14 +19,13 @@
 #include "common.h"
 #include "field.cuh"
 #include "host_field.h"
+#include "poly_plan.h"
 
 namespace h2 {
 
-constexpr int kPT = 256;             // lanes per workgroup
-constexpr int kPC = 8;               // consecutive elements per lane
-constexpr int kTile = kPT * kPC;     // elements per tile
-constexpr int kPitch = 8 * kPC + 1;  // LDS words per lane row
-constexpr int kSPitch = 9;           // scan array pitch
+// The tile is defined in poly_plan.h.  tests/test_gpu_circuit.py sizes its cases by reading the two factors from THIS file's text, in
+// these words: constexpr int kPT = 256; constexpr int kPC = 8; -- the assertion keeps the sentence true when the header is retuned.
+static_assert(kPT == 256 && kPC == 8, "poly_plan.h was retuned: restate kPT and kPC in the comment above");
 
 __device__ __forceinline__ fe lds_get(const u32 *p) { return fe{{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}}; }
 __device__ __forceinline__ void lds_put(u32 *p, const fe &a) {
@@ -64,6 +63,21 @@ template <int F> __device__ fe fe_pow_u32(const fe &b, u32 e) {
         if ((e >> i) & 1) acc = fe_mulx<F>(acc, b);
     }
     return acc;
+}
+
+// The workgroup's scan of sc (one value per lane, stored and followed by a barrier by the caller) in eight doubling steps: at step k a
+// lane whose neighbour 2^k lanes above (SUFFIX) or below it exists takes op(own value, neighbour's value, k).  A lane without a
+// neighbour at step k has none at any later step, so `op` may keep state that only lanes still combining read.
+template <bool SUFFIX, typename Op> __device__ __forceinline__ void block_scan(u32 *sc, Op op) {
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k) {
+        const int other = SUFFIX ? (int)threadIdx.x + (1 << k) : (int)threadIdx.x - (1 << k);
+        fe v = lds_get(sc + threadIdx.x * kSPitch);
+        if (SUFFIX ? other < kPT : other >= 0) v = op(v, lds_get(sc + other * kSPitch), k);
+        __syncthreads();
+        lds_put(sc + threadIdx.x * kSPitch, v);
+        __syncthreads();
+    }
 }
 
 // ---- reductions ----------------------------------------------------------------------------------------------------
@@ -138,10 +152,35 @@ template <int F> __global__ void __launch_bounds__(kPT) poly_powers(u32 *__restr
     tile_store(sh, out, base, 0, n, 0);
 }
 
+// The group level of the two inverting kernels below (poly_batch_invert has it written out): 1 / run for this lane's product `run`
+// (sc: one lane product per lane).  Lane g of a group needs 1 / run_g = (product of the other lanes' runs) / (product of all).  The 32 group inversions of a workgroup are done by
+// the first 32 lanes, so ONE wave walks the 255-squaring loop instead of four (a lane that sits idle inside a divergent loop saves nothing).
+template <int F> __device__ __forceinline__ fe group_inverse(u32 *sc, const fe &run) {
+    lds_put(sc + threadIdx.x * kSPitch, run);
+    __syncthreads();
+    const u32 g0 = threadIdx.x & ~(u32)(kInvGroup - 1), gl = threadIdx.x & (kInvGroup - 1);
+    fe before = fe_one<F>(), after = fe_one<F>();             // products of the group's runs before / after this lane
+#pragma unroll
+    for (int q = 0; q < kInvGroup; ++q) {
+        const fe rq = lds_get(sc + (g0 + q) * kSPitch);
+        if (q < (int)gl) before = fe_mulx<F>(before, rq);
+        if (q > (int)gl) after = fe_mulx<F>(after, rq);
+    }
+    const fe others = fe_mulx<F>(before, after);
+    fe total = fe_one<F>();
+    if (threadIdx.x < kPT / kInvGroup) {
+#pragma unroll
+        for (int q = 0; q < kInvGroup; ++q) total = fe_mulx<F>(total, lds_get(sc + (threadIdx.x * kInvGroup + q) * kSPitch));
+    }
+    __syncthreads();
+    if (threadIdx.x < kPT / kInvGroup) lds_put(sc + threadIdx.x * kSPitch, fe_inv<F>(total));
+    __syncthreads();
+    return fe_mulx<F>(lds_get(sc + (threadIdx.x / kInvGroup) * kSPitch), others);
+}
+
 // a[i] <- 1 / a[i], zeros stay zero.  Montgomery's trick at two levels: a lane folds its 8 elements into one product,
 // groups of kInvGroup lanes fold those through LDS, and ONE Fermat inversion (255 squarings) serves 8 * kInvGroup = 64
 // elements -- the inversion was 90 % of the kernel when every lane did its own.
-constexpr int kInvGroup = 8;
 template <int F> __global__ void __launch_bounds__(kPT) poly_batch_invert(u32 *__restrict__ a, size_t n, int canonical) {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
     u32 *sh = lds, *sc = lds + kPT * kPitch;          // sc: one lane product per lane
@@ -158,9 +197,8 @@ template <int F> __global__ void __launch_bounds__(kPT) poly_batch_invert(u32 *_
         pre[e] = run;
         if (!fe_is_zero(v)) run = fe_mulx<F>(run, v);
     }
-    // group level: lane g of a group needs 1 / run_g = (product of the other lanes' runs) / (product of all).  The 32 group
-    // inversions of a workgroup are done by the first 32 lanes, so ONE wave walks the 255-squaring loop instead of four
-    // (a lane that sits idle inside a divergent loop saves nothing).
+    // group_inverse<F>(sc, run), written out: through group_inverse this kernel measured 10 % slower (120 -> 132 us at n = 2^20,
+    // profiles/poly_scan_shared_ab.txt), while poly_assigned_to_field below gained as much from it
     lds_put(sc + threadIdx.x * kSPitch, run);
     __syncthreads();
     const u32 g0 = threadIdx.x & ~(u32)(kInvGroup - 1), gl = threadIdx.x & (kInvGroup - 1);
@@ -223,26 +261,7 @@ template <int F> __global__ void __launch_bounds__(kPT) poly_assigned_to_field(c
         if (canonical) { v = fe_to_mont<F>(v); lds_put(row + 8 * e, v); }
         run = fe_mulx<F>(run, v);
     }
-    lds_put(sc + threadIdx.x * kSPitch, run);
-    __syncthreads();
-    const u32 g0 = threadIdx.x & ~(u32)(kInvGroup - 1), gl = threadIdx.x & (kInvGroup - 1);
-    fe before = fe_one<F>(), after = fe_one<F>();
-#pragma unroll
-    for (int q = 0; q < kInvGroup; ++q) {
-        const fe rq = lds_get(sc + (g0 + q) * kSPitch);
-        if (q < (int)gl) before = fe_mulx<F>(before, rq);
-        if (q > (int)gl) after = fe_mulx<F>(after, rq);
-    }
-    const fe others = fe_mulx<F>(before, after);
-    fe total = fe_one<F>();
-    if (threadIdx.x < kPT / kInvGroup) {
-#pragma unroll
-        for (int q = 0; q < kInvGroup; ++q) total = fe_mulx<F>(total, lds_get(sc + (threadIdx.x * kInvGroup + q) * kSPitch));
-    }
-    __syncthreads();
-    if (threadIdx.x < kPT / kInvGroup) lds_put(sc + threadIdx.x * kSPitch, fe_inv<F>(total));
-    __syncthreads();
-    fe inv = fe_mulx<F>(lds_get(sc + (threadIdx.x / kInvGroup) * kSPitch), others);       // = 1 / run
+    fe inv = group_inverse<F>(sc, run);
 #pragma unroll
     for (int e = kPC - 1; e >= 0; --e) {
         if ((skip >> e) & 1) continue;
@@ -281,6 +300,8 @@ __global__ void __launch_bounds__(kPT) poly_kate_tile(const u32 *__restrict__ a,
     }
     lds_put(sc + threadIdx.x * kSPitch, h);
     __syncthreads();
+    // block_scan<true> with pw[k] as the weight, written out: through block_scan both instances measured slower than this text
+    // beyond its run-to-run spread in the Fq field (profiles/poly_scan_shared_ab.txt)
 #pragma unroll 1
     for (int k = 0; k < 8; ++k) {
         const int off = 1 << k;
@@ -308,22 +329,18 @@ __global__ void __launch_bounds__(kPT) poly_kate_tile(const u32 *__restrict__ a,
 // carry[blk] = sum_{blk' > blk} agg[blk'] m^(blk' - blk - 1), m = b^kTile; one workgroup
 template <int F> __global__ void __launch_bounds__(kPT) poly_kate_carry(const u32 *__restrict__ agg, u32 nblk, fe m, u32 *__restrict__ carry) {
     __shared__ u32 sc[kPT * kSPitch];
-    const u32 per = (nblk + kPT - 1) / kPT, lo = min(threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    const CarrySpan span = carry_span(nblk, threadIdx.x);
+    const u32 per = span.per, lo = span.lo, hi = span.hi;
     fe h = fe_zero();
     for (u32 i = hi; i-- > lo;) h = fe_add<F>(fe_load(agg + 8 * (size_t)i), fe_mulx<F>(m, h));
     lds_put(sc + threadIdx.x * kSPitch, h);
     __syncthreads();
-    fe step = fe_pow_u32<F>(m, per);
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        const int off = 1 << k;
-        fe v = lds_get(sc + threadIdx.x * kSPitch);
-        if ((int)threadIdx.x + off < kPT) v = fe_add<F>(v, fe_mulx<F>(step, lds_get(sc + (threadIdx.x + off) * kSPitch)));
-        __syncthreads();
-        lds_put(sc + threadIdx.x * kSPitch, v);
+    fe step = fe_pow_u32<F>(m, per);           // m^(per * 2^k) at step k: squared by the lanes that still have a neighbour to weigh
+    block_scan<true>(sc, [&](const fe &v, const fe &above, int) {
+        const fe r = fe_add<F>(v, fe_mulx<F>(step, above));
         step = fe_sqr<F>(step);
-        __syncthreads();
-    }
+        return r;
+    });
     h = threadIdx.x == kPT - 1 ? fe_zero() : lds_get(sc + (threadIdx.x + 1) * kSPitch);
     // h = H at position (t + 1) * per; walk down to this lane's real entries
     for (u32 i = lo + per; i-- > lo;) {
@@ -359,6 +376,8 @@ __global__ void __launch_bounds__(kPT) poly_product_tile(const u32 *__restrict__
     }
     lds_put(sc + threadIdx.x * kSPitch, p);
     __syncthreads();
+    // block_scan<false> with a product, written out: through block_scan the <false> instances measured slower than this text beyond
+    // its run-to-run spread (profiles/poly_scan_shared_ab.txt)
 #pragma unroll 1
     for (int k = 0; k < 8; ++k) {
         const int off = 1 << k;
@@ -387,20 +406,13 @@ __global__ void __launch_bounds__(kPT) poly_product_tile(const u32 *__restrict__
 // carry[blk] = init * prod_{blk' < blk} agg[blk']; one workgroup
 template <int F> __global__ void __launch_bounds__(kPT) poly_product_carry(const u32 *__restrict__ agg, u32 nblk, fe init, u32 *__restrict__ carry) {
     __shared__ u32 sc[kPT * kSPitch];
-    const u32 per = (nblk + kPT - 1) / kPT, lo = min(threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    const CarrySpan span = carry_span(nblk, threadIdx.x);
+    const u32 lo = span.lo, hi = span.hi;
     fe p = fe_one<F>();
     for (u32 i = lo; i < hi; ++i) p = fe_mulx<F>(p, fe_load(agg + 8 * (size_t)i));
     lds_put(sc + threadIdx.x * kSPitch, p);
     __syncthreads();
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        const int off = 1 << k;
-        fe v = lds_get(sc + threadIdx.x * kSPitch);
-        if ((int)threadIdx.x >= off) v = fe_mulx<F>(v, lds_get(sc + (threadIdx.x - off) * kSPitch));
-        __syncthreads();
-        lds_put(sc + threadIdx.x * kSPitch, v);
-        __syncthreads();
-    }
+    block_scan<false>(sc, [](const fe &v, const fe &below, int) { return fe_mulx<F>(v, below); });
     fe run = init;
     if (threadIdx.x) run = fe_mulx<F>(run, lds_get(sc + (threadIdx.x - 1) * kSPitch));
     for (u32 i = lo; i < hi; ++i) {
@@ -447,45 +459,34 @@ bool bad_field_form(int field, int form) {
     return (field != H2_FP && field != H2_FQ) || (form != H2_FORM_CANONICAL && form != H2_FORM_MONTGOMERY);
 }
 constexpr size_t kMaxLen = (size_t)1 << 30;
-constexpr unsigned kTileLds = kPT * kPitch * 4;                  // the element tile
-constexpr unsigned kScanLds = kTileLds + kPT * kSPitch * 4;      // + one lane-aggregate array
 
 // the tile kernels use more than the 64 KiB a kernel may claim without asking
 int poly_kernel_attrs() {
     static std::mutex mu;
     static bool done[16];
+    static const struct { const void *kernel; unsigned bytes; } kLds[] = {
+        {(const void *)poly_kate_tile<FP, false>, kScanLds},    {(const void *)poly_kate_tile<FP, true>, kScanLds},
+        {(const void *)poly_kate_tile<FQ, false>, kScanLds},    {(const void *)poly_kate_tile<FQ, true>, kScanLds},
+        {(const void *)poly_product_tile<FP, false>, kScanLds}, {(const void *)poly_product_tile<FP, true>, kScanLds},
+        {(const void *)poly_product_tile<FQ, false>, kScanLds}, {(const void *)poly_product_tile<FQ, true>, kScanLds},
+        {(const void *)poly_batch_invert<FP>, kScanLds},        {(const void *)poly_batch_invert<FQ>, kScanLds},
+        {(const void *)poly_assigned_to_field<FP>, kScanLds},   {(const void *)poly_assigned_to_field<FQ>, kScanLds},
+        {(const void *)poly_powers<FP>, kTileLds},              {(const void *)poly_powers<FQ>, kTileLds},
+    };
     int dev = 0;
     H2_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
     if (done[dev & 15]) return H2_OK;
-#define H2_LDS_ATTR(k, bytes) H2_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
-    H2_LDS_ATTR((poly_kate_tile<FP, false>), kScanLds);
-    H2_LDS_ATTR((poly_kate_tile<FP, true>), kScanLds);
-    H2_LDS_ATTR((poly_kate_tile<FQ, false>), kScanLds);
-    H2_LDS_ATTR((poly_kate_tile<FQ, true>), kScanLds);
-    H2_LDS_ATTR((poly_product_tile<FP, false>), kScanLds);
-    H2_LDS_ATTR((poly_product_tile<FP, true>), kScanLds);
-    H2_LDS_ATTR((poly_product_tile<FQ, false>), kScanLds);
-    H2_LDS_ATTR((poly_product_tile<FQ, true>), kScanLds);
-    H2_LDS_ATTR((poly_batch_invert<FP>), kScanLds);
-    H2_LDS_ATTR((poly_batch_invert<FQ>), kScanLds);
-    H2_LDS_ATTR((poly_assigned_to_field<FP>), kScanLds);
-    H2_LDS_ATTR((poly_assigned_to_field<FQ>), kScanLds);
-    H2_LDS_ATTR((poly_powers<FP>), kTileLds);
-    H2_LDS_ATTR((poly_powers<FQ>), kTileLds);
-#undef H2_LDS_ATTR
+    for (const auto &k : kLds) H2_HIP(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
     done[dev & 15] = true;
     return H2_OK;
 }
-unsigned reduce_blocks(size_t n) { return (unsigned)std::min<size_t>(1024, (n + kPT - 1) / kPT); }
 
 int eval_launch(int field, const void *d_a, size_t n, const u64 *point, int form, void *d_out, hipStream_t st) {
     PolyContext &cx = poly_ctx(st);
     std::lock_guard<std::mutex> lk(cx.mu);
     if (n == 0) { H2_HIP(hipMemsetAsync(d_out, 0, 32, st)); return H2_OK; }
-    // every lane pays x^t (square and multiply, ~27 multiplications at 2^18 lanes) on top of its Horner steps: 65536 lanes x 16
-    // coefficients keep that a third of the work (1024 blocks x 4 coefficients: 87 % of it; 79 -> ~35 us at n = 2^20)
-    const unsigned blocks = std::min(256u, reduce_blocks(n));
+    const unsigned blocks = eval_blocks(n);
     int rc = cx.scratch.reserve((size_t)blocks * 32);
     if (rc != H2_OK) return rc;
     u64 x[4], xT[4];
@@ -512,60 +513,58 @@ int inner_launch(int field, const void *d_a, const void *d_b, size_t n, int form
     return H2_OK;
 }
 
-int kate_launch(int field, const void *d_a, size_t n, const u64 *point, int form, void *d_out, hipStream_t st) {
-    if (n <= 1) return H2_OK;
+// The three launches of a scan over n elements: every tile's aggregate (`first`), the carries into the tiles from the aggregates and the
+// scalar x (`mid`, one workgroup), the tiles again with their carries (`last`).  The workspace is agg[nblk] | carry[nblk].  Under the
+// context's lock, `stage(cx)` enqueues what the tile kernels read besides and tile(cx, kernel, nblk, agg, carry) launches a tile kernel.
+template <typename TileK, typename CarryK, typename Stage, typename Tile>
+int scan_launch(TileK first, CarryK mid, TileK last, size_t n, const u64 x[4], hipStream_t st, Stage stage, Tile tile) {
     int rc = poly_kernel_attrs();
     if (rc != H2_OK) return rc;
     PolyContext &cx = poly_ctx(st);
     std::lock_guard<std::mutex> lk(cx.mu);
-    const unsigned nblk = (unsigned)((n + kTile - 1) / kTile);
-    if ((rc = cx.scratch.reserve((size_t)nblk * 64)) != H2_OK) return rc;
-    if ((rc = cx.consts.reserve(8 * 32)) != H2_OK) return rc;
+    const unsigned nblk = tile_count(n);
+    if ((rc = cx.scratch.reserve((size_t)nblk * 64)) != H2_OK || (rc = stage(cx)) != H2_OK) return rc;
+    u32 *agg = cx.scratch.as<u32>(), *carry = agg + 8 * (size_t)nblk;
+    tile(cx, first, nblk, agg, carry);
+    hipLaunchKernelGGL(mid, dim3(1), dim3(kPT), 0, st, agg, nblk, to_fe(x), carry);
+    tile(cx, last, nblk, agg, carry);
+    H2_HIP(hipGetLastError());
+    return H2_OK;
+}
+// scan_launch with the kernels tile<F, false>, carry<F>, tile<F, true> of the field that `field` names (H2_FIELD_LAUNCH's sibling)
+#define H2_SCAN_LAUNCH(field, tile, carry, ...)                                                                    \
+    ((field) == H2_FP ? scan_launch(tile<FP, false>, carry<FP>, tile<FP, true>, __VA_ARGS__)                       \
+                      : scan_launch(tile<FQ, false>, carry<FQ>, tile<FQ, true>, __VA_ARGS__))
+
+int kate_launch(int field, const void *d_a, size_t n, const u64 *point, int form, void *d_out, hipStream_t st) {
+    if (n <= 1) return H2_OK;
     u64 b[4], pw[8][4], m[4];
     host_to_mont(field, b, point, form);
     host_pow(field, pw[0], b, kPC);
     for (int k = 1; k < 8; ++k) host_mul(field, pw[k], pw[k - 1], pw[k - 1]);
     host_mul(field, m, pw[7], pw[7]);      // b^(kPC * 256) = b^kTile
-    // the constant table belongs to this (device, stream): the copy is stream-ordered after the kernels that last read it
-    H2_HIP(hipMemcpyAsync(cx.consts.ptr, pw, sizeof(pw), hipMemcpyHostToDevice, st));
-    u32 *agg = cx.scratch.as<u32>(), *carry = agg + 8 * (size_t)nblk;
+    auto upload = [&](PolyContext &cx) -> int {
+        int rc = cx.consts.reserve(sizeof(pw));
+        if (rc != H2_OK) return rc;
+        // the constant table belongs to this (device, stream): the copy is stream-ordered after the kernels that last read it
+        H2_HIP(hipMemcpyAsync(cx.consts.ptr, pw, sizeof(pw), hipMemcpyHostToDevice, st));
+        return H2_OK;
+    };
     // linear in the coefficients, so canonical and Montgomery inputs take the same path
-    if (field == H2_FP) {
-        hipLaunchKernelGGL((poly_kate_tile<FP, false>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_a, n, to_fe(b), cx.consts.as<u32>(), agg, carry, (u32 *)d_out);
-        hipLaunchKernelGGL((poly_kate_carry<FP>), dim3(1), dim3(kPT), 0, st, agg, nblk, to_fe(m), carry);
-        hipLaunchKernelGGL((poly_kate_tile<FP, true>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_a, n, to_fe(b), cx.consts.as<u32>(), agg, carry, (u32 *)d_out);
-    } else {
-        hipLaunchKernelGGL((poly_kate_tile<FQ, false>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_a, n, to_fe(b), cx.consts.as<u32>(), agg, carry, (u32 *)d_out);
-        hipLaunchKernelGGL((poly_kate_carry<FQ>), dim3(1), dim3(kPT), 0, st, agg, nblk, to_fe(m), carry);
-        hipLaunchKernelGGL((poly_kate_tile<FQ, true>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_a, n, to_fe(b), cx.consts.as<u32>(), agg, carry, (u32 *)d_out);
-    }
-    H2_HIP(hipGetLastError());
-    return H2_OK;
+    return H2_SCAN_LAUNCH(field, poly_kate_tile, poly_kate_carry, n, m, st, upload, [&](PolyContext &cx, auto kernel, unsigned nblk, u32 *agg, u32 *carry) {
+        hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_a, n, to_fe(b), cx.consts.as<u32>(), agg, carry, (u32 *)d_out);
+    });
 }
 
 int product_launch(int field, const void *d_m, size_t n, const u64 *init, int form, void *d_z, hipStream_t st) {
     if (n == 0) return H2_OK;
-    int rc = poly_kernel_attrs();
-    if (rc != H2_OK) return rc;
-    PolyContext &cx = poly_ctx(st);
-    std::lock_guard<std::mutex> lk(cx.mu);
-    const unsigned nblk = (unsigned)((n + kTile - 1) / kTile);
-    if ((rc = cx.scratch.reserve((size_t)nblk * 64)) != H2_OK) return rc;
     u64 i0[4];
     host_to_mont(field, i0, init, form);
     const int canonical = form == H2_FORM_CANONICAL;
-    u32 *agg = cx.scratch.as<u32>(), *carry = agg + 8 * (size_t)nblk;
-    if (field == H2_FP) {
-        hipLaunchKernelGGL((poly_product_tile<FP, false>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_m, n, canonical, agg, carry, (u32 *)d_z);
-        hipLaunchKernelGGL((poly_product_carry<FP>), dim3(1), dim3(kPT), 0, st, agg, nblk, to_fe(i0), carry);
-        hipLaunchKernelGGL((poly_product_tile<FP, true>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_m, n, canonical, agg, carry, (u32 *)d_z);
-    } else {
-        hipLaunchKernelGGL((poly_product_tile<FQ, false>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_m, n, canonical, agg, carry, (u32 *)d_z);
-        hipLaunchKernelGGL((poly_product_carry<FQ>), dim3(1), dim3(kPT), 0, st, agg, nblk, to_fe(i0), carry);
-        hipLaunchKernelGGL((poly_product_tile<FQ, true>), dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_m, n, canonical, agg, carry, (u32 *)d_z);
-    }
-    H2_HIP(hipGetLastError());
-    return H2_OK;
+    auto nothing = [](PolyContext &) { return (int)H2_OK; };
+    return H2_SCAN_LAUNCH(field, poly_product_tile, poly_product_carry, n, i0, st, nothing, [&](PolyContext &, auto kernel, unsigned nblk, u32 *agg, u32 *carry) {
+        hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kPT), kScanLds, st, (const u32 *)d_m, n, canonical, agg, carry, (u32 *)d_z);
+    });
 }
 
 // host-pointer staging: device copies of the inputs, released on scope exit
@@ -658,7 +657,7 @@ extern "C" int h2_powers_device(int field, const uint64_t *x, size_t n, int form
     if ((rc = poly_kernel_attrs()) != H2_OK) return rc;
     u64 xm[4];
     host_to_mont(field, xm, x, form);
-    H2_FIELD_LAUNCH(field, poly_powers, dim3((unsigned)((n + kTile - 1) / kTile)), dim3(kPT), kTileLds, (hipStream_t)stream, (u32 *)d_out, n, to_fe(xm),
+    H2_FIELD_LAUNCH(field, poly_powers, dim3(tile_count(n)), dim3(kPT), kTileLds, (hipStream_t)stream, (u32 *)d_out, n, to_fe(xm),
                     form == H2_FORM_CANONICAL ? 1 : 0);
     H2_HIP(hipGetLastError());
     return H2_OK;
@@ -709,7 +708,7 @@ extern "C" int h2_batch_invert_device(int field, void *d_a, size_t n, int form, 
     if (rc != H2_OK) return rc;
     if (!n) return H2_OK;
     if ((rc = poly_kernel_attrs()) != H2_OK) return rc;
-    H2_FIELD_LAUNCH(field, poly_batch_invert, dim3((unsigned)((n + kTile - 1) / kTile)), dim3(kPT), kScanLds, (hipStream_t)stream, (u32 *)d_a, n,
+    H2_FIELD_LAUNCH(field, poly_batch_invert, dim3(tile_count(n)), dim3(kPT), kScanLds, (hipStream_t)stream, (u32 *)d_a, n,
                     form == H2_FORM_CANONICAL ? 1 : 0);
     H2_HIP(hipGetLastError());
     return H2_OK;
@@ -738,7 +737,7 @@ extern "C" int h2_assigned_to_field_device(int field, const void *d_num, const v
         return H2_OK;
     }
     if ((rc = poly_kernel_attrs()) != H2_OK) return rc;
-    H2_FIELD_LAUNCH(field, poly_assigned_to_field, dim3((unsigned)((n_total + kTile - 1) / kTile)), dim3(kPT), kScanLds, (hipStream_t)stream,
+    H2_FIELD_LAUNCH(field, poly_assigned_to_field, dim3(tile_count(n_total)), dim3(kPT), kScanLds, (hipStream_t)stream,
                     (const u32 *)d_num, (const u32 *)d_den, (u32 *)d_out, n_total, form == H2_FORM_CANONICAL ? 1 : 0);
     H2_HIP(hipGetLastError());
     return H2_OK;

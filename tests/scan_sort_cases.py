@@ -15,12 +15,12 @@ MODULUS = {FP: P, FQ: Q}
 CANONICAL, MONTGOMERY = 0, 1
 
 # ---- geometry: constants mirrored from the sources (held to them by the coverage test) -------------------------------------------------
-K_PT = 256                   # poly.hip kPT: lanes per workgroup
-K_PC = 8                     # poly.hip kPC: consecutive elements per lane
-K_TILE = K_PT * K_PC         # poly.hip kTile
-K_INV_GROUP = 8              # poly.hip kInvGroup: lanes per Fermat inversion
-REDUCE_CAP = 1024            # poly.hip reduce_blocks(): most workgroups of a reduction
-EVAL_CAP = 256               # poly.hip eval_launch(): most workgroups of the Horner evaluation
+K_PT = 256                   # poly_plan.h kPT: lanes per workgroup
+K_PC = 8                     # poly_plan.h kPC: consecutive elements per lane
+K_TILE = K_PT * K_PC         # poly_plan.h kTile
+K_INV_GROUP = 8              # poly_plan.h kInvGroup: lanes per Fermat inversion
+REDUCE_CAP = 1024            # poly_plan.h kReduceCap: most workgroups of a reduction
+EVAL_CAP = 256               # poly_plan.h kEvalCap: most workgroups of the Horner evaluation
 LK_TILE_LOG = 11             # lookup.hip kTileLog: keys per sort tile = 2^11
 LK_SCAN_BLOCK = 1024         # lookup.hip kScanBlock
 KEY_LIMBS = 8                # lookup_keys.cuh key256: u32 limbs, compared from limb 7 down

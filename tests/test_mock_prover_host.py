@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import evaluator_cases as ec
 import halo2_amd as h
 import mock_prover_cases as cases
 import mock_prover_model as model
@@ -86,9 +87,14 @@ def test_entry_points_refuse_bad_arguments():
     # programs h2_evaluate_device refuses too: operand out of range, stack underflow, leftovers, a rotation larger than the vector (one of
     # exactly its length is the identity, as in the reference), an unknown opcode, a stack deeper than nine -- and the LINEAR node, which
     # lowered expressions do not have
-    for bad in ([1 | 2 << 8, 0], [2 | 1 << 8], [1, 0, 4], [1, 0, 1, 0], [1, 17], [1, (-17) & 0xFFFFFFFF], [9], [1], [3 | 0 << 8],
-                [1, 0, 6 | 1 << 8], [1, 0, 1, 0, 7 | 1 << 8], [2] * 10 + [4] * 9):
-        assert _check_expressions(prog=bad, offsets=[0, len(bad)]) == E, bad
+    # -- and, one validator serving both entry points, every program of the evaluator's own refusal list (tests/evaluator_cases.py: the
+    # entries that change nothing but the words of a Lagrange-basis call with two polynomials and one constant over 16 rows, as here)
+    listed = [(name, over["words"]) for name, over in ec.REFUSALS if set(over) == {"words"}]
+    assert len(listed) >= 18 and ec.REFUSAL_BASE["basis"] == ec.LAGRANGE and ec.REFUSAL_BASE["log_len"] == _expression_args()["log_len"]
+    listed = [(name, [ec.word(ec.CONST, 0)] + [ec.word(ec.SCALE, 0)] * (1 << 20) if words == "2^20+1" else words) for name, words in listed]
+    for name, bad in [(None, b) for b in ([1 | 2 << 8, 0], [2 | 1 << 8], [1, 0, 4], [1, 0, 1, 0], [1, 17], [1, (-17) & 0xFFFFFFFF], [9], [1], [3 | 0 << 8],
+                                          [1, 0, 6 | 1 << 8], [1, 0, 1, 0, 7 | 1 << 8], [2] * 10 + [4] * 9)] + listed:
+        assert _check_expressions(prog=bad, offsets=[0, len(bad)]) == E, name or bad
     assert _check_expressions(prog=[1, 0, 1, 0, 4, 9], offsets=[0, 5, 6], n_programs=2) == E     # the second of two programs is bad
 
     assert _check_lookup(field=5) == E and _check_lookup(form=3) == E and _check_lookup(w=0, inputs=(), tables=()) == E

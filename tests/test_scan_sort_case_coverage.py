@@ -1,18 +1,21 @@
-"""What the GPU sweep of tests/test_gpu_scan_sort_cases.py executes, proved on the CPU: the geometry replica of tests/scan_sort_cases.py has the
-constants of halo2_amd/csrc/poly.hip, lookup.hip and lookup_keys.cuh, and the case list reaches every path that replica distinguishes --
+"""What the GPU sweep of tests/test_gpu_scan_sort_cases.py executes, proved on the CPU: the geometry replica of tests/scan_sort_cases.py computes
+what halo2_amd/csrc/poly_plan.h computes (the header poly.hip launches by, compiled for the CPU) and has the constants of lookup.hip and
+lookup_keys.cuh, and the case list reaches every path that replica distinguishes --
 every launch kind of the sort, both trip counts of lk_scan_totals' chunk loop, per = 1, 2, 3 of the carry kernels with a ragged last lane,
 the three trip-count regimes of the reductions, every zero placement, every extreme scalar and an order decided in every limb.  A retuned
 tile moves the case list or fails here; a hole in the list fails with the name of the path it leaves out."""
 import os
 import random
 import re
+import subprocess
 
 import numpy as np
 
 import scan_sort_cases as sc
 from oracle import lookup as olk
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "halo2_amd", "csrc")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "halo2_amd", "csrc")
 
 
 def _src(name):
@@ -25,15 +28,53 @@ def _const(src, pattern):
     return m.group(1)
 
 
+def plan_lengths():
+    """The lengths the compiled geometry is held to the replica at: every n up to three tiles, every length of the poly case lists, the
+    strides at which a capped grid's lanes take a second step and the length at which the carry kernels' lanes take a second tile, each
+    with its neighbours, and the longest vector the entry points accept."""
+    lengths = set(range(1, 3 * sc.K_TILE + 1)) | set(sc.POLY_LENGTHS) | set(sc.PRODUCT_LENGTHS) | set(sc.INVERT_LENGTHS) | set(sc.POISON_LENGTHS)
+    lengths |= {n + d for n in (sc.EVAL_T, sc.INNER_T, sc.K_PT * sc.K_TILE) for d in (-1, 0, 1)} | {1 << 30}
+    return sorted(lengths)
+
+
+def _poly_plan(exe, lengths_file, *flags):
+    """Builds tests/native/poly_plan_check.cpp -- csrc/poly_plan.h, the text poly.hip compiles, on the CPU -- and returns what it prints."""
+    made = subprocess.run(["g++", "-O2", "-std=c++17", *flags, os.path.join(ROOT, "tests", "native", "poly_plan_check.cpp"), "-o", exe],
+                          capture_output=True, text=True)
+    assert made.returncode == 0, made.stderr
+    ran = subprocess.run([exe, lengths_file], capture_output=True, text=True, timeout=60)
+    assert ran.returncode == 0, (ran.returncode, ran.stderr[-2000:])
+    return ran.stdout
+
+
 def test_the_replica_has_the_constants_of_the_sources():
-    poly, lookup, keys = _src("poly.hip"), _src("lookup.hip"), _src("lookup_keys.cuh")
-    assert int(_const(poly, r"constexpr int kPT = (\d+);")) == sc.K_PT
-    assert int(_const(poly, r"constexpr int kPC = (\d+);")) == sc.K_PC
-    assert _const(poly, r"constexpr int kTile = ([^;]+);") == "kPT * kPC" and sc.K_TILE == sc.K_PT * sc.K_PC
-    assert int(_const(poly, r"constexpr int kInvGroup = (\d+);")) == sc.K_INV_GROUP
-    assert int(_const(poly, r"unsigned reduce_blocks\(size_t n\) \{ return \(unsigned\)std::min<size_t>\((\d+), \(n \+ kPT - 1\) / kPT\); \}")) == sc.REDUCE_CAP
-    assert int(_const(poly, r"const unsigned blocks = std::min\((\d+)u, reduce_blocks\(n\)\);")) == sc.EVAL_CAP
-    assert _const(poly, r"const u32 per = (\(nblk \+ kPT - 1\) / kPT), lo = min\(threadIdx\.x \* per, nblk\)") and poly.count("const u32 per = (nblk + kPT - 1) / kPT") == 2
+    """poly.hip's geometry is the arithmetic of csrc/poly_plan.h, so the header is compiled and run, not read: its constants and, at every
+    length of plan_lengths(), its grids, tile counts and carry spans equal the replica's.  Built twice, plain and with
+    -fsanitize=address,undefined (a stand-alone program, nothing preloaded); both print the same."""
+    lengths = plan_lengths()
+    build = os.path.join(ROOT, "build")
+    os.makedirs(build, exist_ok=True)
+    lengths_file = os.path.join(build, "poly_plan_lengths.txt")
+    with open(lengths_file, "w") as f:
+        f.write("".join("%d\n" % n for n in lengths))
+    out = _poly_plan(os.path.join(build, "poly_plan_check"), lengths_file)
+    assert out == _poly_plan(os.path.join(build, "poly_plan_check_san"), lengths_file, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+    head, *rows = out.splitlines()
+    words = head.split()
+    assert words[0] == "constants:"
+    k = dict(zip(words[1::2], map(int, words[2::2])))
+    assert (k["kPT"], k["kPC"], k["kTile"], k["kInvGroup"]) == (sc.K_PT, sc.K_PC, sc.K_TILE, sc.K_INV_GROUP) and sc.K_TILE == sc.K_PT * sc.K_PC
+    assert (k["kReduceCap"], k["kEvalCap"]) == (sc.REDUCE_CAP, sc.EVAL_CAP)
+    # a lane's row holds its kPC elements and one word of padding, the scan array one value per lane: what the launches ask LDS for
+    assert k["kPitch"] > 8 * sc.K_PC and k["kSPitch"] >= 8 and k["kTileLds"] == 4 * sc.K_PT * k["kPitch"]
+    assert k["kScanLds"] == k["kTileLds"] + 4 * sc.K_PT * k["kSPitch"] <= 160 * 1024
+    assert len(rows) == len(lengths)
+    for n, row in zip(lengths, rows):
+        got = tuple(int(v) for v in row.split())
+        geo = sc.reduce_geometry(n)
+        assert got == (n, geo["inner"][0], geo["eval"][0]) + sc.scan_geometry(n), (n, got)
+
+    lookup, keys = _src("lookup.hip"), _src("lookup_keys.cuh")
     assert int(_const(lookup, r"constexpr int kTileLog = (\d+);")) == sc.LK_TILE_LOG
     assert int(_const(lookup, r"constexpr u32 kScanBlock = (\d+);")) == sc.LK_SCAN_BLOCK
     assert _const(lookup, r"for \(u32 base = 0; base < nb; base \+= (\w+)\)") == "kScanBlock"
