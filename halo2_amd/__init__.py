@@ -15,3 +15,5 @@ from . import range_check  # noqa: F401
 from .poly import Coeff, ExtendedLagrangeCoeff, LagrangeCoeff, Polynomial  # noqa: F401
 from .circuit import (Assigned, Circuit, Column, ConstraintSystem, Expression, Rotation, Selector, SimpleFloorPlanner, TableColumn,  # noqa: F401
                       Value, create_proof, keygen_pk, keygen_vk, lower)
+from . import floor_planner  # noqa: F401
+from .floor_planner import V1  # noqa: F401

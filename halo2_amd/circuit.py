@@ -1003,6 +1003,17 @@ def _table_length(default_and_assigned) -> int:                               # 
     return length
 
 
+def assign_table(cs: Assembly, table_columns: list, assignment) -> None:
+    """`assign_table` of every layouter (single_pass.rs:150-185, v1.rs:289-326): the cells, the length check, the columns recorded in
+    `table_columns` so that no later table takes them, and the default value filled in below the table."""
+    table = Table(cs, table_columns)
+    assignment(table)
+    first_unused = _table_length(table.default_and_assigned)
+    table_columns += list(table.default_and_assigned)
+    for column, (default, _) in table.default_and_assigned.items():
+        cs.fill_from_row(column.inner, first_unused, lambda: default[0])
+
+
 class _Namespace:
     def __init__(self, layouter):
         self._layouter = layouter
@@ -1043,12 +1054,7 @@ class SingleChipLayouter:
         return result
 
     def assign_table(self, name, assignment) -> None:                         # :150-185
-        table = Table(self.cs, self.table_columns)
-        assignment(table)
-        first_unused = _table_length(table.default_and_assigned)
-        self.table_columns += list(table.default_and_assigned)
-        for column, (default, _) in table.default_and_assigned.items():
-            self.cs.fill_from_row(column.inner, first_unused, lambda: default[0])
+        assign_table(self.cs, self.table_columns, assignment)
 
     def constrain_instance(self, cell: Cell, instance: Column, row: int) -> None:      # :187-199
         self.cs.copy(cell.column, self.regions[cell.region_index] + cell.row_offset, instance, row)

@@ -241,7 +241,7 @@ class MockProver:
 
     @classmethod
     def run_circuit(cls, k: int, circuit, instances, field: int, device=None) -> "MockProver":
-        """dev.rs:463-574 from a `halo2_amd.circuit.Circuit`: configure, synthesize with the witness (SimpleFloorPlanner), invert the
+        """dev.rs:463-574 from a `halo2_amd.circuit.Circuit`: configure, synthesize with the witness (the circuit's floor planner), invert the
         assigned cells' denominators, compress the selectors, lower, `run`.  instances: the instance columns, integer lists."""
         from . import circuit as front
         instances = [list(col) for col in instances]

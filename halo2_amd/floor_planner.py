@@ -1,0 +1,182 @@
+"""circuit::floor_planner: `SimpleFloorPlanner` (single pass, halo2_amd/circuit.py) and `V1` (circuit/floor_planner/v1.rs,
+v1/strategy.rs, circuit/layouter.rs:121-250).
+
+`V1` runs a circuit twice.  The measurement pass runs `circuit.without_witnesses()` against shape-mode regions and records
+(columns, row_count) per region; no value closure runs and no backend is touched.  The plan sorts the regions by advice area
+(advice columns x rows), largest first, and gives each the lowest row at which all of its columns are free for row_count rows, gaps
+left by earlier regions included.  The assignment pass runs the real circuit with region i at regions[i]; the constants the regions
+asked for go, afterwards, into the rows of the constants columns that the regions left free above `first_unassigned_row`.
+
+The planning functions are plain functions over shapes, `(columns, row_count)` pairs with columns `Column`s and `Selector`s.  The
+reference keeps each column's allocations in an ordered set, clones it and walks all of it for every column of every placement.
+Here a column is the bitmap of its allocated rows in one Python integer: the rows taken in any column of a region are the OR of
+its columns' bitmaps, the starts at which row_count rows are free come from log2(row_count) shift-and-AND steps over the complement
+(infinitely many ones above the last allocation: the unbounded interval), and the lowest set bit is the first fit.  That is
+O(columns + log row_count) word-parallel operations on `rows` bits per region, whatever the number of regions placed before it."""
+from __future__ import annotations
+
+from itertools import islice
+
+from .circuit import (ADVICE, FIXED, INSTANCE, Assembly, Cell, Column, NotEnoughColumnsForConstants, Region, Selector,  # noqa: F401
+                      SimpleFloorPlanner, Synthesis, _Namespace, assign_table)
+
+_KIND_ORDER = {INSTANCE: 0, ADVICE: 1, FIXED: 2}
+
+
+def column_order(column) -> tuple:
+    """The sort key of a region's column, `RegionColumn`'s Ord: columns before selectors (layouter.rs:146-155); columns by type --
+    Instance, Advice, Fixed -- then index (plonk/circuit.rs:47-56, 87-103); selectors by index."""
+    if isinstance(column, Selector):
+        return (1, 0, column.index)
+    return (0, _KIND_ORDER[column.kind], column.index)
+
+
+def advice_area(shape) -> int:
+    """The sort key of a region (strategy.rs:202-214)."""
+    columns, row_count = shape
+    return sum(1 for c in set(columns) if isinstance(c, Column) and c.kind == ADVICE) * row_count
+
+
+def slot_in(shapes):
+    """strategy.rs:165-195: every shape, in the order given, at the lowest row at which all of its columns are free for row_count
+    rows.  -> (starts, allocations): the start per shape, and per column the sorted (start, length) of its allocations, in the
+    order the columns were first visited.  A shape without columns starts at 0 and allocates nothing."""
+    occupied, allocations, starts = {}, {}, []
+    for columns, row_count in shapes:
+        columns = sorted(set(columns), key=column_order)
+        if not columns:
+            starts.append(0)
+            continue
+        if row_count < 1:
+            raise ValueError("a region with columns has at least one row")
+        taken = 0
+        for c in columns:
+            taken |= occupied.get(c, 0)
+        fits = ~taken                                                         # bit r: rows r .. r + run - 1 are free in every column
+        run = 1
+        while run < row_count:
+            step = min(run, row_count - run)
+            fits &= fits >> step
+            run += step
+        start = (fits & -fits).bit_length() - 1
+        block = ((1 << row_count) - 1) << start
+        for c in columns:
+            occupied[c] = occupied.get(c, 0) | block
+            allocations.setdefault(c, []).append((start, row_count))
+        starts.append(start)
+    for allocated in allocations.values():
+        allocated.sort()
+    return starts, allocations
+
+
+def slot_in_biggest_advice_first(shapes):
+    """strategy.rs:198-242: a stable ascending sort by advice area, reversed -- so of equal areas the higher region index is placed
+    first -- then `slot_in`; the starts come back in the order of `shapes`."""
+    shapes = list(shapes)
+    order = sorted(range(len(shapes)), key=lambda i: advice_area(shapes[i]))[::-1]
+    placed, allocations = slot_in([shapes[i] for i in order])
+    starts = [0] * len(shapes)
+    for i, start in zip(order, placed):
+        starts[i] = start
+    return starts, allocations
+
+
+def first_unassigned_row(allocations) -> int:
+    """v1.rs:83-87: the largest end of any column's last allocation."""
+    return max((a[-1][0] + a[-1][1] for a in allocations.values() if a), default=0)
+
+
+def constant_positions(allocations, constants, end: int):
+    """v1.rs:90-108: the (column, row) free for constants -- the rows of [0, end) no region took, ascending, the columns in the order of
+    `constants`; a column no region used is free throughout."""
+    for column in constants:
+        row = 0
+        for start, length in allocations.get(column, ()):
+            if start >= end:
+                continue
+            for free in range(row, start):
+                yield column, free
+            row = max(row, start + length)
+        for free in range(row, end):
+            yield column, free
+
+
+class _NoBackend:
+    """What `layouter.cs` is during the measurement pass: an assignment that keeps nothing, so the bulk gadgets lay out their shape
+    and launch nothing, as they do for keygen."""
+    collect_fixed = collect_advice = False
+
+    def __init__(self, cs: Assembly):
+        self.k, self.n, self.usable, self.cs, self.field, self.m = cs.k, cs.n, cs.usable, cs.cs, cs.field, cs.m
+
+
+class MeasurementPass:
+    """v1.rs:223-250 behind the `Layouter` interface: regions are measured, tables and instance constraints ignored (:178-200)."""
+
+    def __init__(self, cs: Assembly):
+        self.cs = _NoBackend(cs)
+        self.regions, self.shapes = [], []                                    # no region has a start yet: 0 each
+
+    def assign_region(self, name, assignment):
+        shape = Region(len(self.shapes))
+        result = assignment(shape)
+        self.regions.append(0)
+        self.shapes.append((list(shape.columns), shape.row_count))
+        return result
+
+    def assign_table(self, name, assignment) -> None:
+        pass
+
+    def constrain_instance(self, cell: Cell, instance: Column, row: int) -> None:
+        pass
+
+    def namespace(self, name=None):
+        return _Namespace(self)
+
+
+class AssignmentPass:
+    """v1.rs:252-341 and V1Region (:343-478): region i is assigned at regions[i]; what the regions constrain to constants is kept, in
+    pass order, for `V1.synthesize` to place.  `.cs`, `.regions` and `.shapes` read as the single-pass layouter's."""
+
+    def __init__(self, cs: Assembly, regions, shapes):
+        self.cs, self.regions, self.shapes = cs, list(regions), list(shapes)
+        self.constants, self.table_columns = [], []                           # (constant, Cell); the table columns in use
+        self.region_index = 0
+
+    def assign_region(self, name, assignment):
+        if self.region_index >= len(self.regions):
+            raise Synthesis(f"the assignment pass asks for region {self.region_index}; the measurement pass saw {len(self.regions)}")
+        region = Region(self.region_index, self)
+        self.region_index += 1
+        result = assignment(region)
+        self.constants += region.constants
+        return result
+
+    def assign_table(self, name, assignment) -> None:
+        assign_table(self.cs, self.table_columns, assignment)
+
+    def constrain_instance(self, cell: Cell, instance: Column, row: int) -> None:
+        self.cs.copy(cell.column, self.regions[cell.region_index] + cell.row_offset, instance, row)
+
+    def namespace(self, name=None):
+        return _Namespace(self)
+
+
+class V1:
+    """`floor_planner = V1` on a `Circuit` class: two passes, first fit by advice area (v1.rs:59-141)."""
+
+    @staticmethod
+    def synthesize(cs: Assembly, circuit, config, constants) -> AssignmentPass:
+        measure = MeasurementPass(cs)
+        circuit.without_witnesses().synthesize(config, measure)
+        regions, allocations = slot_in_biggest_advice_first(measure.shapes)
+        end = first_unassigned_row(allocations)
+        plan = AssignmentPass(cs, regions, measure.shapes)
+        circuit.synthesize(config, plan)
+        positions = list(islice(constant_positions(allocations, constants, end), len(plan.constants)))
+        if len(positions) < len(plan.constants):
+            raise NotEnoughColumnsForConstants()
+        for (column, row), (constant, advice) in zip(positions, plan.constants):
+            cs.assign_fixed(column, row, lambda constant=constant: constant)
+            cs.copy(column, row, advice.column, regions[advice.region_index] + advice.row_offset)
+        return plan
