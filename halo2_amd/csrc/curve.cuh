@@ -13,6 +13,7 @@
 // order groups and (0, 0) is not on the curve, all-zero is unambiguous.
 #pragma once
 #include "field.cuh"
+#include "../../include/halo2_mi355x.h"   // H2_OUT_AFFINE / H2_OUT_JACOBIAN (point_out_store)
 
 namespace h2 {
 
@@ -189,6 +190,25 @@ template <int F> __device__ inline affine<F> xyzz_to_affine(const xyzz<F> &p) {
     r.x = fe_mulx<F>(p.x, fe_mulx<F>(i, p.zzz));   // X/ZZ
     r.y = fe_mulx<F>(p.y, fe_mulx<F>(i, p.zz));    // Y/ZZZ
     return r;
+}
+
+// A finished point, as an entry point hands it out: affine {x, y} (H2_OUT_AFFINE, 16 words) or Jacobian {X, Y, Z} (24 words), in Montgomery
+// form or (out_mont == 0) canonical.  One lane writes.
+__device__ __forceinline__ u32 point_out_words(int out_kind) { return out_kind == H2_OUT_AFFINE ? 16 : 24; }
+template <int F> __device__ __forceinline__ void point_out_store(u32 *out, const xyzz<F> &r, int out_kind, int out_mont) {
+    if (out_kind == H2_OUT_AFFINE) {
+        affine<F> a = xyzz_to_affine<F>(r);
+        if (!out_mont) { a.x = fe_from_mont<F>(a.x); a.y = fe_from_mont<F>(a.y); }
+        fe_store(out, a.x);
+        fe_store(out + 8, a.y);
+    } else {
+        fe X, Y, Z;
+        xyzz_to_jacobian<F>(r, X, Y, Z);
+        if (!out_mont) { X = fe_from_mont<F>(X); Y = fe_from_mont<F>(Y); Z = fe_from_mont<F>(Z); }
+        fe_store(out, X);
+        fe_store(out + 8, Y);
+        fe_store(out + 16, Z);
+    }
 }
 
 template <int F> __device__ __forceinline__ affine<F> aff_load(const void *p) {

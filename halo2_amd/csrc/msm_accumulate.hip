@@ -233,36 +233,9 @@ __global__ void __launch_bounds__(256) msm_segments_to_r256(const u32 *__restric
 }
 
 
-// ---- explicit instantiations (both curves) ----
-template __global__ void msm_bases_to_m9_glv<FP>(const u32 *__restrict__ bases, u32 *__restrict__ out, u32 n);
-template __global__ void msm_bases_to_m9_glv<FQ>(const u32 *__restrict__ bases, u32 *__restrict__ out, u32 n);
-template __global__ void msm_accumulate<FP, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FP, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FQ, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FQ, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FP, false, true, 512>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_accumulate<FQ, false, true, 512>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void msm_segments_to_r256<FP>(const u32 *__restrict__ raw, u32 *__restrict__ heads,
-                                                            u32 *__restrict__ buckets, u32 T, u32 total_buckets);
-template __global__ void msm_segments_to_r256<FQ>(const u32 *__restrict__ raw, u32 *__restrict__ heads,
-                                                            u32 *__restrict__ buckets, u32 T, u32 total_buckets);
+// ---- explicit instantiations (the lists beside the declarations in msm_internal.cuh) ----
+H2_INSTANCES_msm_bases_to_m9_glv(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_accumulate(H2_INSTANTIATE_KERNEL)
+H2_INSTANCES_msm_segments_to_r256(H2_INSTANTIATE_KERNEL)
 
 }  // namespace h2

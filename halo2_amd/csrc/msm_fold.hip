@@ -1,8 +1,14 @@
 // After the accumulate: finish (range heads into their buckets), the fold of a bucket slice down to its weighted sum, and the Horner step over
-// window slices (reference: the running-sum fold of arithmetic.rs:86-92 and the window loop of :169-178, restructured as trees).
+// window slices (reference: the running-sum fold of arithmetic.rs:86-92 and the window loop of :169-178, restructured as trees).  Two layers,
+// one of everything on each: the 8 x 32 fold (msm_finish_* .. msm_sum_slice; host side fold_r256) and the carry-free fold (fold9_*; host side
+// fold9_group).  The pieces they are made of -- head split, heavy ticket, gather and tree, plane arrival -- are in msm_internal.cuh, the plane
+// and launch arithmetic in msm_plan.h, the point writer in curve.cuh.  Every kernel here is launched from this file alone: the host functions
+// at its foot (declared in msm_internal.cuh) dispatch on the base field, which is what instantiates the kernels for both curves.
 #include "msm_internal.cuh"
 
 namespace h2 {
+
+static_assert(r256_tree_bytes(kTreeLanes) == (kTreeLanes / kGroup) * 128, "a quad of lanes per point of the 8 x 32 tree");
 
 // ---- finisher: bucket b = its own non-head segment + the heads of the ranges that begin inside it -----
 // Buckets owning more than kHeavy heads (scalars repeated thousands of times) are parked on a list and summed
@@ -16,28 +22,14 @@ __global__ void __launch_bounds__(256) msm_finish_buckets(const u32 *__restrict_
     const u32 b = (blockIdx.x * blockDim.x + threadIdx.x) / kGroup;
     if (b >= total_buckets) return;
     const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
-    const u32 M = starts[total_buckets];
-    T = eff_lanes(M, T, div);
-    const u32 chunk = max(1u, (M + T - 1) / T);
-    const u32 h0 = (starts[b] + chunk - 1) / chunk, h1 = (starts[b + 1] + chunk - 1) / chunk;
-    if (h1 <= h0) return;
-    if (h1 - h0 > kHeavy) {
-        u32 slot = 0;
-        if (lead) slot = atomicAdd(&heavy[1], 1u);
-        slot = (u32)__builtin_amdgcn_mov_dpp((int)slot, 0, 0xf, 0xf, false);   // quad lane 0's ticket
-        if (slot < kMaxHeavy) {
-            if (lead) {
-                heavy[2 + slot] = b;
-                atomicAdd(&heavy[0], 1u);
-            }
-            return;
-        }
-    }
+    const HeadRange h = bucket_heads<false>(starts, b, total_buckets, T, div);
+    if (h.h1 <= h.h0) return;
+    if (h.h1 - h.h0 > kHeavy && heavy_park<kGroup>(heavy, b, lead)) return;
     xyzz<FB> acc = xyzz_load<FB>(buckets + 32 * (size_t)b);
-    xyzz<FB> nxt = xyzz_load<FB>(heads + 32 * (size_t)h0);
-    for (u32 t = h0; t < h1; ++t) {
+    xyzz<FB> nxt = xyzz_load<FB>(heads + 32 * (size_t)h.h0);
+    for (u32 t = h.h0; t < h.h1; ++t) {
         xyzz<FB> p = nxt;
-        if (t + 1 < h1) nxt = xyzz_load<FB>(heads + 32 * (size_t)(t + 1));
+        if (t + 1 < h.h1) nxt = xyzz_load<FB>(heads + 32 * (size_t)(t + 1));
         xyzz_add_wide<FB>(acc, p);
     }
     if (lead) xyzz_store<FB>(buckets + 32 * (size_t)b, acc);
@@ -49,29 +41,11 @@ __global__ void __launch_bounds__(256) msm_finish_heavy(const u32 *__restrict__ 
     H2_LATENCY_STAGE();
     extern __shared__ __attribute__((aligned(16))) u32 sh[];
     if (blockIdx.y >= min(heavy[1], kMaxHeavy)) return;
-    const u32 b = heavy[2 + blockIdx.y], t = threadIdx.x / kGroup, nl = blockDim.x / kGroup;
-    const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
-    const u32 M = starts[total_buckets];
-    T = eff_lanes(M, T, div);
-    const u32 chunk = max(1u, (M + T - 1) / T);
-    const u32 h0 = (starts[b] + chunk - 1) / chunk, h1 = (starts[b + 1] + chunk - 1) / chunk;
-    const u32 share = (h1 - h0 + kHeavyBlocks - 1) / kHeavyBlocks;
-    const u32 lo = h0 + blockIdx.x * share, hi = min(h1, lo + share);
-    xyzz<FB> acc = xyzz_identity<FB>();
-    for (u32 i = lo + t; i < hi; i += nl) {
-        xyzz<FB> p = xyzz_load<FB>(heads + 32 * (size_t)i);
-        xyzz_add_wide<FB>(acc, p);
-    }
-    if (lead) xyzz_store<FB>(sh + 32 * t, acc);
-    __syncthreads();
-    for (u32 off = nl / 2; off > 0; off >>= 1) {
-        if (t < off) {
-            xyzz<FB> x = xyzz_load<FB>(sh + 32 * t), y = xyzz_load<FB>(sh + 32 * (t + off));
-            xyzz_add_wide<FB>(x, y);
-            if (lead) xyzz_store<FB>(sh + 32 * t, x);
-        }
-        __syncthreads();
-    }
+    const HeadRange h = bucket_heads<false>(starts, heavy[2 + blockIdx.y], total_buckets, T, div);
+    const u32 share = (h.h1 - h.h0 + kHeavyBlocks - 1) / kHeavyBlocks;
+    const u32 lo = h.h0 + blockIdx.x * share, hi = min(h.h1, lo + share);
+    const xyzz<FB> acc = r256_quad_gather<FB>(heads, hi > lo ? hi - lo : 0u, [lo](u32 k) { return lo + k; });
+    r256_quads_sum<FB>(acc, sh, blockDim.x / kGroup);
     if (threadIdx.x == 0) {
         xyzz<FB> r = xyzz_load<FB>(sh);
         xyzz_store<FB>(scratch + 32 * ((size_t)blockIdx.y * kHeavyBlocks + blockIdx.x), r);
@@ -92,16 +66,7 @@ __global__ void __launch_bounds__(64) msm_finish_heavy2(const u32 *__restrict__ 
         xyzz<FB> p = xyzz_load<FB>(src + 32 * i);
         xyzz_add_wide<FB>(acc, p);
     }
-    if (lead) xyzz_store<FB>(sh + 32 * q, acc);
-    __syncthreads();
-    for (u32 off = 8; off > 0; off >>= 1) {
-        if (q < off) {
-            xyzz<FB> x = xyzz_load<FB>(sh + 32 * q), y = xyzz_load<FB>(sh + 32 * (q + off));
-            xyzz_add_wide<FB>(x, y);
-            if (lead) xyzz_store<FB>(sh + 32 * q, x);
-        }
-        __syncthreads();
-    }
+    r256_quads_sum<FB>(acc, sh, 16);
     if (q == 0) {
         xyzz<FB> r = xyzz_load<FB>(sh), own = xyzz_load<FB>(buckets + 32 * (size_t)b);
         xyzz_add_wide<FB>(r, own);
@@ -131,7 +96,7 @@ __global__ void __launch_bounds__(256) msm_bucket_add(u32 *__restrict__ total, c
 template <int FB>
 __global__ void __launch_bounds__(256) fold9_finish(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
                                                     u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs) {
-    if (!cs.lowprio) H2_LATENCY_STAGE();        // (a fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps priority 0)
+    fold9_stage(cs);
     const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= total_buckets) return;
     if (gridDim.z > 1) {
@@ -140,28 +105,17 @@ __global__ void __launch_bounds__(256) fold9_finish(const u32 *__restrict__ head
         buckets9 = H2_COLZ(buckets9, cs.buckets);
         heavy = H2_COLZ(heavy, cs.heavy);
     }
-    const u32 base = starts[0];                      // (a slice group's view: see msm_accumulate)
-    const u32 M = starts[total_buckets] - base;
-    T = eff_lanes(M, T, div);
-    const u32 chunk = max(1u, (M + T - 1) / T);
-    const u32 h0 = (starts[b] - base + chunk - 1) / chunk, h1 = (starts[b + 1] - base + chunk - 1) / chunk;
-    if (h1 <= h0) return;
-    if (h1 - h0 > kHeavy) {
-        const u32 slot = atomicAdd(&heavy[1], 1u);
-        if (slot < kMaxHeavy) {
-            heavy[2 + slot] = b;
-            atomicAdd(&heavy[0], 1u);
-            return;
-        }
-    }
+    const HeadRange h = bucket_heads<true>(starts, b, total_buckets, T, div);      // (a slice group's view: see msm_accumulate)
+    if (h.h1 <= h.h0) return;
+    if (h.h1 - h.h0 > kHeavy && heavy_park<1>(heavy, b, true)) return;
     xyzz9<FB> acc = xyzz9_load_raw<FB>(buckets9 + 36 * (size_t)b);
-    for (u32 t = h0; t < h1; ++t) xyzz9_add<FB>(acc, xyzz9_load_raw<FB>(heads9 + 36 * (size_t)t));
+    for (u32 t = h.h0; t < h.h1; ++t) xyzz9_add<FB>(acc, xyzz9_load_raw<FB>(heads9 + 36 * (size_t)t));
     xyzz9_store_raw<FB>(buckets9 + 36 * (size_t)b, acc);
 }
 template <int FB>
 __global__ void __launch_bounds__(256, 3) fold9_finish_heavy(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
                                                           const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs) {
-    if (!cs.lowprio) H2_LATENCY_STAGE();        // (a fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps priority 0)
+    fold9_stage(cs);
     __shared__ __attribute__((aligned(16))) u32 sh[32 * 36];
     if (gridDim.z > 1) {
         heavy = H2_COLZ(heavy, cs.heavy);
@@ -173,15 +127,11 @@ __global__ void __launch_bounds__(256, 3) fold9_finish_heavy(const u32 *__restri
     // bucket -- 32 x 512 workgroups that found an empty list and left, ~12 us of dispatch per commit; a column has no heavy bucket
     // unless it is degenerate, and then a handful)
     const u32 count = min(heavy[1], kMaxHeavy);
-    const u32 base = starts[0];
-    const u32 M = starts[total_buckets] - base;
-    T = eff_lanes(M, T, div);
-    const u32 chunk = max(1u, (M + T - 1) / T);
+    const HeadSplit hs = head_split<true>(starts, total_buckets, T, div);
     for (u32 slot = blockIdx.y; slot < count; slot += gridDim.y) {
-        const u32 b = heavy[2 + slot];
-        const u32 h0 = (starts[b] - base + chunk - 1) / chunk, h1 = (starts[b + 1] - base + chunk - 1) / chunk;
-        const u32 share = (h1 - h0 + kHeavyBlocks - 1) / kHeavyBlocks;
-        const u32 lo = h0 + blockIdx.x * share, hi = min(h1, lo + share);
+        const HeadRange h = bucket_heads(hs, starts, heavy[2 + slot]);
+        const u32 share = (h.h1 - h.h0 + kHeavyBlocks - 1) / kHeavyBlocks;
+        const u32 lo = h.h0 + blockIdx.x * share, hi = min(h.h1, lo + share);
         xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(heads9, hi > lo ? hi - lo : 0u, [lo](u32 k) { return lo + k; });
         acc = fold9_quads_sum<FB>(acc, sh);
         if (fold9_root() && (threadIdx.x & (kGroup - 1)) == 0) xyzz9_store_raw<FB>(scratch9 + 36 * ((size_t)slot * kHeavyBlocks + blockIdx.x), acc);
@@ -191,7 +141,7 @@ __global__ void __launch_bounds__(256, 3) fold9_finish_heavy(const u32 *__restri
 template <int FB>
 __global__ void __launch_bounds__(64, 3) fold9_finish_heavy2(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
                                                              ColStride cs) {
-    if (!cs.lowprio) H2_LATENCY_STAGE();        // (a fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps priority 0)
+    fold9_stage(cs);
     __shared__ __attribute__((aligned(16))) u32 sh[8 * 36];
     if (gridDim.z > 1) {
         heavy = H2_COLZ(heavy, cs.heavy);
@@ -216,7 +166,7 @@ __global__ void __launch_bounds__(64, 3) fold9_finish_heavy2(const u32 *__restri
 // lines9[lo] = C_lo (lo < S), lines9[S + hi] = R_hi (1 <= hi < NR; row 0 carries weight 0 and is never formed), raw M9.
 template <int FB>
 __global__ void __launch_bounds__(256, 3) fold9_rowcol(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs) {
-    if (!cs.lowprio) H2_LATENCY_STAGE();        // (a fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps priority 0)
+    fold9_stage(cs);
     __shared__ __attribute__((aligned(16))) u32 sh[32 * 36];
     if (gridDim.z > 1) {
         buckets9 = H2_COLZ(buckets9, cs.buckets);
@@ -232,17 +182,15 @@ __global__ void __launch_bounds__(256, 3) fold9_rowcol(const u32 *__restrict__ b
         xyzz9_store_raw<FB>(lines9 + 36 * ((size_t)blockIdx.y * (S + NR) + (is_col ? id : S + id)), acc);
 }
 // The rest of the fold of a wide slice in ONE launch.  sum_j (j + 1) B_j = sum_lo (lo + 1) C_lo + S sum_hi hi R_hi is a sum of
-// `planes` = log2 S + log2 NR bit planes: plane t (weight 2^t) holds the columns with bit t of lo + 1 set (t < log2 S; plane
-// log2 S holds C_{S-1} alone) and the rows with bit t - log2 S of hi set.  Workgroup t sums plane t -- a tree over at most
+// `planes` = log2 S + log2 NR bit planes (msm_plan.h: which lines plane t holds).  Workgroup t sums plane t -- a tree over at most
 // S / 2 + NR / 2 lines --, doubles the sum t times (the planes do that side by side: the top plane's t doublings are the chain
-// nothing shortens, everything else hides behind it), and the workgroup that finishes LAST (a counter behind a fence; it leaves
-// the counter at zero for the next launch) adds the 16 weighted planes with one more tree: ~8 + 15 + 5 dependent quad-lane
-// operations, against the ~60 of a running sum over segments, a slice tree and a Horner step in three launches
-// (reduce_segments + sum_slice + combine: 126 us of a 1.28 ms commit; this kernel: ~70).
+// nothing shortens, everything else hides behind it), and the workgroup that finishes LAST (fold9_plane_arrive) adds the 16 weighted
+// planes with one more tree: ~8 + 15 + 5 dependent quad-lane operations, against the ~60 of a running sum over segments, a slice
+// tree and a Horner step in three launches (reduce_segments + sum_slice + combine: 126 us of a 1.28 ms commit; this kernel: ~70).
 template <int FB>
 __global__ void __launch_bounds__(256, 3) fold9_planes(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
                                                     int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs) {
-    if (!cs.lowprio) H2_LATENCY_STAGE();        // (a fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps priority 0)
+    fold9_stage(cs);
     __shared__ __attribute__((aligned(16))) u32 sh[32 * 36];
     __shared__ u32 s_last;
     if (gridDim.z > 1) {
@@ -252,57 +200,26 @@ __global__ void __launch_bounds__(256, 3) fold9_planes(const u32 *__restrict__ l
         out = co.out[blockIdx.z];
     }
     const u32 t = blockIdx.x, planes = gridDim.x;
-    const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
     lines9 += 36 * (size_t)blockIdx.y * (S + NR);                     // blockIdx.y: the bucket slice = the output (paired commits: 2)
     planes9 += 36 * (size_t)blockIdx.y * 32;
     counter += blockIdx.y;
-    out += (out_kind == kOutSliceSum ? 32 : out_kind == H2_OUT_AFFINE ? 16 : 24) * (size_t)blockIdx.y;
-    const u32 ncol = (int)t < cb ? S / 2 : (int)t == cb ? 1u : 0u, nrow = (int)t >= cb ? NR / 2 : 0u;
-    const u32 jc = t, jr = t - (u32)cb;
-    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(lines9, ncol + nrow, [=](u32 k) {
-        if (k < ncol) {
-            if ((int)jc == cb) return S - 1;                                                         // lo + 1 = S
-            return ((((k >> jc) << (jc + 1)) | (1u << jc) | (k & ((1u << jc) - 1u))) - 1u);         // k-th value of lo + 1 with bit jc set
-        }
-        const u32 r = k - ncol;
-        return S + (((r >> jr) << (jr + 1)) | (1u << jr) | (r & ((1u << jr) - 1u)));                // k-th hi with bit jr set
-    });
+    out += (out_kind == kOutSliceSum ? 32 : point_out_words(out_kind)) * (size_t)blockIdx.y;
+    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(lines9, fold9_plane_cols(S, cb, t) + fold9_plane_rows(NR, cb, t),
+                                                     [=](u32 k) { return fold9_plane_line(S, cb, t, k); });
     acc = fold9_quads_sum<FB>(acc, sh);
-    if (fold9_root()) {
-        for (u32 k = 0; k < t; ++k) acc = xyzz9_dbl_wide<FB>(acc);         // the plane's weight, applied here: the planes double side by side
-        if (lead) {
-            xyzz9_store_raw<FB>(planes9 + 36 * (size_t)t, acc);
-            __threadfence();
-            s_last = atomicAdd(counter, 1u) == planes - 1 ? 1u : 0u;
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
+    if (!fold9_plane_arrive<FB>(acc, t, planes9, counter, planes, s_last)) return;
     // the workgroup that arrived last adds the weighted planes (a tree again)
     acc = fold9_quad_gather<FB, H2_FOLD_D>(planes9, planes, [](u32 k) { return k; });
     acc = fold9_quads_sum<FB>(acc, sh);
     if (!fold9_root()) return;
     const xyzz<FB> r = xyzz9_to_r256_wide<FB>(acc);
-    if (!lead) return;
+    if ((threadIdx.x & (kGroup - 1)) != 0) return;
     *counter = 0;
     if (out_kind == kOutSliceSum) {              // a window slice of a generic multiexp: XYZZ in the reference's form, for msm_combine
         xyzz_store<FB>(out, r);
         return;
     }
-    if (out_kind == H2_OUT_AFFINE) {
-        affine<FB> o = xyzz_to_affine<FB>(r);
-        if (!out_mont) { o.x = fe_from_mont<FB>(o.x); o.y = fe_from_mont<FB>(o.y); }
-        fe_store(out, o.x);
-        fe_store(out + 8, o.y);
-    } else {
-        fe X, Y, Z;
-        xyzz_to_jacobian<FB>(r, X, Y, Z);
-        if (!out_mont) { X = fe_from_mont<FB>(X); Y = fe_from_mont<FB>(Y); Z = fe_from_mont<FB>(Z); }
-        fe_store(out, X);
-        fe_store(out + 8, Y);
-        fe_store(out + 16, Z);
-    }
+    point_out_store<FB>(out, r, out_kind, out_mont);
 }
 
 // The three tail kernels below run each logical lane as a quad of 4 hardware lanes (curve_wide.cuh): the chip
@@ -337,25 +254,10 @@ __global__ void __launch_bounds__(256) msm_sum_slice(const u32 *__restrict__ par
                                                      u32 share) {
     H2_LATENCY_STAGE();
     extern __shared__ __attribute__((aligned(16))) u32 sh[];
-    const u32 sl = blockIdx.y, blk = blockIdx.x, t = threadIdx.x / kGroup, nl = blockDim.x / kGroup;
-    const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
+    const u32 sl = blockIdx.y, blk = blockIdx.x;
     const u32 lo = blk * share, hi = min(per_slice, lo + share);
-    const u32 *src = partial + 32 * (size_t)sl * per_slice;
-    xyzz<FB> acc = xyzz_identity<FB>();
-    for (u32 i = lo + t; i < hi; i += nl) {
-        xyzz<FB> p = xyzz_load<FB>(src + 32 * (size_t)i);
-        xyzz_add_wide<FB>(acc, p);
-    }
-    if (lead) xyzz_store<FB>(sh + 32 * t, acc);
-    __syncthreads();
-    for (u32 off = nl / 2; off > 0; off >>= 1) {
-        if (t < off) {
-            xyzz<FB> a = xyzz_load<FB>(sh + 32 * t), b = xyzz_load<FB>(sh + 32 * (t + off));
-            xyzz_add_wide<FB>(a, b);
-            if (lead) xyzz_store<FB>(sh + 32 * t, a);
-        }
-        __syncthreads();
-    }
+    const xyzz<FB> acc = r256_quad_gather<FB>(partial + 32 * (size_t)sl * per_slice, hi > lo ? hi - lo : 0u, [lo](u32 k) { return lo + k; });
+    r256_quads_sum<FB>(acc, sh, blockDim.x / kGroup);
     if (threadIdx.x == 0) {
         xyzz<FB> r = xyzz_load<FB>(sh);
         xyzz_store<FB>(out + 32 * ((size_t)sl * gridDim.x + blk), r);
@@ -372,27 +274,11 @@ template <int FB>
 __global__ void __launch_bounds__(256) msm_rowcol_sums(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR) {
     H2_LATENCY_STAGE();
     extern __shared__ __attribute__((aligned(16))) u32 sh[];
-    const u32 t = threadIdx.x / kGroup, nl = blockDim.x / kGroup;
-    const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
     const bool is_col = blockIdx.x < S;
     const u32 id = is_col ? blockIdx.x : blockIdx.x - S + 1;          // column lo, or row hi (row 0 carries weight 0)
-    const u32 cnt = is_col ? NR : S;
     const size_t base = is_col ? id : (size_t)id * S, step = is_col ? S : 1;
-    xyzz<FB> acc = xyzz_identity<FB>();
-    for (u32 i = t; i < cnt; i += nl) {
-        xyzz<FB> p = xyzz_load<FB>(buckets + 32 * (base + (size_t)i * step));
-        xyzz_add_wide<FB>(acc, p);
-    }
-    if (lead) xyzz_store<FB>(sh + 32 * t, acc);
-    __syncthreads();
-    for (u32 off = nl / 2; off > 0; off >>= 1) {
-        if (t < off) {
-            xyzz<FB> a = xyzz_load<FB>(sh + 32 * t), b = xyzz_load<FB>(sh + 32 * (t + off));
-            xyzz_add_wide<FB>(a, b);
-            if (lead) xyzz_store<FB>(sh + 32 * t, a);
-        }
-        __syncthreads();
-    }
+    const xyzz<FB> acc = r256_quad_gather<FB>(buckets, is_col ? NR : S, [base, step](u32 k) { return base + (size_t)k * step; });
+    r256_quads_sum<FB>(acc, sh, blockDim.x / kGroup);
     if (threadIdx.x == 0) {
         xyzz<FB> r = xyzz_load<FB>(sh);
         xyzz_store<FB>(wide + 32 * (is_col ? (size_t)id : (size_t)NR + id - 1), r);
@@ -413,7 +299,7 @@ __global__ void __launch_bounds__(64) msm_combine(const u32 *__restrict__ slice_
     // one block: Horner over the slices.  Several blocks (pair commits): block b emits slice b alone as output b.
     if (gridDim.x > 1) {
         slice_sums += 32 * (size_t)blockIdx.x;
-        out += (out_kind == H2_OUT_AFFINE ? 16 : 24) * (size_t)blockIdx.x;
+        out += point_out_words(out_kind) * (size_t)blockIdx.x;
         slices = 1;
     }
     // the chain runs on the carry-free layer (curve9_wide.cuh): ~850 instructions per doubling against ~1300, and the 128-130
@@ -434,19 +320,7 @@ __global__ void __launch_bounds__(64) msm_combine(const u32 *__restrict__ slice_
         xyzz_store<FB>(out, r);
         return;
     }
-    if (out_kind == H2_OUT_AFFINE) {
-        affine<FB> a = xyzz_to_affine<FB>(r);
-        if (!out_mont) { a.x = fe_from_mont<FB>(a.x); a.y = fe_from_mont<FB>(a.y); }
-        fe_store(out, a.x);
-        fe_store(out + 8, a.y);
-    } else {
-        fe X, Y, Z;
-        xyzz_to_jacobian<FB>(r, X, Y, Z);
-        if (!out_mont) { X = fe_from_mont<FB>(X); Y = fe_from_mont<FB>(Y); Z = fe_from_mont<FB>(Z); }
-        fe_store(out, X);
-        fe_store(out + 8, Y);
-        fe_store(out + 16, Z);
-    }
+    point_out_store<FB>(out, r, out_kind, out_mont);
 }
 
 template <int FB>
@@ -469,99 +343,86 @@ __global__ void __launch_bounds__(64) msm_combine_ranges(RangeSums rs, int range
         xyzz9_add_wide<FB>(r9, xyzz9_load_raw<FB>(sh + 36 * s));
     }
     const xyzz<FB> r = xyzz9_to_r256_wide<FB>(r9);
-    if (threadIdx.x != 0) return;
-    if (out_kind == H2_OUT_AFFINE) {
-        affine<FB> a = xyzz_to_affine<FB>(r);
-        if (!out_mont) { a.x = fe_from_mont<FB>(a.x); a.y = fe_from_mont<FB>(a.y); }
-        fe_store(out, a.x);
-        fe_store(out + 8, a.y);
-    } else {
-        fe X, Y, Z;
-        xyzz_to_jacobian<FB>(r, X, Y, Z);
-        if (!out_mont) { X = fe_from_mont<FB>(X); Y = fe_from_mont<FB>(Y); Z = fe_from_mont<FB>(Z); }
-        fe_store(out, X);
-        fe_store(out + 8, Y);
-        fe_store(out + 16, Z);
-    }
+    if (threadIdx.x == 0) point_out_store<FB>(out, r, out_kind, out_mont);
 }
 
+// ---- host: every launch of the kernels above (declared in msm_internal.cuh) -------------------------------------------------------------------
+// H2_FOLD_FB(fb, f, args...): f<FP>(args...) or f<FQ>(args...)
+#define H2_FOLD_FB(fb, f, ...) ((fb) == FP ? f<FP>(__VA_ARGS__) : f<FQ>(__VA_ARGS__))
 
-// ---- explicit instantiations (both curves) ----
-template __global__ void msm_finish_buckets<FP>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                          u32 *__restrict__ buckets, u32 *__restrict__ heavy,
-                                                          u32 total_buckets, u32 T, u32 div);
-template __global__ void msm_finish_buckets<FQ>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                          u32 *__restrict__ buckets, u32 *__restrict__ heavy,
-                                                          u32 total_buckets, u32 T, u32 div);
-template __global__ void msm_finish_heavy<FP>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                        u32 *__restrict__ scratch, const u32 *__restrict__ heavy,
-                                                        u32 total_buckets, u32 T, u32 div);
-template __global__ void msm_finish_heavy<FQ>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                        u32 *__restrict__ scratch, const u32 *__restrict__ heavy,
-                                                        u32 total_buckets, u32 T, u32 div);
-template __global__ void msm_finish_heavy2<FP>(const u32 *__restrict__ scratch, u32 *__restrict__ buckets,
-                                                        const u32 *__restrict__ heavy);
-template __global__ void msm_finish_heavy2<FQ>(const u32 *__restrict__ scratch, u32 *__restrict__ buckets,
-                                                        const u32 *__restrict__ heavy);
-template __global__ void msm_bucket_add<FP>(u32 *__restrict__ total, const u32 *__restrict__ part, u32 nb);
-template __global__ void msm_bucket_add<FQ>(u32 *__restrict__ total, const u32 *__restrict__ part, u32 nb);
-template __global__ void fold9_finish<FP>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
-                                                    u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void fold9_finish<FQ>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
-                                                    u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void fold9_finish_heavy<FP>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
-                                                          const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void fold9_finish_heavy<FQ>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
-                                                          const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template __global__ void fold9_finish_heavy2<FP>(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
-                                                             ColStride cs);
-template __global__ void fold9_finish_heavy2<FQ>(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
-                                                             ColStride cs);
-template __global__ void fold9_rowcol<FP>(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs);
-template __global__ void fold9_rowcol<FQ>(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs);
-template __global__ void fold9_planes<FP>(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
-                                                    int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs);
-template __global__ void fold9_planes<FQ>(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
-                                                    int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs);
-template __global__ void msm_reduce_segments<FP>(const u32 *__restrict__ buckets, u32 *__restrict__ partial,
-                                                           u32 NB, u32 total_segments, int seg);
-template __global__ void msm_reduce_segments<FQ>(const u32 *__restrict__ buckets, u32 *__restrict__ partial,
-                                                           u32 NB, u32 total_segments, int seg);
-template __global__ void msm_sum_slice<FP>(const u32 *__restrict__ partial, u32 *__restrict__ out, u32 per_slice,
-                                                     u32 share);
-template __global__ void msm_sum_slice<FQ>(const u32 *__restrict__ partial, u32 *__restrict__ out, u32 per_slice,
-                                                     u32 share);
-template __global__ void msm_rowcol_sums<FP>(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR);
-template __global__ void msm_rowcol_sums<FQ>(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR);
-template __global__ void msm_combine<FP>(const u32 *__restrict__ slice_sums, int slices, int c, u32 *__restrict__ out,
-                                                  int out_kind, int out_mont, int extra_dbl, const u32 *__restrict__ addend, int addend_first);
-template __global__ void msm_combine<FQ>(const u32 *__restrict__ slice_sums, int slices, int c, u32 *__restrict__ out,
-                                                  int out_kind, int out_mont, int extra_dbl, const u32 *__restrict__ addend, int addend_first);
-template __global__ void msm_combine_ranges<FP>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
-template __global__ void msm_combine_ranges<FQ>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
-
-// ---- host: the five launches of the carry-free fold, for every caller (declared in msm_internal.cuh)
-template <int FB>
-void fold9_group(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
-                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
-                 const ColOut &co, const ColStride &cs) {
-    const u32 fz = cs.joined ? 1 : cols, ftb = cs.joined ? cols * tb : tb;       // joined columns: one pass over the cols x tb buckets
-    int cb = 0;
-    while ((1u << cb) < wideS) ++cb;
-    u32 *lines = lines9 + 36 * (size_t)slice0 * (wideS + wideNR);
-    hipLaunchKernelGGL((fold9_finish<FB>), dim3((ftb + 255) / 256, 1, fz), dim3(256), 0, st, heads9, starts, buckets9, heavy, ftb, T, lane_div, cs);
-    hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows, fz), dim3(256), 0, st, heads9, starts, hscratch, (const u32 *)heavy, ftb, T, lane_div, cs);
-    hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows, 1, fz), dim3(64), 0, st, (const u32 *)hscratch, buckets9, (const u32 *)heavy, cs);
+// the five launches of the carry-free fold
+template <int FB> static void fold9_group_launch(hipStream_t st, const Fold9Group &g) {
+    const ColStride &cs = g.cs;
+    const u32 fz = cs.joined ? 1 : g.cols, ftb = cs.joined ? g.cols * g.tb : g.tb;       // joined columns: one pass over the cols x tb buckets
+    const u32 S = g.wideS, NR = g.wideNR;
+    u32 *lines = g.lines9 + 36 * (size_t)g.slice0 * (S + NR);
+    hipLaunchKernelGGL((fold9_finish<FB>), dim3((ftb + 255) / 256, 1, fz), dim3(256), 0, st, g.heads9, g.starts, g.buckets9, g.heavy, ftb, g.T, g.lane_div, cs);
+    hipLaunchKernelGGL((fold9_finish_heavy<FB>), dim3(kHeavyBlocks, kHeavyRows, fz), dim3(256), 0, st, g.heads9, g.starts, g.hscratch, (const u32 *)g.heavy, ftb, g.T, g.lane_div, cs);
+    hipLaunchKernelGGL((fold9_finish_heavy2<FB>), dim3(kHeavyRows, 1, fz), dim3(64), 0, st, (const u32 *)g.hscratch, g.buckets9, (const u32 *)g.heavy, cs);
     // line sums, then the bit planes of the line weights and their combination in one launch (fold9_planes)
-    hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(wideS + wideNR - 1, nslices, cols), dim3(256), 0, st, (const u32 *)buckets9, lines, wideS, wideNR, cs);
-    hipLaunchKernelGGL((fold9_planes<FB>), dim3(c - 1, nslices, cols), dim3(256), 0, st, (const u32 *)lines, planes9 + 36 * (size_t)slice0 * 32, ctr + slice0, wideS, wideNR,
-                       cb, out + 32 * (size_t)slice0, out_kind, out_mont ? 1 : 0, co, cs);
+    hipLaunchKernelGGL((fold9_rowcol<FB>), dim3(S + NR - 1, g.nslices, g.cols), dim3(256), 0, st, (const u32 *)g.buckets9, lines, S, NR, cs);
+    hipLaunchKernelGGL((fold9_planes<FB>), dim3(fold9_plane_count(g.c), g.nslices, g.cols), dim3(256), 0, st, (const u32 *)lines, g.planes9 + 36 * (size_t)g.slice0 * 32, g.ctr + g.slice0, S, NR,
+                       fold9_col_bits(S), g.out + 32 * (size_t)g.slice0, g.out_kind, g.out_mont ? 1 : 0, g.co, cs);
 }
-template void fold9_group<FP>(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
-                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
-                 const ColOut &co, const ColStride &cs);
-template void fold9_group<FQ>(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
-                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
-                 const ColOut &co, const ColStride &cs);
+void fold9_group(int fb, hipStream_t st, const Fold9Group &g) { H2_FOLD_FB(fb, fold9_group_launch, st, g); }
+
+template <int FB> static void combine_launch(hipStream_t st, size_t lds, u32 outputs, const u32 *slice_sums, int slices, int c, u32 *out, int out_kind, bool out_mont,
+                                             int extra_dbl, const u32 *addend, bool addend_first) {
+    hipLaunchKernelGGL((msm_combine<FB>), dim3(outputs), dim3(64), lds, st, slice_sums, slices, c, out, out_kind, out_mont ? 1 : 0, extra_dbl, addend, addend_first ? 1 : 0);
+}
+void msm_combine_launch(int fb, hipStream_t st, size_t lds, u32 outputs, const u32 *slice_sums, int slices, int c, u32 *out, int out_kind, bool out_mont,
+                        int extra_dbl, const u32 *addend, bool addend_first) {
+    H2_FOLD_FB(fb, combine_launch, st, lds, outputs, slice_sums, slices, c, out, out_kind, out_mont, extra_dbl, addend, addend_first);
+}
+int msm_combine_allow_lds(size_t bytes) {
+    H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return H2_OK;
+}
+template <int FB> static void combine_ranges_launch(hipStream_t st, const RangeSums &rs, int ranges, int slices, int c, u32 *out, int out_kind, bool out_mont) {
+    hipLaunchKernelGGL((msm_combine_ranges<FB>), dim3(1), dim3(64), 0, st, rs, ranges, slices, c, out, out_kind, out_mont ? 1 : 0);
+}
+void msm_combine_ranges_launch(int fb, hipStream_t st, const RangeSums &rs, int ranges, int slices, int c, u32 *out, int out_kind, bool out_mont) {
+    H2_FOLD_FB(fb, combine_ranges_launch, st, rs, ranges, slices, c, out, out_kind, out_mont);
+}
+template <int FB> static void bucket_add_launch(hipStream_t st, u32 *total, const u32 *part, u32 nb) {
+    hipLaunchKernelGGL((msm_bucket_add<FB>), dim3((nb * kGroup + 255) / 256), dim3(256), 0, st, total, part, nb);
+}
+void msm_bucket_add_launch(int fb, hipStream_t st, u32 *total, const u32 *part, u32 nb) { H2_FOLD_FB(fb, bucket_add_launch, st, total, part, nb); }
+
+// the 8 x 32 finisher and fold (the geometry: r256_fold_geometry, msm_plan.h)
+template <int FB> static int fold_r256_launch(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
+    const u32 tb = p.tb, T = p.T;
+    const size_t tree_lds = r256_tree_bytes(kTreeLanes);
+    if (!p.fold_only) {
+        hipLaunchKernelGGL((msm_finish_buckets<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, cx.heads.as<u32>(),
+                           cx.starts.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
+        hipLaunchKernelGGL((msm_finish_heavy<FB>), dim3(kHeavyBlocks, kMaxHeavy), dim3(kTreeLanes), tree_lds, st,
+                           cx.heads.as<u32>(), cx.starts.as<u32>(), cx.hscratch.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
+        hipLaunchKernelGGL((msm_finish_heavy2<FB>), dim3(kMaxHeavy), dim3(64), 0, st, cx.hscratch.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>());
+    }
+    if (p.add_only) {
+        bucket_add_launch<FB>(st, a.add_into, cx.buckets.as<u32>(), tb);
+        return H2_OK;
+    }
+    // what the fold runs over: the bucket slices themselves, or (wide slices) the row / column sums as two slices
+    const R256Fold f = r256_fold_geometry(p.sh, p.wide_reduce, p.wideNR);
+    const u32 *fold_src = p.fold_only ? a.fold_from : cx.buckets.as<u32>();
+    if (p.wide_reduce) {
+        u32 *wide = cx.partial.as<u32>() + 32 * (size_t)(2 * p.wideNR / kSeg);     // after the fold's own partials
+        H2_HIP(hipMemsetAsync(wide, 0, (size_t)2 * p.wideNR * 128, st));
+        hipLaunchKernelGGL((msm_rowcol_sums<FB>), dim3(p.wideS + p.wideNR - 1), dim3(kTreeLanes), tree_lds, st, fold_src, wide, p.wideS, p.wideNR);
+        fold_src = wide;
+    }
+    hipLaunchKernelGGL((msm_reduce_segments<FB>), dim3((f.segs * kGroup + 255) / 256), dim3(256), 0, st, fold_src, cx.partial.as<u32>(), f.nb, f.segs, f.seg);
+    for (int l = 0; l < f.levels; ++l) {      // partials -> (heads[], free again: the first level's output ->) slice sums
+        const R256Fold::Level &v = f.level[l];
+        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(v.blocks, f.slices), dim3(kTreeLanes), tree_lds, st, l ? cx.heads.as<u32>() : cx.partial.as<u32>(),
+                           l == f.levels - 1 ? cx.ssums.as<u32>() : cx.heads.as<u32>(), v.per_slice, v.share);
+    }
+    combine_launch<FB>(st, 0, p.pair ? 2 : 1, cx.ssums.as<u32>(), (int)f.slices, f.c, (u32 *)a.d_out, a.out_kind, a.form == H2_FORM_MONTGOMERY, 0, nullptr, false);
+    return H2_OK;
+}
+int fold_r256(int fb, MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) { return H2_FOLD_FB(fb, fold_r256_launch, cx, p, a, st); }
 
 }  // namespace h2

@@ -64,8 +64,7 @@ int grouped_reserve(MsmContext &cx, const GroupedPlan &gp, u32 m, u32 W, u32 NB,
     if (!cx.attr_grouped_set) {       // (one flag per context: both curves' chain links, whichever curve comes first)
         H2_HIP(hipFuncSetAttribute((const void *)msm_d1_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
         H2_HIP(hipFuncSetAttribute((const void *)msm_s2_bins, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-        H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        H2_HIP(hipFuncSetAttribute((const void *)msm_combine<FQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        if ((rc = msm_combine_allow_lds(128 * 1024)) != H2_OK) return rc;
         cx.attr_grouped_set = true;
     }
     // Hardware queues.  HIP multiplexes streams onto a handful of hardware queues (four per priority level), and every packet of a queue waits
@@ -119,9 +118,7 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     auto ev_chain = [&](int g) { return cx.gev[4 + 3 * g]; };
     auto fold_s = [&](int g) { return g == G - 1 ? st : cx.gstream[(g & 1) ? 2 : 0]; };          // the last group folds behind its accumulate
 
-    ColOut co;
     ColStride cs;
-    memset(&co, 0, sizeof co);
     memset(&cs, 0, sizeof cs);
     const bool mont = a.form == H2_FORM_MONTGOMERY;
     uint16_t *digits = cx.digits.as<uint16_t>();
@@ -163,9 +160,26 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
     // a group's fold down to its slice sums: finish (range heads into their buckets), the heavy buckets, line sums, planes
     auto fold_group = [&](int g, hipStream_t s_) {
         const Group &q = grp[g];
-        fold9_group<FB>(s_, heads_of[g], cx.starts.as<u32>() + q.starts_off, buckets_all + 36 * q.bucket_off, cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2),
-                        cx.hscratch.as<u32>() + (size_t)g * kMaxHeavy * kHeavyBlocks * 36, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
-                        q.tb, q.T, kLaneDiv, (int)c, wideS, wideNR, q.w0, q.ns, 1u, co, cs);
+        Fold9Group f;
+        f.heads9 = heads_of[g];
+        f.starts = cx.starts.as<u32>() + q.starts_off;
+        f.buckets9 = buckets_all + 36 * q.bucket_off;
+        f.heavy = cx.heavy.as<u32>() + (size_t)g * (kMaxHeavy + 2);
+        f.hscratch = cx.hscratch.as<u32>() + (size_t)g * kMaxHeavy * kHeavyBlocks * 36;
+        f.lines9 = lines9;
+        f.planes9 = planes9;
+        f.ctr = cx.fold_ctr.as<u32>();
+        f.out = ssums;
+        f.out_mont = mont;
+        f.tb = q.tb;
+        f.T = q.T;
+        f.lane_div = kLaneDiv;
+        f.c = (int)c;
+        f.wideS = wideS;
+        f.wideNR = wideNR;
+        f.slice0 = q.w0;
+        f.nslices = q.ns;
+        fold9_group(FB, s_, f);      // (one column, no strides; slice sums out)
     };
 
     // ---- sorts: the first group on the caller's stream, the others on the side stream behind it (they share hist / tagged / plan)
@@ -193,15 +207,15 @@ int msm_generic_grouped(MsmContext &cx, const MsmArgs &a, const MsmShape &sh, si
             fold_group(g, fs);
             if (g) H2_HIP(hipStreamWaitEvent(fs, ev_chain(g - 1), 0));
             // A_g = Horner(group g) + D_(g-1);  D_g = 2^(c ns_(g+1)) A_g, an XYZZ point behind the slice sums
-            hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), gp.lds_fence ? 100 * 1024 : 0, fs, (const u32 *)(ssums + 32 * (size_t)q.w0), (int)q.ns, (int)c, ssums + 32 * (size_t)(W + g), kOutSliceSum, 1,
-                               (int)(c * grp[g + 1].ns), g ? (const u32 *)(ssums + 32 * (size_t)(W + g - 1)) : (const u32 *)nullptr, 1);
+            msm_combine_launch(FB, fs, gp.lds_fence ? 100 * 1024 : 0, 1, ssums + 32 * (size_t)q.w0, (int)q.ns, (int)c, ssums + 32 * (size_t)(W + g), kOutSliceSum, true,
+                               (int)(c * grp[g + 1].ns), g ? ssums + 32 * (size_t)(W + g - 1) : nullptr, true);
             H2_HIP(hipEventRecord(ev_chain(g), fs));
         }
     }
     fold_group(G - 1, st);
     if (G > 1) H2_HIP(hipStreamWaitEvent(st, ev_chain(G - 2), 0));
-    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)(ssums + 32 * (size_t)grp[G - 1].w0), (int)grp[G - 1].ns, (int)c, (u32 *)a.d_out, a.out_kind,
-                       mont ? 1 : 0, 0, G > 1 ? (const u32 *)(ssums + 32 * (size_t)(W + G - 2)) : (const u32 *)nullptr, 1);
+    msm_combine_launch(FB, st, 0, 1, ssums + 32 * (size_t)grp[G - 1].w0, (int)grp[G - 1].ns, (int)c, (u32 *)a.d_out, a.out_kind, mont, 0,
+                       G > 1 ? ssums + 32 * (size_t)(W + G - 2) : nullptr, true);
     H2_HIP(hipGetLastError());
     if (st != caller) {               // ... and the caller's stream for the result
         H2_HIP(hipEventRecord(cx.gev[3 + 3 * G], st));

@@ -155,8 +155,7 @@ static int msm_host_chunked(MsmContext &cx, int curve, const uint64_t *scalars, 
         RangeSums rs;
         memset(&rs, 0, sizeof rs);
         for (unsigned q = 0; q < Q; ++q) rs.p[q] = hp.ctx[q]->ssums.as<u32>();
-        if (curve == H2_PALLAS) hipLaunchKernelGGL((msm_combine_ranges<FP>), dim3(1), dim3(64), 0, hp.light, rs, (int)Q, slices, c, cx.out.as<u32>(), out_kind, form == H2_FORM_MONTGOMERY);
-        else hipLaunchKernelGGL((msm_combine_ranges<FQ>), dim3(1), dim3(64), 0, hp.light, rs, (int)Q, slices, c, cx.out.as<u32>(), out_kind, form == H2_FORM_MONTGOMERY);
+        msm_combine_ranges_launch(base_field(curve), hp.light, rs, (int)Q, slices, c, cx.out.as<u32>(), out_kind, form == H2_FORM_MONTGOMERY);
         H2_HIP(hipGetLastError());
         return (int)H2_OK;
     };
@@ -486,11 +485,7 @@ static int commit_host_pipelined_locked(HostPipe &hp, Bases &b, const uint64_t *
         H2_HIP(hipStreamWaitEvent(hp.copy, hp.done[j], 0));
     }
     if (rc == H2_OK) {
-        if (used == 2) {
-            const dim3 grid((unsigned)((nb * kGroup + 255) / 256)), blk(256);
-            if (b.curve == H2_PALLAS) hipLaunchKernelGGL((msm_bucket_add<FP>), grid, blk, 0, hp.copy, total[0], (const u32 *)total[1], (u32)nb);
-            else hipLaunchKernelGGL((msm_bucket_add<FQ>), grid, blk, 0, hp.copy, total[0], (const u32 *)total[1], (u32)nb);
-        }
+        if (used == 2) msm_bucket_add_launch(base_field(b.curve), hp.copy, total[0], total[1], (u32)nb);
         MsmContext &cx = msm_ctx(hp.copy);
         std::lock_guard<std::mutex> cl(cx.mu);
         MsmArgs a{nullptr, nullptr, b.d_table, nullptr, 0, true, b.c, b.stride, (u32)b.n, form, out_kind, d_res};

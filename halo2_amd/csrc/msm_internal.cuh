@@ -1,7 +1,9 @@
 // Internal header of the multi-scalar-multiplication translation units (msm_*.hip): constants, the structures that travel between
-// the host orchestration and the kernels, small device helpers more than one unit uses, and the declarations of every kernel and
-// host function that is defined in one unit and used from another.  Kernels are templates on the base field FB / scalar field FS
-// (FP = 0, FQ = 1); the unit that defines one instantiates it explicitly for both curves and the others see `extern template`.
+// the host orchestration and the kernels, small device helpers more than one unit uses (among them the fold's shared pieces: head split,
+// heavy ticket, gather and tree of either layer, plane arrival), and the declarations of every kernel and host function that is defined in
+// one unit and used from another.  Kernels are templates on the base field FB / scalar field FS (FP = 0, FQ = 1).  A kernel of the sort or
+// the accumulate lists its instances ONCE beside its declaration (H2_INSTANCES_<kernel>): `extern template` here, the instantiations at the
+// foot of its unit.  The fold's kernels are declared nowhere: msm_fold.hip launches them all, behind host functions that take the base field.
 // Nothing here is part of the C ABI (include/halo2_mi355x.h).
 #pragma once
 #include <algorithm>
@@ -84,20 +86,86 @@ __device__ __forceinline__ u32 upper_bucket(const u32 *__restrict__ arr, u32 n, 
     return lo;
 }
 
-// finisher constants: buckets owning more than kHeavy range heads are parked on a list and summed by whole workgroups
+// ---- the fold's shared pieces (msm_fold.hip, msm_subdigit.hip): one of each per layer -- `xyzz` on 8 x 32 limbs, `xyzz9` carry-free ------------
+// buckets owning more than kHeavy range heads are parked on a list and summed by whole workgroups
 static constexpr u32 kHeavy = 64;
 static constexpr u32 kHeavyRows = 16;     // workgroup rows of the heavy-bucket launches: they walk the list (at most kMaxHeavy long, usually empty)
-// ---- the levels after that: trees, on quads of lanes ---------------------------------------------------------------------------
+static constexpr int kOutSliceSum = 100;  // out_kind of fold9_planes / msm_combine: the sum as XYZZ (32 words) instead of a finished point
+#ifndef H2_FOLD_D
+#define H2_FOLD_D 2
+#endif
+// A fold with slack -- a group of a generic multiexp folded beside the next group's accumulate -- keeps wave priority 0 (ColStride::lowprio);
+// every other fold is a latency stage.
+__device__ __forceinline__ void fold9_stage(const ColStride &cs) {
+    if (!cs.lowprio) H2_LATENCY_STAGE();
+}
+// The range heads of a bucket: the accumulate cut the M sorted entries into ranges of `chunk`, and bucket b owns the heads [h0, h1) of the
+// ranges that begin inside it.  VIEW: `starts` is a slice group's view into a longer boundary array, so positions count from starts[0]
+// (the carry-free kernels); the 8 x 32 kernels' array begins at zero and they do not load it.
+struct HeadSplit {
+    u32 base, chunk;
+    __device__ __forceinline__ u32 head(u32 pos) const { return (pos - base + chunk - 1) / chunk; }
+};
+struct HeadRange {
+    u32 h0, h1;
+};
+template <bool VIEW> __device__ __forceinline__ HeadSplit head_split(const u32 *__restrict__ starts, u32 total_buckets, u32 T, u32 div) {
+    const u32 base = VIEW ? starts[0] : 0u, M = starts[total_buckets] - base;
+    T = eff_lanes(M, T, div);
+    return {base, max(1u, (M + T - 1) / T)};
+}
+__device__ __forceinline__ HeadRange bucket_heads(const HeadSplit &hs, const u32 *__restrict__ starts, u32 b) {
+    return {hs.head(starts[b]), hs.head(starts[b + 1])};
+}
+template <bool VIEW> __device__ __forceinline__ HeadRange bucket_heads(const u32 *__restrict__ starts, u32 b, u32 total_buckets, u32 T, u32 div) {
+    return bucket_heads(head_split<VIEW>(starts, total_buckets, T, div), starts, b);
+}
+// Parks bucket b on the heavy list (heavy[0]: parked, heavy[1]: tickets drawn, heavy[2 ..]: the list) and says whether it found room; a bucket
+// beyond kMaxHeavy is summed in place by the caller.  LANES lanes act for the bucket: lane 0 of them (`lead`) draws the ticket, the others
+// learn it by DPP.
+template <int LANES> __device__ __forceinline__ bool heavy_park(u32 *__restrict__ heavy, u32 b, bool lead) {
+    u32 slot = 0;
+    if (LANES == 1 || lead) slot = atomicAdd(&heavy[1], 1u);
+    if (LANES > 1) slot = (u32)__builtin_amdgcn_mov_dpp((int)slot, 0, 0xf, 0xf, false);   // quad lane 0's ticket
+    if (slot >= kMaxHeavy) return false;
+    if (LANES == 1 || lead) {
+        heavy[2 + slot] = b;
+        atomicAdd(&heavy[0], 1u);
+    }
+    return true;
+}
+// The 8 x 32 layer's tree.  Quad q of the workgroup sums the points src[32 * index(k)], k = q, q + nq, ... < count ...
+template <int FB, class Index> __device__ __forceinline__ xyzz<FB> r256_quad_gather(const u32 *__restrict__ src, u32 count, Index index) {
+    const u32 q = threadIdx.x / kGroup, nq = blockDim.x / kGroup;
+    xyzz<FB> acc = xyzz_identity<FB>();
+    for (u32 k = q; k < count; k += nq) {
+        xyzz<FB> p = xyzz_load<FB>(src + 32 * (size_t)index(k));
+        xyzz_add_wide<FB>(acc, p);
+    }
+    return acc;
+}
+// ... and the sum of the nq (a power of two) points the quads hold lands in sh[0 .. 32), behind a barrier; sh: nq points
+template <int FB> __device__ __forceinline__ void r256_quads_sum(const xyzz<FB> &acc, u32 *sh, u32 nq) {
+    const u32 q = threadIdx.x / kGroup;
+    const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
+    if (lead) xyzz_store<FB>(sh + 32 * q, acc);
+    __syncthreads();
+    for (u32 off = nq / 2; off > 0; off >>= 1) {
+        if (q < off) {
+            xyzz<FB> x = xyzz_load<FB>(sh + 32 * q), y = xyzz_load<FB>(sh + 32 * (q + off));
+            xyzz_add_wide<FB>(x, y);
+            if (lead) xyzz_store<FB>(sh + 32 * q, x);
+        }
+        __syncthreads();
+    }
+}
+// ---- the carry-free layer's tree, on quads of lanes ------------------------------------------------------------------------------
 // Past the per-bucket stage every sum is a TREE (a line of the bucket matrix, the heads of a heavy bucket, a bit plane of the
 // line sums): its depth in dependent point additions is the latency, and most lanes idle anyway.  A point addition on a quad
 // of lanes (curve9_wide.cuh: 4 product levels of ~165 instructions) takes a wave ~850 instructions for 16 additions where
 // the one-lane form takes ~2700 for up to 64 -- less wave time from the third tree level up, and a third of the latency at
 // every level (a line of 256 buckets: 72 -> ~25 us).
 //
-static constexpr int kOutSliceSum = 100;      // fold9_planes: the slice's sum as XYZZ (32 words) instead of a finished commitment
-#ifndef H2_FOLD_D
-#define H2_FOLD_D 2
-#endif
 // quad q of the workgroup sums the raw points src[36 * index(k)], k = q, q + nq, ... < count.  D points are in flight: each
 // lane fetches ONE coordinate (9 words) of each and the quad exchanges them by DPP when the point's turn comes -- the strided
 // loads of a line overlap instead of each waiting behind the previous addition.  These kernels run while other streams'
@@ -139,6 +207,24 @@ template <int FB> __device__ __forceinline__ xyzz9<FB> fold9_quads_sum(xyzz9<FB>
         __syncthreads();
     }
     return acc;
+}
+// The arrival of bit plane t (fold9_planes, sub_planes): the root quad doubles its plane sum t times -- the plane's weight, applied here: the
+// planes double side by side --, its lead lane publishes it in planes9[t] and, behind a fence, draws a ticket; true in every lane of the
+// workgroup that arrives LAST of `planes` (s_last: a word of its LDS), which then reads all planes and resets the counter for the next launch.
+template <int FB>
+__device__ __forceinline__ bool fold9_plane_arrive(xyzz9<FB> acc, u32 t, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 planes, u32 &s_last) {
+    if (fold9_root()) {
+        for (u32 k = 0; k < t; ++k) acc = xyzz9_dbl_wide<FB>(acc);
+        if ((threadIdx.x & (kGroup - 1)) == 0) {
+            xyzz9_store_raw<FB>(planes9 + 36 * (size_t)t, acc);
+            __threadfence();
+            s_last = atomicAdd(counter, 1u) == planes - 1 ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    if (!s_last) return false;
+    __threadfence();
+    return true;
 }
 // The Horner step over the window slices of SEVERAL ranges of one multiexp (h2_msm's range pipeline): slice sums are linear in the
 // points, so sum_q Horner(S_q) = Horner(sum_q S_q) -- quad w adds slice w's sums over the ranges (side by side), then quad 0 runs ONE
@@ -214,15 +300,38 @@ MsmContext &msm_ctx(hipStream_t st = nullptr);          // msm_launch.hip
 // that of `to`'s (each context's mutex taken in turn, never both)
 void msm_hand_last_plan(hipStream_t from, hipStream_t to, u32 caller, u32 count, u32 cols_first = 0, u32 cols_last = 0);
 
-// Launched from more than one place (msm_launch.hip, msm_generic.hip), defined beside the kernels they launch.
-// msm_fold.hip: the carry-free fold of a contiguous GROUP of slices [slice0, slice0 + nslices) down to its slice sums -- finish (range heads into
-// their buckets), the heavy buckets, line sums, bit planes.  heads9 / starts / buckets9 / heavy / hscratch are the group's own; lines9 / planes9 /
-// ctr / out are those of slice 0 (the group's lie slice0 slices in).  tb: the group's buckets (per column); cols: columns of a batched commit --
-// grid z of every launch, except that JOINED columns (cs.joined) are finished as one list of cols x tb buckets.
-template <int FB>
-void fold9_group(hipStream_t st, const u32 *heads9, const u32 *starts, u32 *buckets9, u32 *heavy, u32 *hscratch, u32 *lines9, u32 *planes9, u32 *ctr,
-                 u32 *out, int out_kind, bool out_mont, u32 tb, u32 T, u32 lane_div, int c, u32 wideS, u32 wideNR, u32 slice0, u32 nslices, u32 cols,
-                 const ColOut &co, const ColStride &cs);
+// ---- msm_fold.hip: the host side of everything behind the accumulate.  The fold kernels are launched from there and nowhere else, so none of
+// them is declared here; `fb` is the base field (FP / FQ) whose instances a call launches.
+inline int base_field(int curve) { return curve == H2_PALLAS ? FP : FQ; }
+// The carry-free fold of a contiguous GROUP of slices [slice0, slice0 + nslices) down to its slice sums -- finish (range heads into their
+// buckets), the heavy buckets, line sums, bit planes: five launches on `st`.
+struct Fold9Group {
+    const u32 *heads9 = nullptr, *starts = nullptr;                        // the group's own areas: range heads, bucket boundaries,
+    u32 *buckets9 = nullptr, *heavy = nullptr, *hscratch = nullptr;        // bucket slots, heavy list and its scratch
+    u32 *lines9 = nullptr, *planes9 = nullptr, *ctr = nullptr;             // the areas of slice 0: the group's lie slice0 slices in
+    u32 *out = nullptr;                                                    // ... and so does its output when that is slice sums
+    int out_kind = kOutSliceSum;                                           // kOutSliceSum (32 words a slice) or a finished point per slice
+    bool out_mont = true;
+    u32 tb = 0;                                                            // the group's buckets (per column)
+    u32 T = 0, lane_div = 0;                                               // as its accumulate was launched
+    int c = 0;
+    u32 wideS = 0, wideNR = 0;                                             // the bucket matrix of a slice
+    u32 slice0 = 0, nslices = 0;
+    u32 cols = 1;                 // columns of a batched commit: grid z of every launch, except that JOINED columns (cs.joined) are finished as one list of cols x tb buckets
+    ColOut co = {};
+    ColStride cs = {};
+};
+void fold9_group(int fb, hipStream_t st, const Fold9Group &g);
+// the 8 x 32 finisher and fold of a call of msm_launch.  A range of a chunked commit stops at its finished buckets (added into add_into); the
+// fold-only call starts from buckets summed that way.
+int fold_r256(int fb, MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st);
+// msm_combine: the Horner step over `slices` slice sums (outputs > 1: slice i alone becomes output i); lds: dynamic LDS the launch asks for
+// and never touches (the grouped form's fence, msm_generic.hip), which msm_combine_allow_lds has to have raised the limit for
+void msm_combine_launch(int fb, hipStream_t st, size_t lds, u32 outputs, const u32 *slice_sums, int slices, int c, u32 *out, int out_kind, bool out_mont,
+                        int extra_dbl = 0, const u32 *addend = nullptr, bool addend_first = false);
+int msm_combine_allow_lds(size_t bytes);
+void msm_combine_ranges_launch(int fb, hipStream_t st, const RangeSums &rs, int ranges, int slices, int c, u32 *out, int out_kind, bool out_mont);
+void msm_bucket_add_launch(int fb, hipStream_t st, u32 *total, const u32 *part, u32 nb);      // total[b] += part[b], b < nb
 // msm_sort.hip: pass 2 of a two-pass sort in its one-launch form -- msm_s2_bins (a workgroup per pass-1 bin; it lists the bins beyond its LDS stage
 // in `big` and clears the raw bucket slots `zero9` when given) and, when max_big is non-zero, the chunked msm_s2_big_* kernels over that list
 void sort2_pass2_bins(hipStream_t st, const u32 *tagged, const uint16_t *tagged_low, const u32 *bin_start, const Sort2 &S2, u32 tb, size_t cap_entries,
@@ -365,11 +474,12 @@ __global__ void __launch_bounds__(512) msm_d1_count(const uint16_t *__restrict__
 __global__ void __launch_bounds__(512) msm_d1_scatter(const uint16_t *__restrict__ digits, GroupSort P, const u32 *__restrict__ hist1,
                                                       const u32 *__restrict__ bin_count, u32 *__restrict__ bin_start, u32 *__restrict__ tagged);
 
+
 // ---- kernels defined in msm_accumulate.hip -------------------------------------------------------------------------------------
 template <int FB>
 __global__ void __launch_bounds__(256) msm_bases_to_m9_glv(const u32 *__restrict__ bases, u32 *__restrict__ out, u32 n);
-extern template __global__ void msm_bases_to_m9_glv<FP>(const u32 *__restrict__ bases, u32 *__restrict__ out, u32 n);
-extern template __global__ void msm_bases_to_m9_glv<FQ>(const u32 *__restrict__ bases, u32 *__restrict__ out, u32 n);
+#define H2_INSTANCES_msm_bases_to_m9_glv(X) X(msm_bases_to_m9_glv<FP>) X(msm_bases_to_m9_glv<FQ>)
+H2_INSTANCES_msm_bases_to_m9_glv(H2_EXTERN_KERNEL)
 // BLOCK: lanes per workgroup.  256 everywhere (two workgroups per CU) except the grouped generic multiexp (msm_generic.hip), whose accumulates
 // are launched while the previous group's fold kernels hold wave slots on some CUs: with 256-lane workgroups the dispatcher then puts THREE
 // accumulate workgroups on the free CUs (168 registers allow three waves per SIMD), those run at two thirds of the speed for the whole launch
@@ -379,130 +489,14 @@ __global__ void __launch_bounds__(BLOCK, (M9 ? H2_ACC9_WAVES * 256 / BLOCK : 4))
                                                       u32 extra_index, const u32 *__restrict__ entries,
                                                       const u32 *__restrict__ starts, u32 *__restrict__ heads,
                                                       u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FP, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FP, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FQ, false, false>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FQ, false, true>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FP, false, true, 512>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void msm_accumulate<FQ, false, true, 512>(const u32 *__restrict__ bases, const u32 *__restrict__ extra_base,
-                                                      u32 extra_index, const u32 *__restrict__ entries,
-                                                      const u32 *__restrict__ starts, u32 *__restrict__ heads,
-                                                      u32 *__restrict__ buckets, u32 total_buckets, u32 T, u32 div, ColStride cs);
+#define H2_INSTANCES_msm_accumulate(X)                                                                                                    \
+    X(msm_accumulate<FP, false, false>) X(msm_accumulate<FP, false, true>) X(msm_accumulate<FQ, false, false>) X(msm_accumulate<FQ, false, true>) \
+    X(msm_accumulate<FP, false, true, 512>) X(msm_accumulate<FQ, false, true, 512>)
+H2_INSTANCES_msm_accumulate(H2_EXTERN_KERNEL)
 template <int FB>
 __global__ void __launch_bounds__(256) msm_segments_to_r256(const u32 *__restrict__ raw, u32 *__restrict__ heads,
                                                             u32 *__restrict__ buckets, u32 T, u32 total_buckets);
-extern template __global__ void msm_segments_to_r256<FP>(const u32 *__restrict__ raw, u32 *__restrict__ heads,
-                                                            u32 *__restrict__ buckets, u32 T, u32 total_buckets);
-extern template __global__ void msm_segments_to_r256<FQ>(const u32 *__restrict__ raw, u32 *__restrict__ heads,
-                                                            u32 *__restrict__ buckets, u32 T, u32 total_buckets);
-
-// ---- kernels defined in msm_fold.hip -------------------------------------------------------------------------------------------
-template <int FB>
-__global__ void __launch_bounds__(256) msm_finish_buckets(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                          u32 *__restrict__ buckets, u32 *__restrict__ heavy,
-                                                          u32 total_buckets, u32 T, u32 div);
-extern template __global__ void msm_finish_buckets<FP>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                          u32 *__restrict__ buckets, u32 *__restrict__ heavy,
-                                                          u32 total_buckets, u32 T, u32 div);
-extern template __global__ void msm_finish_buckets<FQ>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                          u32 *__restrict__ buckets, u32 *__restrict__ heavy,
-                                                          u32 total_buckets, u32 T, u32 div);
-template <int FB>
-__global__ void __launch_bounds__(256) msm_finish_heavy(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                        u32 *__restrict__ scratch, const u32 *__restrict__ heavy,
-                                                        u32 total_buckets, u32 T, u32 div);
-extern template __global__ void msm_finish_heavy<FP>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                        u32 *__restrict__ scratch, const u32 *__restrict__ heavy,
-                                                        u32 total_buckets, u32 T, u32 div);
-extern template __global__ void msm_finish_heavy<FQ>(const u32 *__restrict__ heads, const u32 *__restrict__ starts,
-                                                        u32 *__restrict__ scratch, const u32 *__restrict__ heavy,
-                                                        u32 total_buckets, u32 T, u32 div);
-template <int FB>
-__global__ void __launch_bounds__(64) msm_finish_heavy2(const u32 *__restrict__ scratch, u32 *__restrict__ buckets,
-                                                        const u32 *__restrict__ heavy);
-extern template __global__ void msm_finish_heavy2<FP>(const u32 *__restrict__ scratch, u32 *__restrict__ buckets,
-                                                        const u32 *__restrict__ heavy);
-extern template __global__ void msm_finish_heavy2<FQ>(const u32 *__restrict__ scratch, u32 *__restrict__ buckets,
-                                                        const u32 *__restrict__ heavy);
-template <int FB>
-__global__ void __launch_bounds__(256) msm_bucket_add(u32 *__restrict__ total, const u32 *__restrict__ part, u32 nb);
-extern template __global__ void msm_bucket_add<FP>(u32 *__restrict__ total, const u32 *__restrict__ part, u32 nb);
-extern template __global__ void msm_bucket_add<FQ>(u32 *__restrict__ total, const u32 *__restrict__ part, u32 nb);
-template <int FB>
-__global__ void __launch_bounds__(256) fold9_finish(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
-                                                    u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void fold9_finish<FP>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
-                                                    u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void fold9_finish<FQ>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ buckets9,
-                                                    u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template <int FB>
-__global__ void __launch_bounds__(256, 3) fold9_finish_heavy(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
-                                                          const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void fold9_finish_heavy<FP>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
-                                                          const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-extern template __global__ void fold9_finish_heavy<FQ>(const u32 *__restrict__ heads9, const u32 *__restrict__ starts, u32 *__restrict__ scratch9,
-                                                          const u32 *__restrict__ heavy, u32 total_buckets, u32 T, u32 div, ColStride cs);
-template <int FB>
-__global__ void __launch_bounds__(64, 3) fold9_finish_heavy2(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
-                                                             ColStride cs);
-extern template __global__ void fold9_finish_heavy2<FP>(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
-                                                             ColStride cs);
-extern template __global__ void fold9_finish_heavy2<FQ>(const u32 *__restrict__ scratch9, u32 *__restrict__ buckets9, const u32 *__restrict__ heavy,
-                                                             ColStride cs);
-template <int FB>
-__global__ void __launch_bounds__(256, 3) fold9_rowcol(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs);
-extern template __global__ void fold9_rowcol<FP>(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs);
-extern template __global__ void fold9_rowcol<FQ>(const u32 *__restrict__ buckets9, u32 *__restrict__ lines9, u32 S, u32 NR, ColStride cs);
-template <int FB>
-__global__ void __launch_bounds__(256, 3) fold9_planes(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
-                                                    int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs);
-extern template __global__ void fold9_planes<FP>(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
-                                                    int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs);
-extern template __global__ void fold9_planes<FQ>(const u32 *__restrict__ lines9, u32 *__restrict__ planes9, u32 *__restrict__ counter, u32 S, u32 NR,
-                                                    int cb, u32 *__restrict__ out, int out_kind, int out_mont, ColOut co, ColStride cs);
-template <int FB>
-__global__ void __launch_bounds__(256) msm_reduce_segments(const u32 *__restrict__ buckets, u32 *__restrict__ partial,
-                                                           u32 NB, u32 total_segments, int seg);
-extern template __global__ void msm_reduce_segments<FP>(const u32 *__restrict__ buckets, u32 *__restrict__ partial,
-                                                           u32 NB, u32 total_segments, int seg);
-extern template __global__ void msm_reduce_segments<FQ>(const u32 *__restrict__ buckets, u32 *__restrict__ partial,
-                                                           u32 NB, u32 total_segments, int seg);
-template <int FB>
-__global__ void __launch_bounds__(256) msm_sum_slice(const u32 *__restrict__ partial, u32 *__restrict__ out, u32 per_slice,
-                                                     u32 share);
-extern template __global__ void msm_sum_slice<FP>(const u32 *__restrict__ partial, u32 *__restrict__ out, u32 per_slice,
-                                                     u32 share);
-extern template __global__ void msm_sum_slice<FQ>(const u32 *__restrict__ partial, u32 *__restrict__ out, u32 per_slice,
-                                                     u32 share);
-template <int FB>
-__global__ void __launch_bounds__(256) msm_rowcol_sums(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR);
-extern template __global__ void msm_rowcol_sums<FP>(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR);
-extern template __global__ void msm_rowcol_sums<FQ>(const u32 *__restrict__ buckets, u32 *__restrict__ wide, u32 S, u32 NR);
-template <int FB>
-__global__ void __launch_bounds__(64) msm_combine(const u32 *__restrict__ slice_sums, int slices, int c, u32 *__restrict__ out,
-                                                  int out_kind, int out_mont, int extra_dbl = 0, const u32 *__restrict__ addend = nullptr, int addend_first = 0);
-extern template __global__ void msm_combine<FP>(const u32 *__restrict__ slice_sums, int slices, int c, u32 *__restrict__ out,
-                                                  int out_kind, int out_mont, int extra_dbl, const u32 *__restrict__ addend, int addend_first);
-extern template __global__ void msm_combine<FQ>(const u32 *__restrict__ slice_sums, int slices, int c, u32 *__restrict__ out,
-                                                  int out_kind, int out_mont, int extra_dbl, const u32 *__restrict__ addend, int addend_first);
-template <int FB>
-__global__ void __launch_bounds__(64) msm_combine_ranges(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
-extern template __global__ void msm_combine_ranges<FP>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
-extern template __global__ void msm_combine_ranges<FQ>(RangeSums rs, int ranges, int slices, int c, u32 *__restrict__ out, int out_kind, int out_mont);
+#define H2_INSTANCES_msm_segments_to_r256(X) X(msm_segments_to_r256<FP>) X(msm_segments_to_r256<FQ>)
+H2_INSTANCES_msm_segments_to_r256(H2_EXTERN_KERNEL)
 
 }  // namespace h2

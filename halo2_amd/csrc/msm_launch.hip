@@ -93,19 +93,7 @@ __global__ void k_points_sum(const u32 *__restrict__ pts, u32 count, u32 *__rest
         q.zzz = fe_mulx<FB>(q.zz, Z);
         xyzz_add<FB>(r, q);
     }
-    if (out_kind == H2_OUT_AFFINE) {
-        affine<FB> a = xyzz_to_affine<FB>(r);
-        if (!out_mont) { a.x = fe_from_mont<FB>(a.x); a.y = fe_from_mont<FB>(a.y); }
-        fe_store(out, a.x);
-        fe_store(out + 8, a.y);
-        return;
-    }
-    fe X, Y, Z;
-    xyzz_to_jacobian<FB>(r, X, Y, Z);
-    if (!out_mont) { X = fe_from_mont<FB>(X); Y = fe_from_mont<FB>(Y); Z = fe_from_mont<FB>(Z); }
-    fe_store(out, X);
-    fe_store(out + 8, Y);
-    fe_store(out + 16, Z);
+    point_out_store<FB>(out, r, out_kind, out_mont);
 }
 
 // ---- debug timeline (H2_TIMELINE=1): one-lane stamp kernels between the stages of a commit record the device wall
@@ -271,7 +259,7 @@ template <int FB> static int msm_empty(MsmContext &cx, const MsmArgs &a, hipStre
     int rc;
     if ((rc = cx.ssums.reserve(128)) != H2_OK) return rc;
     H2_HIP(hipMemsetAsync(cx.ssums.ptr, 0, 128, st));
-    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), 1, 0, (u32 *)a.d_out, a.out_kind, a.form == H2_FORM_MONTGOMERY);
+    msm_combine_launch(FB, st, 0, 1, cx.ssums.as<u32>(), 1, 0, (u32 *)a.d_out, a.out_kind, a.form == H2_FORM_MONTGOMERY);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }
@@ -401,68 +389,41 @@ template <int FB> static void accumulate(MsmContext &cx, const MsmPlan &p, const
                            cx.entries.as<u32>(), cx.starts.as<u32>(), cx.heads.as<u32>(), cx.buckets.as<u32>(), tb, T, p.lane_div, p.cs);
     }
 }
+// what the carry-free folds of a call share: the lines, planes (behind every slice's lines in cx.partial) and arrival counters, and the shape
+static Fold9Group fold9_shared(MsmContext &cx, const MsmPlan &p) {
+    Fold9Group g;
+    g.lines9 = cx.partial.as<u32>();
+    g.planes9 = g.lines9 + 36 * (size_t)p.K * p.sh.slices * (p.wideS + p.wideNR);
+    g.ctr = cx.fold_ctr.as<u32>();
+    g.T = p.T;
+    g.lane_div = p.lane_div;
+    g.c = p.sh.c;
+    g.wideS = p.wideS;
+    g.wideNR = p.wideNR;
+    g.co = p.co;
+    g.cs = p.cs;
+    return g;
+}
 // the carry-free fold: finish on the raw M9 segments, one lane per bucket; the buckets stay in cx.seg9.  Window slices (generic path) meet in
 // msm_combine's Horner step, unless the caller wants the slice sums (slice_sums_only)
 template <int FB> static void fold_carry_free(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
     const MsmShape &sh = p.sh;
     const bool mont = a.form == H2_FORM_MONTGOMERY, windows = p.glv;
-    u32 *heads9 = cx.seg9.as<u32>(), *buckets9 = heads9 + 36 * p.head_slots;
-    u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)p.K * sh.slices * (p.wideS + p.wideNR);
-    fold9_group<FB>(st, heads9, cx.starts.as<u32>(), buckets9, cx.heavy.as<u32>(), cx.hscratch.as<u32>(), lines9, planes9, cx.fold_ctr.as<u32>(),
-                    windows ? cx.ssums.as<u32>() : (u32 *)a.d_out, windows ? kOutSliceSum : a.out_kind, mont, p.tb, p.T, p.lane_div, sh.c, p.wideS, p.wideNR,
-                    0u, sh.slices, p.K, p.co, p.cs);
-    if (windows && !a.slice_sums_only)
-        hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)sh.slices, sh.c, (u32 *)a.d_out, a.out_kind, mont);
-}
-// the 8 x 32 finisher and fold.  A range of a chunked commit stops at its finished buckets (added into add_into); the fold-only call
-// starts from buckets summed that way.
-template <int FB> static int fold_r256(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
-    const MsmShape &sh = p.sh;
-    const u32 tb = p.tb, T = p.T;
-    if (!p.fold_only) {
-        hipLaunchKernelGGL((msm_finish_buckets<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, cx.heads.as<u32>(),
-                           cx.starts.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
-        hipLaunchKernelGGL((msm_finish_heavy<FB>), dim3(kHeavyBlocks, kMaxHeavy), dim3(256), (256 / kGroup) * 128, st,
-                           cx.heads.as<u32>(), cx.starts.as<u32>(), cx.hscratch.as<u32>(), cx.heavy.as<u32>(), tb, T, p.lane_div);
-        hipLaunchKernelGGL((msm_finish_heavy2<FB>), dim3(kMaxHeavy), dim3(64), 0, st, cx.hscratch.as<u32>(), cx.buckets.as<u32>(), cx.heavy.as<u32>());
-    }
-    if (p.add_only) {
-        hipLaunchKernelGGL((msm_bucket_add<FB>), dim3((tb * kGroup + 255) / 256), dim3(256), 0, st, a.add_into, cx.buckets.as<u32>(), tb);
-        return H2_OK;
-    }
-    // what the fold runs over: the bucket slices themselves, or (wide slices) the row / column sums as two slices
-    const u32 *fold_src = p.fold_only ? a.fold_from : cx.buckets.as<u32>();
-    u32 fold_nb = sh.NB, fold_slices = sh.slices;
-    int fold_c = sh.c;
-    if (p.wide_reduce) {
-        u32 *wide = cx.partial.as<u32>() + 32 * (size_t)(2 * p.wideNR / kSeg);     // after the fold's own partials
-        H2_HIP(hipMemsetAsync(wide, 0, (size_t)2 * p.wideNR * 128, st));
-        hipLaunchKernelGGL((msm_rowcol_sums<FB>), dim3(p.wideS + p.wideNR - 1), dim3(256), (256 / kGroup) * 128, st, fold_src, wide, p.wideS, p.wideNR);
-        fold_src = wide;
-        fold_nb = p.wideNR;
-        fold_slices = 2;
-        fold_c = (sh.c - 1) / 2;      // log2 S
-    }
-    // A segment is 2 seg running-sum additions + a small-scalar multiple (~23 more dependent operations) on one quad of lanes:
-    // 4 buckets while the segments fit the chip a few times over (the fold is their latency: one commit 0.235 -> 0.218 ms,
-    // small commits 5-8 %), 8 when there are many slices (generic multiexps of 2^20 points: the multiples are throughput)
-    const int seg = (size_t)fold_slices * fold_nb / kSeg <= 32768 ? kSeg : 2 * kSeg;
-    const u32 fold_segs = fold_slices * fold_nb / seg;
-    hipLaunchKernelGGL((msm_reduce_segments<FB>), dim3((fold_segs * kGroup + 255) / 256), dim3(256), 0, st, fold_src, cx.partial.as<u32>(), fold_nb, fold_segs, seg);
-    // 64 logical lanes per workgroup; first level leaves <= 32 block sums per slice
-    const u32 per_slice = fold_nb / seg, nl = 256 / kGroup;
-    const u32 bps = std::max(1u, std::min(32u, per_slice / (2 * nl)));
-    const u32 share = (per_slice + bps - 1) / bps;
-    if (bps > 1) {
-        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(bps, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(),
-                           cx.heads.as<u32>(), per_slice, share);     // heads[] is free again: reuse as level-1 output
-        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.heads.as<u32>(), cx.ssums.as<u32>(), bps, bps);
-    } else {
-        hipLaunchKernelGGL((msm_sum_slice<FB>), dim3(1, fold_slices), dim3(256), nl * 128, st, cx.partial.as<u32>(), cx.ssums.as<u32>(), per_slice, per_slice);
-    }
-    hipLaunchKernelGGL((msm_combine<FB>), dim3(p.pair ? 2 : 1), dim3(64), 0, st, cx.ssums.as<u32>(), (int)fold_slices, fold_c, (u32 *)a.d_out,
-                       a.out_kind, a.form == H2_FORM_MONTGOMERY);
-    return H2_OK;
+    Fold9Group g = fold9_shared(cx, p);
+    g.heads9 = cx.seg9.as<u32>();
+    g.starts = cx.starts.as<u32>();
+    g.buckets9 = cx.seg9.as<u32>() + 36 * p.head_slots;
+    g.heavy = cx.heavy.as<u32>();
+    g.hscratch = cx.hscratch.as<u32>();
+    g.out = windows ? cx.ssums.as<u32>() : (u32 *)a.d_out;
+    g.out_kind = windows ? kOutSliceSum : a.out_kind;
+    g.out_mont = mont;
+    g.tb = p.tb;
+    g.slice0 = 0;
+    g.nslices = sh.slices;
+    g.cols = p.K;
+    fold9_group(FB, st, g);
+    if (windows && !a.slice_sums_only) msm_combine_launch(FB, st, 0, 1, cx.ssums.as<u32>(), (int)sh.slices, sh.c, (u32 *)a.d_out, a.out_kind, mont);
 }
 // the slice split, in front of the sort: the bases' conversion (it reads nothing the sort writes) on the side stream, beside the sort
 template <int FB> static int slice_split_convert(MsmContext &cx, const MsmPlan &p, const MsmArgs &a, hipStream_t st) {
@@ -485,8 +446,16 @@ template <int FB> static int slice_split_accumulate_fold(MsmContext &cx, const M
     H2_HIP(hipMemsetAsync(heavy_a, 0, 8, st));
     H2_HIP(hipStreamWaitEvent(st, cx.ev_conv, 0));
     const u32 *pts = cx.bases9.as<u32>(), *starts = cx.starts.as<u32>();
-    u32 *lines9 = cx.partial.as<u32>(), *planes9 = lines9 + 36 * (size_t)sh.slices * (p.wideS + p.wideNR), *ssums = cx.ssums.as<u32>();
+    u32 *ssums = cx.ssums.as<u32>();
     const bool mont = a.form == H2_FORM_MONTGOMERY;
+    Fold9Group upper = fold9_shared(cx, p);      // both groups leave slice sums (kOutSliceSum) in ssums
+    upper.out = ssums;
+    upper.out_mont = mont;
+    Fold9Group lower = upper;
+    upper.heads9 = heads_a; upper.starts = starts + kb; upper.buckets9 = buckets9 + 36 * (size_t)kb; upper.heavy = heavy_a; upper.hscratch = hscr_a;
+    upper.tb = tb_a; upper.slice0 = split_k; upper.nslices = ns_a;
+    lower.heads9 = heads_b; lower.starts = starts; lower.buckets9 = buckets9; lower.heavy = heavy_b; lower.hscratch = hscr_b;
+    lower.tb = kb; lower.slice0 = 0; lower.nslices = split_k;
     // the upper slices first, then the lower ones
     hipLaunchKernelGGL((msm_accumulate<FB, false, true>), dim3(T / 256), dim3(256), 0, st, pts, (const u32 *)nullptr, 0xFFFFFFFFu, cx.entries.as<u32>(),
                        starts + kb, heads_a, buckets9 + 36 * (size_t)kb, tb_a, T, p.lane_div, p.cs);
@@ -495,17 +464,13 @@ template <int FB> static int slice_split_accumulate_fold(MsmContext &cx, const M
                        starts, heads_b, buckets9, kb, T, p.lane_div, p.cs);
     // upper group on the side stream: fold, Horner over its slices, split_k c more doublings -> one weighted point behind the slice sums
     H2_HIP(hipStreamWaitEvent(cx.side, cx.ev_acc_a, 0));
-    fold9_group<FB>(cx.side, heads_a, starts + kb, buckets9 + 36 * (size_t)kb, heavy_a, hscr_a, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
-                    tb_a, T, p.lane_div, sh.c, p.wideS, p.wideNR, split_k, ns_a, 1u, p.co, p.cs);
-    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, cx.side, (const u32 *)(ssums + 32 * (size_t)split_k), (int)ns_a, sh.c, ssums + 32 * (size_t)sh.slices,
-                       kOutSliceSum, 1, p.split_k * sh.c, (const u32 *)nullptr);
+    fold9_group(FB, cx.side, upper);
+    msm_combine_launch(FB, cx.side, 0, 1, ssums + 32 * (size_t)split_k, (int)ns_a, sh.c, ssums + 32 * (size_t)sh.slices, kOutSliceSum, true, p.split_k * sh.c);
     H2_HIP(hipEventRecord(cx.ev_join, cx.side));
     // lower group behind its accumulate, then the two halves meet
-    fold9_group<FB>(st, heads_b, starts, buckets9, heavy_b, hscr_b, lines9, planes9, cx.fold_ctr.as<u32>(), ssums, kOutSliceSum, mont,
-                    kb, T, p.lane_div, sh.c, p.wideS, p.wideNR, 0u, split_k, 1u, p.co, p.cs);
+    fold9_group(FB, st, lower);
     H2_HIP(hipStreamWaitEvent(st, cx.ev_join, 0));
-    hipLaunchKernelGGL((msm_combine<FB>), dim3(1), dim3(64), 0, st, (const u32 *)ssums, p.split_k, sh.c, (u32 *)a.d_out, a.out_kind, mont ? 1 : 0, 0,
-                       (const u32 *)(ssums + 32 * (size_t)sh.slices));
+    msm_combine_launch(FB, st, 0, 1, ssums, p.split_k, sh.c, (u32 *)a.d_out, a.out_kind, mont, 0, ssums + 32 * (size_t)sh.slices);
     return H2_OK;
 }
 // One multiexp, or one phase of it (MsmArgs::phase): 1 = the sort; 2 = accumulate + fold behind a phase-1 sort; 3 = the accumulate; 4 = the fold.
@@ -559,7 +524,7 @@ template <int FB, int FS> static int msm_launch(MsmContext &cx, const MsmArgs &a
     if (folds) {
         prof_begin(PROF_MSM_REDUCE, st);
         if (p.fold9) fold_carry_free<FB>(cx, p, a, st);
-        else if ((rc = fold_r256<FB>(cx, p, a, st)) != H2_OK) return rc;
+        else if ((rc = fold_r256(FB, cx, p, a, st)) != H2_OK) return rc;
         prof_end(PROF_MSM_REDUCE, st);
         if (!p.add_only) TL_STAMP(tl_id | 4);
     }

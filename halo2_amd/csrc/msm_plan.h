@@ -559,6 +559,72 @@ inline h2_commit_plan_t empty_summary(const MsmArgs &a, u32 kind) {
     return r;
 }
 
+// ---- the fold (msm_fold.hip, msm_subdigit.hip): the integer code that decides which line carries which weight, and the 8 x 32 fold's launch
+// geometry.  tests/native/msm_fold_check.cpp compiles this text for the CPU and tests/test_msm_fold_planes.py adds the weights up.
+#ifndef H2_HD
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define H2_HD __host__ __device__ __forceinline__
+#else
+#define H2_HD inline
+#endif
+#endif
+// the k-th (k = 0, 1, ...) non-negative integer with bit t set: bit t goes in between k's upper and lower bits
+H2_HD u32 kth_with_bit(u32 k, u32 t) { return ((k >> t) << (t + 1)) | (1u << t) | (k & ((1u << t) - 1u)); }
+// fold9_planes: sum_j (j + 1) B_j = sum_lo (lo + 1) C_lo + S sum_hi hi R_hi over the lines C_0 .. C_(S-1), R_0 .. R_(NR-1) of a slice's NR x S
+// bucket matrix (S = 2^cb; line index: lo, or S + hi).  Plane t (weight 2^t, t < cb + log2 NR) holds the columns with bit t of lo + 1 set
+// -- plane cb: lo + 1 = S alone -- and the rows with bit t - cb of hi set.
+H2_HD u32 fold9_plane_cols(u32 S, int cb, u32 t) { return (int)t < cb ? S / 2 : (int)t == cb ? 1u : 0u; }
+H2_HD u32 fold9_plane_rows(u32 NR, int cb, u32 t) { return (int)t >= cb ? NR / 2 : 0u; }
+H2_HD u32 fold9_plane_line(u32 S, int cb, u32 t, u32 k) {      // the line of the plane's k-th summand: its columns, then its rows
+    const u32 ncol = fold9_plane_cols(S, cb, t);
+    if (k < ncol) return (int)t == cb ? S - 1 : kth_with_bit(k, t) - 1u;
+    return S + kth_with_bit(k - ncol, t - (u32)cb);
+}
+inline u32 fold9_plane_count(int c) { return (u32)c - 1; }      // planes of a slice of 2^(c-1) buckets = workgroups (grid x) of fold9_planes: log2 S + log2 NR
+inline int fold9_col_bits(u32 S) {
+    int cb = 0;
+    while ((1u << cb) < S) ++cb;
+    return cb;
+}
+// sub_planes: a slice of 128 buckets (bucket b weighs b + 1) in 8 planes; plane t < 7 holds the 64 buckets with bit t of b + 1 set, plane 7
+// bucket 127 alone
+H2_HD u32 sub_plane_count(u32 t) { return t < 7 ? 64u : 1u; }
+H2_HD u32 sub_plane_bucket(u32 t, u32 k) { return t < 7 ? kth_with_bit(k, t) - 1u : 127u; }
+
+// The 8 x 32 fold behind the finished buckets (fold_r256).  Wide slices (wide_reduce) are folded through their row / column sums, laid out as
+// two slices of wideNR points that a Horner step of log2 S bits joins.  A segment is 2 seg running-sum additions + a small-scalar multiple
+// (~23 more dependent operations) on one quad of lanes: 4 buckets while the segments fit the chip a few times over (the fold is their
+// latency: one commit 0.235 -> 0.218 ms, small commits 5-8 %), 8 when there are many slices (generic multiexps of 2^20 points: the multiples
+// are throughput).  The slice tree (msm_sum_slice) has 64 quads per workgroup; its first level leaves <= 32 block sums per slice, which a
+// second level of one workgroup per slice adds; few partials take that one workgroup alone.
+static constexpr u32 kTreeLanes = 256;
+constexpr size_t r256_tree_bytes(u32 lanes) { return (size_t)lanes / 4 * 128; }      // dynamic LDS of a tree launch: one XYZZ point per quad of lanes
+struct R256Fold {
+    u32 nb, slices;     // what msm_reduce_segments runs over: `slices` slices of `nb` points
+    int c;              // the Horner step's window width
+    int seg;            // buckets per segment
+    u32 segs;           // segments in all
+    int levels;         // launches of msm_sum_slice: 1 or 2
+    struct Level {
+        u32 blocks;     // workgroups per slice = sums this level leaves per slice (the last level: 1)
+        u32 per_slice;  // points per slice it reads
+        u32 share;      // ... and per workgroup
+    } level[2];
+};
+inline R256Fold r256_fold_geometry(const MsmShape &sh, bool wide_reduce, u32 wideNR) {
+    R256Fold f;
+    f.nb = wide_reduce ? wideNR : sh.NB;
+    f.slices = wide_reduce ? 2 : sh.slices;
+    f.c = wide_reduce ? (sh.c - 1) / 2 : sh.c;      // (log2 S)
+    f.seg = (size_t)f.slices * f.nb / kSeg <= 32768 ? kSeg : 2 * kSeg;
+    f.segs = f.slices * f.nb / f.seg;
+    const u32 per_slice = f.nb / f.seg, bps = std::max(1u, std::min(32u, per_slice / (2 * (kTreeLanes / 4))));
+    f.levels = bps > 1 ? 2 : 1;
+    f.level[0] = {bps, per_slice, (per_slice + bps - 1) / bps};
+    f.level[1] = {1, bps, bps};
+    return f;
+}
+
 // ---- the grouped form of a large generic multiexp (msm_generic.hip has the description) ---------------------------------------------
 struct Group {
     u32 w0 = 0, ns = 0;     // window slices [w0, w0 + ns)

@@ -187,12 +187,10 @@ __global__ void __launch_bounds__(256, 3) fold9_finish_dense(const u32 *__restri
                                                            u32 total_buckets, u32 T, u32 div) {
     H2_LATENCY_STAGE();
     __shared__ __attribute__((aligned(16))) u32 sh[32 * 36];
-    const u32 b = blockIdx.x, base = starts[0];
-    const u32 M = starts[total_buckets] - base;
-    T = eff_lanes(M, T, div);
-    const u32 chunk = max(1u, (M + T - 1) / T);
-    const u32 h0 = (starts[b] - base + chunk - 1) / chunk, h1 = (starts[b + 1] - base + chunk - 1) / chunk;
-    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(heads9, h1 > h0 ? h1 - h0 : 0u, [h0](u32 k) { return h0 + k; });
+    const u32 b = blockIdx.x;
+    const HeadRange h = bucket_heads<true>(starts, b, total_buckets, T, div);
+    const u32 h0 = h.h0;
+    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(heads9, h.h1 > h0 ? h.h1 - h0 : 0u, [h0](u32 k) { return h0 + k; });
     acc = fold9_quads_sum<FB>(acc, sh);
     if (!fold9_root()) return;
     xyzz9_add_wide<FB>(acc, xyzz9_load_raw<FB>(buckets9 + 36 * (size_t)b));
@@ -214,21 +212,9 @@ __global__ void __launch_bounds__(256, 3) sub_planes(const u32 *__restrict__ buc
     const bool lead = (threadIdx.x & (kGroup - 1)) == 0;
     const u32 *src = buckets9 + 36 * (size_t)129 * y;
     planes9 += 36 * (size_t)8 * y;
-    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(src, t < 7 ? 64u : 1u, [t](u32 k) {
-        return t < 7 ? ((((k >> t) << (t + 1)) | (1u << t) | (k & ((1u << t) - 1u))) - 1u) : 127u;      // the k-th b with bit t of b + 1 set
-    });
+    xyzz9<FB> acc = fold9_quad_gather<FB, H2_FOLD_D>(src, sub_plane_count(t), [t](u32 k) { return sub_plane_bucket(t, k); });
     acc = fold9_quads_sum<FB>(acc, sh);
-    if (fold9_root()) {
-        for (u32 k = 0; k < t; ++k) acc = xyzz9_dbl_wide<FB>(acc);
-        if (lead) {
-            xyzz9_store_raw<FB>(planes9 + 36 * (size_t)t, acc);
-            __threadfence();
-            s_last = atomicAdd(counter + y, 1u) == 7u ? 1u : 0u;
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
+    if (!fold9_plane_arrive<FB>(acc, t, planes9, counter + y, 8u, s_last)) return;
     acc = fold9_quad_gather<FB, H2_FOLD_D>(planes9, 8u, [](u32 k) { return k; });
     acc = fold9_quads_sum<FB>(acc, sh, 8u);
     if (!fold9_root()) return;
@@ -248,20 +234,7 @@ __global__ void __launch_bounds__(256, 3) sub_planes(const u32 *__restrict__ buc
     const xyzz<FB> r = xyzz9_to_r256_wide<FB>(acc);
     if (!lead) return;
     counter[4 + (y >> 1)] = 0;
-    out += (out_kind == H2_OUT_AFFINE ? 16 : 24) * (size_t)(y >> 1);
-    if (out_kind == H2_OUT_AFFINE) {
-        affine<FB> a = xyzz_to_affine<FB>(r);
-        if (!out_mont) { a.x = fe_from_mont<FB>(a.x); a.y = fe_from_mont<FB>(a.y); }
-        fe_store(out, a.x);
-        fe_store(out + 8, a.y);
-    } else {
-        fe X, Y, Z;
-        xyzz_to_jacobian<FB>(r, X, Y, Z);
-        if (!out_mont) { X = fe_from_mont<FB>(X); Y = fe_from_mont<FB>(Y); Z = fe_from_mont<FB>(Z); }
-        fe_store(out, X);
-        fe_store(out + 8, Y);
-        fe_store(out + 16, Z);
-    }
+    point_out_store<FB>(out + point_out_words(out_kind) * (size_t)(y >> 1), r, out_kind, out_mont);
 }
 
 template <int FB, int FS>
