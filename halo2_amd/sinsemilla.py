@@ -40,7 +40,9 @@ class Bottom(ValueError):
 
 
 def generator_table():
-    """S(0) .. S(1023) as a (1024, 8) int64 CUDA tensor of Montgomery affine limbs on the current device; built on first use."""
+    """S(0) .. S(1023) as a (1024, 8) int64 CUDA tensor of Montgomery affine limbs on the current device; built on first use, on the
+    stream current then.  The build is asynchronous, so the table is cached with an event recorded behind it: a caller on another
+    stream is made to wait for that event, until the event is seen complete once and dropped (steady-state calls pay one dict look-up)."""
     import torch
     dev = fields.current_device()
     if dev.index not in _tables:
@@ -48,8 +50,16 @@ def generator_table():
         out = torch.empty((1 << K, 8), dtype=torch.int64, device=dev)
         check(lib().h2_hash_to_curve_device(PALLAS, S_PERSONALIZATION.encode(), msgs.data_ptr(), 4, 1 << K, FORM_MONTGOMERY,
                                             out.data_ptr(), _stream_ptr()), "h2_hash_to_curve_device")
-        _tables[dev.index] = out
-    return _tables[dev.index]
+        built = torch.cuda.Event()
+        built.record(torch.cuda.current_stream(dev))
+        _tables[dev.index] = (out, built)
+    out, built = _tables[dev.index]
+    if built is not None:
+        if built.query():
+            _tables[dev.index] = (out, None)
+        else:
+            torch.cuda.current_stream(dev).wait_event(built)
+    return out
 
 
 def _points_to_ints(limbs) -> list:

@@ -152,7 +152,12 @@ int h2_divide_by_vanishing_poly(int field, uint64_t *a, unsigned ext_k, const ui
 
 /* ---- device-resident variants (data already in HBM; `stream` is a hipStream_t or NULL) -------- */
 /* Same contracts as above with device pointers; asynchronous on `stream`; outputs land in device
- * memory.  Used by batched provers and by bench.py (inputs resident in HBM before timing starts). */
+ * memory.  Used by batched provers and by bench.py (inputs resident in HBM before timing starts).
+ * "Asynchronous on `stream`" is an ordering promise: everything a call enqueues runs behind what `stream` already holds and has
+ * finished before anything enqueued on `stream` afterwards runs, work on the library's own streams included; no other stream and
+ * no device-wide synchronise is needed around a call (tests/test_gpu_stream_order.py).  It is not a promise that the host never
+ * waits: the entry points that say "synchronises `stream`" do, and so does h2_divide_by_vanishing_poly_device, which stages its nt
+ * factors through a small per-stream buffer and waits for `stream` before and after that copy. */
 int h2_msm_device(int curve, const void *d_scalars, const void *d_bases_xy, size_t n, int form,
                   int out_kind, void *d_out, void *stream);
 /* Blind base: `Params::w` is a field of `Params`, fixed for its life (poly/commitment.rs:26-33, :102-103), and here a property of
@@ -379,7 +384,8 @@ int h2_transcript_cb_squeeze(void *user, uint64_t *challenge);
 /* ---- Params set-up: Lagrange basis by an FFT over curve points -------------------------------- */
 /* replaces the point FFT + 2^-k scaling + batch_normalize of Params::new
  * (halo2_proofs/src/poly/commitment.rs:77-100): out[j] = 2^-k * sum_i alpha_inv^(i*j) * g[i], affine, where
- * alpha_inv is the inverse 2^k-th root of unity of the curve's scalar field.  g and out hold 2^k points. */
+ * alpha_inv is the inverse 2^k-th root of unity of the curve's scalar field.  g and out hold 2^k points.
+ * The device variant allocates its scratch per call and synchronises `stream` before it frees it: it returns with out complete. */
 int h2_lagrange_basis(int curve, const uint64_t *g_xy, uint64_t *out_xy, unsigned k, int form);
 int h2_lagrange_basis_device(int curve, const void *d_g_xy, void *d_out_xy, unsigned k, int form, void *stream);
 
