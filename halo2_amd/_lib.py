@@ -150,6 +150,10 @@ SIGNATURES = {
                                 C.c_int, vp, vp, vp], C.c_int),
     "h2_permutation_check_device": ([C.c_int, C.POINTER(vp), C.POINTER(C.c_uint8), C.c_size_t, vp, C.c_uint, C.c_size_t, C.c_int, vp, vp, vp],
                                     C.c_int),
+    "h2_cells_assigned_check": ([C.c_uint, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t),
+                                 C.c_size_t, C.POINTER(C.c_uint32), u64p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), u64p],
+                                C.c_int),
     "h2_points_compress": ([C.c_int, u64p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8)], C.c_int),
     "h2_points_compress_device": ([C.c_int, vp, C.c_size_t, C.c_int, vp, vp], C.c_int),
     "h2_points_decompress": ([C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, u64p], C.c_int),

@@ -16,7 +16,11 @@ synthesis is the existing prover.  A key made here prints as the reference's `Pi
 
 One extension: `Region.assign_advice_column` / `assign_fixed_column` assign a whole vector of rows in one call (a 2^20-row column
 is otherwise a million Python calls) and `Region.enable_selector_rows` enables a selector on an array of offsets; they lay out
-exactly as that many single calls would."""
+exactly as that many single calls would.
+
+`synthesize(..., regions=True)` also records, per region and table, what dev::MockProver keeps of it (dev.rs:42-73, `RegionRecord`):
+the layouters bracket their assignment pass with `Assembly.enter_region` / `exit_region` where the reference's do, and a bulk
+assignment is recorded as one range, not as its cells."""
 from __future__ import annotations
 
 import hashlib
@@ -727,11 +731,34 @@ class _ColumnCells:
                     den[lo:hi] = limbs([1 if v_den is None else v_den])[0]
 
 
+class RegionRecord:
+    """dev::Region (dev.rs:42-73): what the MockProver keeps of one region.  `rows` is (first, last) over the assigned cells alone, None
+    while nothing is assigned (enabling a selector does not extend it); `enabled_selectors` maps a selector's index to the absolute rows
+    it was enabled on, in enable order; `cells` lists the assignments as ranges (column, first row, count) in call order -- a single
+    cell is a range of one, a whole vector is one range however long, a cell assigned twice is listed twice."""
+    __slots__ = ("index", "name", "columns", "rows", "enabled_selectors", "cells")
+
+    def __init__(self, index: int, name: str):
+        self.index, self.name = index, name
+        self.columns, self.rows, self.enabled_selectors, self.cells = set(), None, {}, []
+
+    def assigned(self, column: Column, row: int, count: int = 1) -> None:      # update_extent + cells.push, for `count` rows at once
+        self.columns.add(column)
+        first, last = self.rows or (row, row)
+        self.rows = (min(first, row), max(last, row + count - 1))
+        self.cells.append((column, row, count))
+
+    def __repr__(self):
+        return (f"RegionRecord({self.index}, {self.name!r}, columns={sorted(self.columns, key=lambda c: (c.kind, c.index))}, rows={self.rows}, "
+                f"enabled_selectors={self.enabled_selectors}, cells={self.cells})")
+
+
 class Assembly:
     """The `Assignment` every synthesis here runs against.  fixed=True collects fixed cells, selectors and copies (keygen.rs:46-186);
-    advice=True collects advice cells (prover.rs:145-245); both: dev.rs:296-461."""
+    advice=True collects advice cells (prover.rs:145-245); both: dev.rs:296-461.  regions=True also keeps a `RegionRecord` per
+    `enter_region` / `exit_region` bracket in `.regions` (dev.rs:314-331); what is assigned outside a bracket belongs to no region."""
 
-    def __init__(self, k: int, cs: ConstraintSystem, field: int, fixed: bool, advice: bool, instances=None):
+    def __init__(self, k: int, cs: ConstraintSystem, field: int, fixed: bool, advice: bool, instances=None, regions: bool = False):
         self.k, self.n, self.cs, self.field, self.m = k, 1 << k, cs, field, fields.MODULUS[field]
         self.usable = self.n - (cs.blinding_factors() + 1)
         self.collect_fixed, self.collect_advice = fixed, advice
@@ -740,6 +767,18 @@ class Assembly:
         self.advice = [_ColumnCells() for _ in range(cs.num_advice_columns)] if advice else None
         self.selectors = np.zeros((cs.num_selectors, self.n), dtype=bool) if fixed else None
         self.permutation = PermutationAssembly(self.n, cs.permutation_columns) if fixed else None
+        self.regions = [] if regions else None
+        self.current_region = None
+
+    def enter_region(self, name) -> None:                                     # dev.rs:314-327
+        if self.regions is not None:
+            assert self.current_region is None, "regions do not nest"
+            self.current_region = RegionRecord(len(self.regions), str(name() if callable(name) else name))
+
+    def exit_region(self) -> None:                                            # dev.rs:329-331
+        if self.regions is not None:
+            self.regions.append(self.current_region)
+            self.current_region = None
 
     def _row(self, row: int, count: int = 1) -> None:
         if row < 0 or row + count > self.usable:
@@ -754,12 +793,16 @@ class Assembly:
     def enable_selector(self, selector: Selector, row: int) -> None:
         if self.collect_fixed:
             self._row(row)
+            if self.current_region is not None:                               # dev.rs:342-350
+                self.current_region.enabled_selectors.setdefault(selector.index, []).append(row)
             self.selectors[selector.index][row] = True
 
     def enable_selector_rows(self, selector: Selector, rows: np.ndarray) -> None:
         if self.collect_fixed and rows.size:
             if int(rows.min()) < 0 or int(rows.max()) >= self.usable:
                 raise NotEnoughRowsAvailable(self.k)
+            if self.current_region is not None:
+                self.current_region.enabled_selectors.setdefault(selector.index, []).extend(rows.tolist())
             self.selectors[selector.index][rows] = True
 
     def query_instance(self, column: Column, row: int) -> Value:
@@ -774,6 +817,8 @@ class Assembly:
         if not self.collect_advice:
             return None
         self._row(row)
+        if self.current_region is not None:                                   # dev.rs:390-393
+            self.current_region.assigned(column, row)
         value = self._assigned(to)
         self.advice[column.index].put(row, value)
         return value
@@ -784,6 +829,8 @@ class Assembly:
         self._row(row)
         if column.index >= len(self.fixed):
             raise BoundsFailure()
+        if self.current_region is not None:                                   # dev.rs:422-425
+            self.current_region.assigned(column, row)
         value = self._assigned(to)
         self.fixed[column.index].put(row, value)
         return value
@@ -793,6 +840,8 @@ class Assembly:
         if (column.kind == ADVICE and not self.collect_advice) or (column.kind == FIXED and not self.collect_fixed):
             return
         self._row(row, int(num.shape[0]))
+        if self.current_region is not None:
+            self.current_region.assigned(column, row, int(num.shape[0]))
         cells[column.index].put_vector(row, num, den)
 
     def copy(self, left_column: Column, left_row: int, right_column: Column, right_row: int) -> None:
@@ -804,6 +853,8 @@ class Assembly:
     def fill_from_row(self, column: Column, from_row: int, to) -> None:       # keygen.rs:152-173
         if self.collect_fixed:
             self._row(from_row)
+            if self.current_region is not None:                               # dev.rs:462-464 assigns row by row: inside a region they are its cells
+                self.current_region.assigned(column, from_row, self.usable - from_row)
             self.fixed[column.index].fill(from_row, self.usable, self._assigned(to))
 
     def host_columns(self, cells) -> list:
@@ -1003,11 +1054,14 @@ def _table_length(default_and_assigned) -> int:                               # 
     return length
 
 
-def assign_table(cs: Assembly, table_columns: list, assignment) -> None:
+def assign_table(cs: Assembly, table_columns: list, assignment, name="") -> None:
     """`assign_table` of every layouter (single_pass.rs:150-185, v1.rs:289-326): the cells, the length check, the columns recorded in
-    `table_columns` so that no later table takes them, and the default value filled in below the table."""
+    `table_columns` so that no later table takes them, and the default value filled in below the table.  The cells are a region of
+    their own under `name` (:158-165); the fill below them is not."""
     table = Table(cs, table_columns)
+    cs.enter_region(name)
     assignment(table)
+    cs.exit_region()
     first_unused = _table_length(table.default_and_assigned)
     table_columns += list(table.default_and_assigned)
     for column, (default, _) in table.default_and_assigned.items():
@@ -1039,8 +1093,10 @@ class SingleChipLayouter:
         self.shapes.append((list(shape.columns), shape.row_count))
         for c in shape.columns:
             self.columns[c] = start + shape.row_count
+        self.cs.enter_region(name)                                            # :109-116: the assignment pass alone
         region = Region(region_index, self)
         result = assignment(region)
+        self.cs.exit_region()
         if not self.constants:                                                # :120-145
             if region.constants:
                 raise NotEnoughColumnsForConstants()
@@ -1054,7 +1110,7 @@ class SingleChipLayouter:
         return result
 
     def assign_table(self, name, assignment) -> None:                         # :150-185
-        assign_table(self.cs, self.table_columns, assignment)
+        assign_table(self.cs, self.table_columns, assignment, name)
 
     def constrain_instance(self, cell: Cell, instance: Column, row: int) -> None:      # :187-199
         self.cs.copy(cell.column, self.regions[cell.region_index] + cell.row_offset, instance, row)
@@ -1085,14 +1141,14 @@ class Circuit:
         raise NotImplementedError
 
 
-def synthesize(circuit, k: int, field: int, fixed: bool, advice: bool, instances=None):
+def synthesize(circuit, k: int, field: int, fixed: bool, advice: bool, instances=None, regions: bool = False):
     """configure + floor-plan one circuit: (constraint system, assembly, layouter).  Raises NotEnoughRowsAvailable as
-    keygen.rs:200-202 does."""
+    keygen.rs:200-202 does.  regions=True: `assembly.regions` holds a `RegionRecord` per region and table, as dev::MockProver keeps."""
     cs = ConstraintSystem(fields.MODULUS[field])
     config = circuit.configure(cs)
     if (1 << k) < cs.minimum_rows():
         raise NotEnoughRowsAvailable(k)
-    assembly = Assembly(k, cs, field, fixed, advice, instances)
+    assembly = Assembly(k, cs, field, fixed, advice, instances, regions)
     layouter = getattr(circuit, "floor_planner", SimpleFloorPlanner).synthesize(assembly, circuit, config, cs.constants)
     return cs, assembly, layouter
 

@@ -7,8 +7,11 @@
 //                                  is the tuples' lexicographic order, the packed table keys are sorted (lookup.hip's bitonic
 //                                  network) and the packed input keys binary-searched;
 //   * h2_permutation_check_device  one gather and one 256-bit compare per cell of the copy-constraint mapping (dev.rs:835-881).
-// A satisfied circuit costs the caller one read of the counts; the planes are fetched only for what failed.  Nothing here
+// A satisfied circuit costs the caller one read of the counts; the planes are fetched only for what failed.  None of the three
 // synchronises or allocates per call beyond the grow-only workspaces of its (device, stream) context.
+// A fourth check works on the regions a circuit's synthesis recorded, not on values: h2_cells_assigned_check (dev.rs:581-641), host
+// memory in and out like h2_points_sum.  ra_mark paints who assigned each cell into an owner plane, ra_check asks it about every cell
+// an enabled gate queries; the records are born on the host and the answer is read there, so this one synchronises.
 #include <algorithm>
 #include <vector>
 
@@ -221,12 +224,79 @@ __global__ void __launch_bounds__(256) mp_permutation(const u32 *const *__restri
     if (threadIdx.x == 0 && s_cnt) atomicAdd(&counts[c], s_cnt);
 }
 
+// ---- the regions' check (dev.rs:581-641): is every cell that an enabled gate queries assigned by the region that enabled it? ----------
+// ra_mark: one lane per ASSIGNED CELL, not per range.  `prefix` holds the exclusive prefix sums of the ranges' counts (n_ranges + 1
+// entries, 64-bit, from the host); lane i finds the last range r with prefix[r] <= i (ranges of no cells share a prefix value and are
+// stepped over) and claims cell i - prefix[r] of it in the owner plane: 0 = unassigned, region + 1 = owned.  A cell that another region
+// holds already is a conflict; the same region assigning a cell twice is not.
+__global__ void __launch_bounds__(256) ra_mark(const u32 *__restrict__ ranges, const unsigned long long *__restrict__ prefix, u32 n_ranges,
+                                               unsigned long long total, u32 *__restrict__ owner, unsigned log_len,
+                                               unsigned long long *__restrict__ conflicts) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    bool conflict = false;
+    if (i < total) {
+        u32 lo = 0, hi = n_ranges;                       // prefix[lo] <= i < prefix[hi]
+        while (hi - lo > 1) {
+            const u32 mid = lo + (hi - lo) / 2;
+            if (prefix[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        const u32 *r = ranges + 4 * (size_t)lo;
+        const size_t at = ((size_t)r[0] << log_len) + r[1] + (size_t)(i - prefix[lo]);
+        const u32 want = r[3] + 1, old = atomicCAS(&owner[at], 0u, want);
+        conflict = old != 0 && old != want;
+    }
+    const unsigned long long b = __ballot(conflict);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(conflicts, (unsigned long long)__popcll(b));
+}
+
+// ra_check: one (gate, selector) pair per launch, one lane per enable event of the selector, every queried cell of the gate in turn.
+// cells: (column code, rotation) pairs; a code is a plane index or 0x80000000 | instance column.  planes: n_cells planes of `words`
+// 64-bit words, cell-major; bit e of plane c: cell c of event e is not assigned.  Consecutive events are mostly consecutive rows of
+// one region, so a wave's owner reads are one or two cache lines per cell.
+__global__ void __launch_bounds__(256) ra_check(const u32 *__restrict__ event_rows, const u32 *__restrict__ event_regions, size_t n_events,
+                                                const u32 *__restrict__ cells, u32 n_cells, const u32 *__restrict__ owner, unsigned log_len,
+                                                const unsigned long long *__restrict__ instance_lens, unsigned long long *__restrict__ planes,
+                                                size_t words, unsigned long long *__restrict__ count) {
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, len = (size_t)1 << log_len;
+    const bool active = e < n_events;                    // no early return: the ballots below want the whole wave
+    const u32 row = active ? event_rows[e] : 0, want = active ? event_regions[e] + 1 : 0;
+    for (u32 c = 0; c < n_cells; ++c) {
+        const u32 code = cells[2 * c];
+        const int rotation = (int)cells[2 * c + 1];
+        bool fail = false;
+        if (active) {
+            const size_t cell_row = (size_t)((long long)row + rotation) & (len - 1);          // dev.rs:603
+            if (code & 0x80000000u) fail = cell_row >= instance_lens[code & 0x7FFFFFFFu];      // InstanceValue::Padding, dev.rs:606-619
+            else fail = owner[((size_t)code << log_len) + cell_row] != want;
+        }
+        const unsigned long long b = __ballot(fail);
+        if ((threadIdx.x & 63) == 0 && (e >> 6) < words) planes[(size_t)c * words + (e >> 6)] = b;
+        mp_count_wave(&s_cnt, b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(count, (unsigned long long)s_cnt);
+}
+
 struct MockContext {
     std::mutex mu;
     DevBuf prog, offsets, consts, ptrs, flags, vals;      // staging of the expression / permutation checks
     std::vector<u32> offs;                                // program offsets as the kernel reads them
     DevBuf sorted, pack_t, pack_i;                        // lookup check: a sorted column or sorted packed keys; packed table / input keys
+    DevBuf ra_ranges, ra_prefix, ra_owner, ra_events, ra_cells, ra_lens, ra_planes, ra_counts;      // the regions' check
+    std::vector<unsigned long long> ra_host;              // its host staging: the prefix sums going up, counts and planes coming back
     void release_all() {
+        ra_ranges.release();
+        ra_prefix.release();
+        ra_owner.release();
+        ra_events.release();
+        ra_cells.release();
+        ra_lens.release();
+        ra_planes.release();
+        ra_counts.release();
         prog.release();
         offsets.release();
         consts.release();
@@ -379,4 +449,156 @@ extern "C" int h2_permutation_check_device(int field, const void *const *d_colum
                        (unsigned long long *)d_fail_bits, (u32 *)d_counts);
     H2_HIP(hipGetLastError());
     return H2_OK;
+}
+
+namespace h2 {
+namespace {
+
+struct RegionCheckArgs {
+    unsigned log_len;
+    size_t n_planes;
+    const uint32_t *ranges;
+    size_t n_ranges;
+    const uint64_t *instance_lens;
+    size_t n_instance;
+    const uint32_t *event_rows, *event_regions;
+    const size_t *selector_offsets;
+    size_t n_selectors;
+    const uint32_t *pair_selector;
+    const size_t *pair_cell_offsets;
+    size_t n_pairs;
+    const uint32_t *cells;
+    uint64_t *counts;
+    uint32_t *records;
+    size_t max_records, *n_records;
+    uint64_t *n_conflicts;
+};
+
+// everything h2_cells_assigned_check refuses, decided before a device is looked for and before an output is written
+bool region_check_args_ok(const RegionCheckArgs &a) {
+    if (a.log_len > 30 || a.n_planes > 65535 || a.n_instance > 0x7FFFFFFFu || a.n_pairs > 0xFFFFFFFFu || !a.selector_offsets ||
+        !a.pair_cell_offsets || !a.n_records || !a.n_conflicts || (a.n_ranges && !a.ranges) || (a.n_instance && !a.instance_lens) ||
+        (a.n_pairs && (!a.pair_selector || !a.counts)) || (a.max_records && !a.records))
+        return false;
+    const size_t len = (size_t)1 << a.log_len;
+    unsigned long long total = 0;
+    for (size_t r = 0; r < a.n_ranges; ++r) {
+        const uint32_t *g = a.ranges + 4 * r;
+        if (g[0] >= a.n_planes || (unsigned long long)g[1] + g[2] > len || g[3] == 0xFFFFFFFFu) return false;
+        total += g[2];
+    }
+    if (total >> 32) return false;
+    for (size_t s = 0; s < a.n_selectors; ++s) {
+        if (a.selector_offsets[s + 1] < a.selector_offsets[s]) return false;
+    }
+    const size_t n_events = a.selector_offsets[a.n_selectors] - a.selector_offsets[0];
+    if (a.selector_offsets[0] != 0 || n_events > 0xFFFFFFFFu || (n_events && (!a.event_rows || !a.event_regions))) return false;
+    for (size_t e = 0; e < n_events; ++e) {
+        if (a.event_rows[e] >= len || a.event_regions[e] == 0xFFFFFFFFu) return false;
+    }
+    for (size_t p = 0; p < a.n_pairs; ++p) {
+        if (a.pair_cell_offsets[p + 1] < a.pair_cell_offsets[p] || a.pair_selector[p] >= a.n_selectors) return false;
+    }
+    const size_t n_cells = a.pair_cell_offsets[a.n_pairs] - a.pair_cell_offsets[0];
+    if (a.pair_cell_offsets[0] != 0 || n_cells > 0xFFFFFFFFu || (n_cells && !a.cells)) return false;
+    for (size_t c = 0; c < n_cells; ++c) {
+        const uint32_t code = a.cells[2 * c];
+        if ((code & 0x80000000u) ? (code & 0x7FFFFFFFu) >= a.n_instance : code >= a.n_planes) return false;
+    }
+    return true;
+}
+
+int region_check_run(MockContext &cx, const RegionCheckArgs &a) {
+    hipStream_t st = 0;
+    const size_t len = (size_t)1 << a.log_len, n_events = a.selector_offsets[a.n_selectors], n_cells = a.pair_cell_offsets[a.n_pairs];
+    // the planes: pair p has one plane per cell of ceil(events of its selector / 64) words, at plane_at[p]
+    std::vector<size_t> plane_at(a.n_pairs + 1, 0);
+    auto events_of = [&](size_t p) { return a.selector_offsets[a.pair_selector[p] + 1] - a.selector_offsets[a.pair_selector[p]]; };
+    auto cells_of = [&](size_t p) { return a.pair_cell_offsets[p + 1] - a.pair_cell_offsets[p]; };
+    for (size_t p = 0; p < a.n_pairs; ++p) plane_at[p + 1] = plane_at[p] + cells_of(p) * ((events_of(p) + 63) / 64);
+    int rc;
+    if ((rc = cx.ra_ranges.reserve(a.n_ranges * 16 + 16)) != H2_OK || (rc = cx.ra_prefix.reserve((a.n_ranges + 1) * 8)) != H2_OK ||
+        (rc = cx.ra_owner.reserve(a.n_planes * len * 4 + 4)) != H2_OK || (rc = cx.ra_events.reserve(n_events * 8 + 8)) != H2_OK ||
+        (rc = cx.ra_cells.reserve(n_cells * 8 + 8)) != H2_OK || (rc = cx.ra_lens.reserve(a.n_instance * 8 + 8)) != H2_OK ||
+        (rc = cx.ra_planes.reserve(plane_at[a.n_pairs] * 8 + 8)) != H2_OK || (rc = cx.ra_counts.reserve((a.n_pairs + 1) * 8)) != H2_OK)
+        return rc;
+    std::vector<unsigned long long> &host = cx.ra_host;                     // lives in the context: the copies below are asynchronous
+    host.assign(a.n_ranges + 1, 0);
+    for (size_t r = 0; r < a.n_ranges; ++r) host[r + 1] = host[r] + a.ranges[4 * r + 2];
+    const unsigned long long total = host[a.n_ranges];
+    unsigned long long *d_counts = cx.ra_counts.as<unsigned long long>(), *d_conflicts = d_counts + a.n_pairs;
+    H2_HIP(hipMemsetAsync(d_counts, 0, (a.n_pairs + 1) * 8, st));
+    if (a.n_planes) H2_HIP(hipMemsetAsync(cx.ra_owner.ptr, 0, a.n_planes * len * 4, st));
+    if (total) {
+        H2_HIP(hipMemcpyAsync(cx.ra_ranges.ptr, a.ranges, a.n_ranges * 16, hipMemcpyHostToDevice, st));
+        H2_HIP(hipMemcpyAsync(cx.ra_prefix.ptr, host.data(), (a.n_ranges + 1) * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(ra_mark, dim3(grid_of(total, 256)), dim3(256), 0, st, cx.ra_ranges.as<u32>(), cx.ra_prefix.as<unsigned long long>(),
+                           (u32)a.n_ranges, total, cx.ra_owner.as<u32>(), a.log_len, d_conflicts);
+        H2_HIP(hipGetLastError());
+    }
+    if (n_events) {
+        H2_HIP(hipMemcpyAsync(cx.ra_events.ptr, a.event_rows, n_events * 4, hipMemcpyHostToDevice, st));
+        H2_HIP(hipMemcpyAsync(cx.ra_events.as<u32>() + n_events, a.event_regions, n_events * 4, hipMemcpyHostToDevice, st));
+    }
+    if (n_cells) H2_HIP(hipMemcpyAsync(cx.ra_cells.ptr, a.cells, n_cells * 8, hipMemcpyHostToDevice, st));
+    if (a.n_instance) H2_HIP(hipMemcpyAsync(cx.ra_lens.ptr, a.instance_lens, a.n_instance * 8, hipMemcpyHostToDevice, st));
+    for (size_t p = 0; p < a.n_pairs; ++p) {
+        const size_t events = events_of(p), first = a.selector_offsets[a.pair_selector[p]];
+        if (!events || !cells_of(p)) continue;                              // a selector nobody enabled launches nothing
+        hipLaunchKernelGGL(ra_check, dim3(grid_of(events, 256)), dim3(256), 0, st, cx.ra_events.as<u32>() + first,
+                           cx.ra_events.as<u32>() + n_events + first, events, cx.ra_cells.as<u32>() + 2 * a.pair_cell_offsets[p], (u32)cells_of(p),
+                           cx.ra_owner.as<u32>(), a.log_len, cx.ra_lens.as<unsigned long long>(), cx.ra_planes.as<unsigned long long>() + plane_at[p],
+                           (events + 63) / 64, d_counts + p);
+    }
+    H2_HIP(hipGetLastError());
+    std::vector<unsigned long long> got(a.n_pairs + 1);
+    H2_HIP(hipMemcpyAsync(got.data(), d_counts, (a.n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));
+    H2_HIP(hipStreamSynchronize(st));
+    // only the planes of a pair that failed somewhere come back; the first max_records set bits in the order (pair, event, cell)
+    size_t written = 0;
+    for (size_t p = 0; p < a.n_pairs && written < a.max_records; ++p) {
+        if (!got[p]) continue;
+        const size_t nc = cells_of(p), words = (events_of(p) + 63) / 64;
+        host.resize(nc * words);
+        H2_HIP(hipMemcpyAsync(host.data(), cx.ra_planes.as<unsigned long long>() + plane_at[p], nc * words * 8, hipMemcpyDeviceToHost, st));
+        H2_HIP(hipStreamSynchronize(st));
+        for (size_t w = 0; w < words && written < a.max_records; ++w) {
+            unsigned long long any = 0;
+            for (size_t c = 0; c < nc; ++c) any |= host[c * words + w];
+            for (; any && written < a.max_records; any &= any - 1) {
+                const int bit = __builtin_ctzll(any);
+                for (size_t c = 0; c < nc && written < a.max_records; ++c) {
+                    if (!((host[c * words + w] >> bit) & 1ull)) continue;
+                    uint32_t *rec = a.records + 3 * written++;
+                    rec[0] = (uint32_t)p;
+                    rec[1] = (uint32_t)(w * 64 + bit);
+                    rec[2] = (uint32_t)c;
+                }
+            }
+        }
+    }
+    for (size_t p = 0; p < a.n_pairs; ++p) a.counts[p] = got[p];
+    *a.n_records = written;
+    *a.n_conflicts = got[a.n_pairs];
+    return H2_OK;
+}
+
+}  // namespace
+}  // namespace h2
+
+extern "C" int h2_cells_assigned_check(unsigned log_len, size_t n_planes, const uint32_t *ranges, size_t n_ranges, const uint64_t *instance_lens,
+                                       size_t n_instance, const uint32_t *event_rows, const uint32_t *event_regions, const size_t *selector_offsets,
+                                       size_t n_selectors, const uint32_t *pair_selector, const size_t *pair_cell_offsets, size_t n_pairs,
+                                       const uint32_t *cells, uint64_t *counts, uint32_t *records, size_t max_records, size_t *n_records,
+                                       uint64_t *n_conflicts) {
+    const RegionCheckArgs a{log_len, n_planes, ranges, n_ranges, instance_lens, n_instance, event_rows, event_regions, selector_offsets,
+                            n_selectors, pair_selector, pair_cell_offsets, n_pairs, cells, counts, records, max_records, n_records, n_conflicts};
+    if (!region_check_args_ok(a)) return H2_ERR_ARGS;
+    int rc = ensure_device();
+    if (rc != H2_OK) return rc;
+    MockContext &cx = g_mock_ctxs.get(0);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    rc = region_check_run(cx, a);
+    if (rc != H2_OK) (void)hipStreamSynchronize(0);      // nothing enqueued may still read the caller's arrays after the return
+    return rc;
 }

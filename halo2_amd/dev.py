@@ -20,13 +20,26 @@ Semantics (dev.rs:576-904, restated for columns that are already assigned): n = 
   -> Permutation((kind, index), row).
 * Order: gates by (gate_index, row), lookups by (lookup_index, row), permutation by (column, row).  (The reference lists a
   lookup's failures by sorted input value, dev.rs:807, and keeps a ConstraintPoisoned per run of poisoned rows; rows are the
-  stable order here.)  The lowered form has no regions and no selectors, so CellNotAssigned / InstanceCellNotAssigned and
-  FailureLocation::InRegion do not exist.
+  stable order here.)  The lowered form has no regions and no selectors: `run` knows neither CellNotAssigned nor a location.
+* Regions: `MockProver.run_circuit(k, circuit, instances, field, regions=True)` keeps the regions of the synthesis
+  (`circuit.RegionRecord`, dev.rs:42-73) and the circuit's own constraint system.  `verify` then starts, as dev.rs:581-641 does,
+  with every cell that a gate queries where one of its selectors is enabled: CellNotAssigned(gate, region, gate_offset, column,
+  offset) unless the region that enabled the selector assigned that cell, InstanceCellNotAssigned(gate, region, gate_offset, column,
+  row) for an instance cell past the values given.  These come first, in the order (gate index, position of the selector in the
+  gate's queried_selectors, enable order -- region by region, within a region as enabled --, position in the gate's queried_cells).
+  (The reference walks regions, then a HashMap of selectors: its order changes from run to run and is not copied.)  The other
+  failures follow as above, each with `location`: InRegion(region, offset) for the first region whose assigned rows contain the row
+  and whose columns meet the failure's (failure.rs:80-106), else OutsideRegion(row); gate failures carry `constraint` = (gate index,
+  gate name, index in the gate, constraint name), print as failure.rs:217-246 does, and list the cells the gate queried in
+  VirtualCell's order.  `gate_index` stays the flat polynomial index.  Without regions=True nothing of this exists: the same
+  classes, `location` and `constraint` None, the strings above.
 * `verify(max_failures=N)` returns at most N failures per kind, the first N in the order above; `failure_counts` is exact.
 
 The checks are three kernels' worth of C ABI (halo2_amd/csrc/mock_prover.hip): `h2_check_expressions_device`,
 `h2_lookup_check_device`, `h2_permutation_check_device`.  They leave bit planes and counts on the device; `verify` reads the
-counts back once (its only synchronisation) and fetches a plane only for what failed."""
+counts back once (its only synchronisation) and fetches a plane only for what failed.  The regions' check is a fourth,
+`h2_cells_assigned_check`: host records in, host records out, two kernels in between (who assigned each cell; is every queried cell
+its region's), with exact counts and the first N failures."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,15 +54,115 @@ from .evaluator import _CONST, _LINEAR, _MULADD, _POLY, _SCALE, LAGRANGE, AstLea
 from .plonk import ConstraintSystem, _Cells
 
 
+_ANY = {"advice": "Advice", "fixed": "Fixed", "instance": "Instance"}
+
+
+def _region_str(region) -> str:                                               # metadata.rs:156-160
+    return f"Region {region[0]} ('{region[1]}')"
+
+
+def _gate_str(gate) -> str:                                                   # metadata.rs:96-100
+    return f"Gate {gate[0]} ('{gate[1]}')"
+
+
+def _column_debug(column) -> str:                                             # `{:?}` of plonk::Column
+    return f"Column {{ index: {column[1]}, column_type: {_ANY[column[0]]} }}"
+
+
+def _constraint_str(constraint) -> str:                                       # metadata.rs:122-137
+    gate_index, gate_name, index, name = constraint
+    return f"Constraint {index}" + (f" ('{name}')" if name else "") + f" in gate {gate_index} ('{gate_name}')"
+
+
+@dataclass(frozen=True)
+class InRegion:
+    """FailureLocation::InRegion: region = (index, name); offset from the region's first assigned row."""
+    region: tuple
+    offset: int
+
+    def __str__(self):                                                        # failure.rs:39
+        return f"in {_region_str(self.region)} at offset {self.offset}"
+
+
+@dataclass(frozen=True)
+class OutsideRegion:
+    """FailureLocation::OutsideRegion."""
+    row: int
+
+    def __str__(self):                                                        # failure.rs:40-42
+        return f"outside any region, on row {self.row}"
+
+
+class FailureLocation:
+    """failure.rs:18-107 over `circuit.RegionRecord`s (or anything with .index, .name, .rows and .columns)."""
+    InRegion, OutsideRegion = InRegion, OutsideRegion
+
+    @staticmethod
+    def find(regions, row: int, columns):
+        """failure.rs:80-106: the first region whose rows contain `row` and whose columns meet `columns`, a set of (kind, index); a
+        region without an assigned cell never matches."""
+        columns = set(columns)
+        for r in regions:
+            if r.rows is not None and r.rows[0] <= row <= r.rows[1] and any((c.kind, c.index) in columns for c in r.columns):
+                return InRegion((r.index, r.name), row - r.rows[0])
+        return OutsideRegion(row)
+
+
+@dataclass(frozen=True)
+class CellNotAssigned:
+    """VerifyFailure::CellNotAssigned: gate = (index, name), region = (index, name), column = (kind, index).  `gate_offset` is what the
+    reference stores, the ABSOLUTE row of the selector (dev.rs:629); `offset` is the cell's row minus the region's first assigned row,
+    negative when the gate looks above it.  A region that enabled a selector and assigned nothing has no first row (the reference
+    panics on `rows.unwrap()`): its smallest enabled row stands in."""
+    gate: tuple
+    region: tuple
+    gate_offset: int
+    column: tuple
+    offset: int
+
+    def __str__(self):                                                        # failure.rs:191-203
+        return (f"{_region_str(self.region)} uses {_gate_str(self.gate)} at offset {self.gate_offset}, which requires cell in column "
+                f"{_column_debug(self.column)} at offset {self.offset} to be assigned.")
+
+
+@dataclass(frozen=True)
+class InstanceCellNotAssigned:
+    """VerifyFailure::InstanceCellNotAssigned: as CellNotAssigned; `row` is the absolute row of the instance cell."""
+    gate: tuple
+    region: tuple
+    gate_offset: int
+    column: tuple
+    row: int
+
+    def __str__(self):                                                        # failure.rs:204-216
+        return (f"{_region_str(self.region)} uses {_gate_str(self.gate)} at offset {self.gate_offset}, which requires cell in instance "
+                f"column {_column_debug(self.column)} at row {self.row} to be assigned.")
+
+
+def _format_value(v) -> str:
+    """util.rs:58-73.  A failure does not carry its field: -1 is p - 1 of either Pasta field (q - 1 is no element of Fp, and p - 1 as a
+    value of Fq is as likely as any other 255-bit number)."""
+    if v is None:
+        return "poison"
+    return "0" if v == 0 else "1" if v == 1 else "-1" if v + 1 in fields.MODULUS.values() else hex(v)
+
+
 @dataclass(frozen=True)
 class ConstraintNotSatisfied:
     """VerifyFailure::ConstraintNotSatisfied.  cell_values: ((kind, column, rotation, canonical value), ...) for every cell the gate
-    queries (util::cell_values); the value of a poisoned cell (it met a zero factor) is None."""
+    queries (util::cell_values); the value of a poisoned cell (it met a zero factor) is None.  From a prover that kept its regions:
+    location (InRegion / OutsideRegion) and constraint = (gate index, gate name, index within the gate, constraint name);
+    `gate_index` stays the flat index of the polynomial."""
     gate_index: int
     row: int
     cell_values: tuple
+    location: object = None
+    constraint: tuple = None
 
     def __str__(self):
+        if self.location is not None:                                         # failure.rs:217-227
+            cells = "".join(f"- Column('{_ANY[kind]}', {col})@{rot} = {_format_value(v)}\n" for kind, col, rot, v in self.cell_values)
+            return f"{_constraint_str(self.constraint)} is not satisfied {self.location}\n" + cells
         cells = ", ".join(f"{kind}[{col}]@{rot:+d} = " + ("poison" if v is None else hex(v)) for kind, col, rot, v in self.cell_values)
         return f"Constraint {self.gate_index} is not satisfied on row {self.row}: {cells}"
 
@@ -60,8 +173,11 @@ class ConstraintPoisoned:
     gate_index: int
     rows: int
     first_row: int
+    constraint: tuple = None
 
     def __str__(self):
+        if self.constraint is not None:                                       # failure.rs:228-234
+            return f"{_constraint_str(self.constraint)} is active on an unusable row - missing selector?"
         return (f"Constraint {self.gate_index} is active on an unusable row ({self.rows} row(s), first {self.first_row}): "
                 "missing selector?")
 
@@ -71,8 +187,11 @@ class Lookup:
     """VerifyFailure::Lookup: the input tuple of `row` is not in the table."""
     lookup_index: int
     row: int
+    location: object = None
 
     def __str__(self):
+        if self.location is not None:                                         # failure.rs:235-238
+            return f"Lookup {self.lookup_index} is not satisfied {self.location}"
         return f"Lookup {self.lookup_index} is not satisfied on row {self.row}"
 
 
@@ -81,12 +200,17 @@ class Permutation:
     """VerifyFailure::Permutation: the cell of permutation column `column` = (kind, index) at `row` differs from its copy."""
     column: tuple
     row: int
+    location: object = None
 
     def __str__(self):
+        if self.location is not None:                                         # failure.rs:239-245; `{:?}` of metadata::Column
+            return (f"Equality constraint not satisfied by cell (Column {{ column_type: {_ANY[self.column[0]]}, index: {self.column[1]} }}, "
+                    f"{self.location})")
         return f"Equality constraint not satisfied by cell ({self.column[0]}[{self.column[1]}], row {self.row})"
 
 
 KINDS = ("ConstraintNotSatisfied", "ConstraintPoisoned", "Lookup", "Permutation")
+REGION_KINDS = ("CellNotAssigned", "InstanceCellNotAssigned")
 
 
 class _RecordingCells:
@@ -174,6 +298,30 @@ def _length(col) -> int:
     return int(col.shape[0]) if hasattr(col, "shape") else len(col)
 
 
+def cells_assigned_check(k: int, n_planes: int, ranges, instance_lens, event_rows, event_regions, selector_offsets, pair_selector, pair_cells,
+                         max_records: int):
+    """h2_cells_assigned_check on host arrays.  ranges: (n, 4) of (plane, first row, count, region); the events grouped by selector
+    with their CSR offsets; pair_cells: per pair the (column code, rotation) list.  -> (counts: uint64 per pair, records: (m, 3) uint32
+    of (pair, event within its selector, cell within its pair), number of conflicting assignments)."""
+    u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None
+    ranges, rows, owners, selectors = u32(ranges).reshape(-1, 4), u32(event_rows), u32(event_regions), u32(pair_selector)
+    lens = np.ascontiguousarray(instance_lens, dtype=np.uint64)
+    offsets = np.ascontiguousarray(selector_offsets, dtype=np.uintp)
+    cell_offsets = np.concatenate([[0], np.cumsum([len(cells) for cells in pair_cells])]).astype(np.uintp)
+    flat = [(code, rot & 0xFFFFFFFF) for cells in pair_cells for code, rot in cells]
+    cells = np.array(flat, dtype=np.uint32).reshape(-1, 2)
+    counts = np.zeros(len(selectors), dtype=np.uint64)
+    records = np.zeros((max_records, 3), dtype=np.uint32)
+    n_records, conflicts = C.c_size_t(0), C.c_uint64(0)
+    sizes = lambda a: a.ctypes.data_as(C.POINTER(C.c_size_t))
+    check(lib().h2_cells_assigned_check(k, n_planes, p32(ranges), len(ranges), _p(lens) if lens.size else None, len(lens), p32(rows), p32(owners),
+                                        sizes(offsets), len(offsets) - 1, p32(selectors), sizes(cell_offsets), len(selectors), p32(cells),
+                                        _p(counts) if counts.size else None, p32(records), max_records, C.byref(n_records), C.byref(conflicts)),
+          "h2_cells_assigned_check")
+    return counts, records[:n_records.value], int(conflicts.value)
+
+
 class MockProver:
     def __init__(self):
         raise TypeError("use MockProver.run(...)")
@@ -237,18 +385,118 @@ class MockProver:
         self._gates, self._lookups = compile_programs(cs, k, field, self._ev)
         self._gate_cells = [queried_cells(g) for g in cs.gates]
         self._counts = None
+        self.regions = self.circuit_cs = self.instance_lens = None
         return self
 
     @classmethod
-    def run_circuit(cls, k: int, circuit, instances, field: int, device=None) -> "MockProver":
+    def run_circuit(cls, k: int, circuit, instances, field: int, device=None, regions: bool = False) -> "MockProver":
         """dev.rs:463-574 from a `halo2_amd.circuit.Circuit`: configure, synthesize with the witness (the circuit's floor planner), invert the
-        assigned cells' denominators, compress the selectors, lower, `run`.  instances: the instance columns, integer lists."""
+        assigned cells' denominators, compress the selectors, lower, `run`.  instances: the instance columns, integer lists.
+        regions=True keeps what the reference's prover keeps beside the columns -- the regions synthesis went through (`.regions`,
+        `circuit.RegionRecord`s), the circuit's own constraint system with its gates' names, selectors and queried cells
+        (`.circuit_cs`) and the instance columns' lengths -- and `verify` then reports unassigned cells and where each failure lies."""
         from . import circuit as front
         instances = [list(col) for col in instances]
-        cs, assembly, _ = front.synthesize(circuit, k, field, fixed=True, advice=True, instances=instances)
+        cs, assembly, _ = front.synthesize(circuit, k, field, fixed=True, advice=True, instances=instances, regions=regions)
         fixed = front.fixed_columns_of(assembly, cs, device)
         advice = assembly.columns_to_field(assembly.advice, device)
-        return cls.run(k, front.lower(cs), fixed, advice, instances, assembly.permutation.flat(), field, device)
+        self = cls.run(k, front.lower(cs), fixed, advice, instances, assembly.permutation.flat(), field, device)
+        if regions:
+            self.regions, self.circuit_cs, self.instance_lens = assembly.regions, cs, [len(col) for col in instances]
+            self._flat_polys = [(g, p) for g, gate in enumerate(cs.gates) for p in range(len(gate.polys))]
+        return self
+
+    # ---- the regions' check (dev.rs:581-641) ------------------------------------------------------------------------------------------
+    def region_check_inputs(self):
+        """The arrays of h2_cells_assigned_check from the kept regions, in two parts: the cells of fixed and advice columns
+        (CellNotAssigned) and the cells of instance columns (InstanceCellNotAssigned), so that each kind has its own cap.
+        -> (ranges, events, parts); ranges: (n_ranges, 4) uint32; events: (rows, regions, selector offsets), region-major within a
+        selector; parts: two lists of (gate index, position of the selector among the gate's queried_selectors, selector index,
+        [(position in queried_cells, column code, rotation)]), in the order (gate, selector position)."""
+        n_fixed = len(self.fixed)
+        plane = lambda column: column.index + (n_fixed if column.kind == "advice" else 0)
+        ranges = np.array([(plane(column), first, count, r.index) for r in self.regions for column, first, count in r.cells],
+                          dtype=np.uint32).reshape(-1, 4)
+        rows, owners, offsets = [], [], [0]
+        for s in range(self.circuit_cs.num_selectors):
+            for r in self.regions:
+                at = r.enabled_selectors.get(s)
+                if at:
+                    rows += at
+                    owners += [r.index] * len(at)
+            offsets.append(len(rows))
+        parts = ([], [])
+        for g, gate in enumerate(self.circuit_cs.gates):
+            plain = [(i, plane(c), rot) for i, (c, rot) in enumerate(gate.queried_cells) if c.kind != "instance"]
+            inst = [(i, 0x80000000 | c.index, rot) for i, (c, rot) in enumerate(gate.queried_cells) if c.kind == "instance"]
+            for position, selector in enumerate(dict.fromkeys(s.index for s in gate.queried_selectors)):
+                for part, cells in zip(parts, (plain, inst)):
+                    if cells:
+                        part.append((g, position, selector, cells))
+        return ranges, (np.array(rows, dtype=np.uint32), np.array(owners, dtype=np.uint32), np.array(offsets, dtype=np.uintp)), parts
+
+    def _check_regions(self, max_failures: int):
+        """-> (failures, count of CellNotAssigned, count of InstanceCellNotAssigned): the first `max_failures` of each kind, merged into
+        the order (gate, selector position, enable order, position in queried_cells)."""
+        ranges, (rows, owners, offsets), parts = self.region_check_inputs()
+        n_planes, n_selectors = len(self.fixed) + len(self.advice), self.circuit_cs.num_selectors
+        starts = [r.rows[0] if r.rows is not None else min((min(at) for at in r.enabled_selectors.values() if at), default=0)
+                  for r in self.regions]
+        names = [r.name for r in self.regions]
+        lens = np.array(self.instance_lens, dtype=np.uint64)
+        found, totals = [], []
+        for kind, pairs in enumerate(parts):
+            if not pairs:
+                totals.append(0)
+                continue
+            mine = ranges if kind == 0 else ranges[:0]                        # instance cells are in no owner plane
+            counts, records, conflicts = cells_assigned_check(self.k, n_planes, mine, lens, rows, owners, offsets,
+                                                              [s for _, _, s, _ in pairs],
+                                                              [[(code, rot) for _, code, rot in cells] for _, _, _, cells in pairs], max_failures)
+            if conflicts:
+                raise ValueError(f"{conflicts} cell(s) are assigned by two regions: no floor planner lays regions over each other")
+            totals.append(int(counts.sum()))
+            for p, e, c in records.tolist():
+                g, selector_position, selector, cells = pairs[p]
+                position, code, rot = cells[c]
+                row, region = int(rows[offsets[selector] + e]), int(owners[offsets[selector] + e])
+                gate = self.circuit_cs.gates[g]
+                column = gate.queried_cells[position][0]
+                cell_row = (row + rot) % self.n
+                where = ((g, gate.name), (region, names[region]), row, (column.kind, column.index))
+                failure = InstanceCellNotAssigned(*where, cell_row) if kind else CellNotAssigned(*where, cell_row - starts[region])
+                found.append(((g, selector_position, e, position), failure))
+        found.sort(key=lambda kf: kf[0])
+        return [f for _, f in found], totals[0], totals[1]
+
+    def _polynomial_columns(self, expressions) -> set:
+        """failure.rs:48-77: the (kind, index) of every column the expressions query."""
+        leaf = lambda kind: lambda q: {(kind, q[1])}
+        none, union = lambda _: set(), lambda a, b: a | b
+        out = set()
+        for e in expressions:
+            out |= e.evaluate(none, none, leaf("fixed"), leaf("advice"), leaf("instance"), lambda a: a, union, union, lambda a, _: a)
+        return out
+
+    def _locate(self, failure):
+        """The failure with its FailureLocation and, for a gate, its constraint's names (dev.rs:670-703, :819-827, :870-877)."""
+        cs = self.circuit_cs
+        if isinstance(failure, (ConstraintNotSatisfied, ConstraintPoisoned)):
+            g, p = self._flat_polys[failure.gate_index]
+            gate = cs.gates[g]
+            constraint = (g, gate.name, p, gate.constraint_names[p])
+            if isinstance(failure, ConstraintPoisoned):
+                return ConstraintPoisoned(failure.gate_index, failure.rows, failure.first_row, constraint)
+            location = FailureLocation.find(self.regions, failure.row, self._polynomial_columns([gate.polys[p]]))
+            # util::cell_values: the cells the gate queried (the combined selector's column is not one), in VirtualCell's order
+            queried = {(c.kind, c.index, rot) for c, rot in gate.queried_cells}
+            order = {"instance": 0, "advice": 1, "fixed": 2}
+            values = tuple(sorted((cv for cv in failure.cell_values if cv[:3] in queried), key=lambda cv: (order[cv[0]], cv[1], cv[2])))
+            return ConstraintNotSatisfied(failure.gate_index, failure.row, values, location, constraint)
+        if isinstance(failure, Lookup):
+            columns = self._polynomial_columns(cs.lookups[failure.lookup_index][0])
+            return Lookup(failure.lookup_index, failure.row, FailureLocation.find(self.regions, failure.row, columns))
+        return Permutation(failure.column, failure.row, FailureLocation.find(self.regions, failure.row, {tuple(failure.column)}))
 
     # ---- the three device checks: enqueue only ---------------------------------------------------------------------------------------
     def _check_expressions(self, linked, n_programs: int, store: bool):
@@ -345,11 +593,15 @@ class MockProver:
                 rows = _set_rows(perm[0][col], left)
                 left -= len(rows)
                 failures += [Permutation(tuple(self.cs.permutation_columns[col]), r) for r in rows]
+        if self.regions is not None:                                          # dev.rs:883-888: the unassigned cells come first
+            unassigned, n_cells, n_instance = self._check_regions(max_failures)
+            self._counts = {"CellNotAssigned": n_cells, "InstanceCellNotAssigned": n_instance, **self._counts}
+            failures = unassigned + [self._locate(f) for f in failures]
         return failures
 
     @property
     def failure_counts(self) -> dict:
-        """Exact number of failures per kind (KINDS), whatever cap `verify` was given."""
+        """Exact number of failures per kind (KINDS; with regions kept also REGION_KINDS), whatever cap `verify` was given."""
         if self._counts is None:
             self.verify(0)
         return dict(self._counts)

@@ -148,12 +148,14 @@ class AssignmentPass:
             raise Synthesis(f"the assignment pass asks for region {self.region_index}; the measurement pass saw {len(self.regions)}")
         region = Region(self.region_index, self)
         self.region_index += 1
+        self.cs.enter_region(name)                                            # v1.rs:278-287
         result = assignment(region)
+        self.cs.exit_region()
         self.constants += region.constants
         return result
 
     def assign_table(self, name, assignment) -> None:
-        assign_table(self.cs, self.table_columns, assignment)
+        assign_table(self.cs, self.table_columns, assignment, name)
 
     def constrain_instance(self, cell: Cell, instance: Column, row: int) -> None:
         self.cs.copy(cell.column, self.regions[cell.region_index] + cell.row_offset, instance, row)

@@ -511,6 +511,31 @@ int h2_lookup_check_device(int field, const void *const *d_inputs, const void *c
 int h2_permutation_check_device(int field, const void *const *d_columns, const uint8_t *column_is_advice, size_t n_columns,
                                 const void *d_mapping, unsigned log_len, size_t usable_rows, int form, void *d_fail_bits, void *d_counts,
                                 void *stream);
+/* Are the cells that enabled gates query assigned by the region that enabled them (dev.rs:581-641: CellNotAssigned and
+ * InstanceCellNotAssigned)?  Host memory in, host memory out, synchronous, like h2_points_sum: the records come from a circuit's
+ * synthesis on the host and the answer is read there.  2^log_len rows; a plane is a fixed or advice column, n_planes of them.
+ *   ranges: n_ranges x (plane, first row, count, region): region `region` assigned `count` cells of the plane from `first row` on
+ *   instance_lens: the number of values given for each of the n_instance instance columns; a cell past them is Padding
+ *   event_rows / event_regions: every enabling of a selector, (absolute row, region), grouped by selector: those of selector s are
+ *     [selector_offsets[s], selector_offsets[s + 1]); n_selectors + 1 offsets from 0
+ *   pair_selector / pair_cell_offsets: n_pairs (gate, selector the gate queries) pairs; pair p checks, at every event of selector
+ *     pair_selector[p], the cells [pair_cell_offsets[p], pair_cell_offsets[p + 1]) of `cells`; n_pairs + 1 offsets from 0
+ *   cells: x (column code, rotation as int32); a column code is a plane index or 0x80000000 | instance column.  The cell of an
+ *     event in row r lies in row (r + rotation) mod 2^log_len; a plane cell fails unless the event's region assigned it, an
+ *     instance cell fails when its row is >= instance_lens[column]
+ *   counts: n_pairs exact numbers of failing cells
+ *   records: the first max_records failures in the order (pair, event, cell) as (pair, event index within its selector, cell index
+ *     within its pair); *n_records of them are written
+ *   n_conflicts: assignments that found their cell held by another region (no floor planner lets two regions share a cell; the
+ *     answer means what the reference's means only when this is 0)
+ * H2_ERR_ARGS, with every output untouched: a null pointer for an array that is not empty or for n_records / n_conflicts /
+ * the offsets, log_len > 30, a range past 2^log_len, a plane >= n_planes, an event row >= 2^log_len, offsets that decrease or do
+ * not start at 0, a selector, instance column or plane out of range, a total of range cells >= 2^32. */
+int h2_cells_assigned_check(unsigned log_len, size_t n_planes, const uint32_t *ranges, size_t n_ranges, const uint64_t *instance_lens,
+                            size_t n_instance, const uint32_t *event_rows, const uint32_t *event_regions, const size_t *selector_offsets,
+                            size_t n_selectors, const uint32_t *pair_selector, const size_t *pair_cell_offsets, size_t n_pairs,
+                            const uint32_t *cells, uint64_t *counts, uint32_t *records, size_t max_records, size_t *n_records,
+                            uint64_t *n_conflicts);
 
 /* ---- compressed points: the URS file and proof encoding --------------------------------------- */
 /* pasta_curves `to_bytes` as Params::write uses it (halo2_proofs/src/poly/commitment.rs:169-181) and write_point
