@@ -12,7 +12,8 @@
 //     below 2^29 ("normalised": limbs 0..7 in [0, 2^29), limb 8 signed) and the other below 2^31.8;
 //   * |value| < 2^258 for both operands.  Then the product is normalised and lies in (-2^255, 2^255 + p): R9 / p = 2^7, so
 //     there is never a conditional subtraction and sums / differences of a few products are again valid operands.
-// fe9_norm is the carry pass (3 ops per limb) that turns any value with limbs below 2^31 into a normalised one.
+// fe9_norm is the carry pass (3 ops per limb) that turns any value with limbs below 2^31 into a normalised one -- as long as every limb
+// PLUS the carry that reaches it (at most 3 up, 4 down) still fits an int32: |limb| <= 2^31 - 5 is enough.
 //
 // Memory formats never change: a field element in HBM is 8 x u32.  fe9_unpack / fe9_pack convert at load / store.
 // "M9 form" of x is x * 2^261 mod p; the reference's Montgomery form is x * 2^256 mod p (fe9_from_r256 / fe9_to_r256).

@@ -21,7 +21,8 @@
 // batched-affine bucket additions would start to pay: it does not -- DESIGN.md section 4.3.)
 //
 // Plain integer code, __host__ __device__: tests/native/modinv_check.cpp runs the very same functions on the CPU against big-integer
-// inverses (no GPU needed); on the device they are checked through every affine output of the parity suite.
+// inverses (no GPU needed), tests/native/modinv_edge_check.cpp under the sanitizers on 2^k, 2^k +- 1 and p - 2^k for every k; on the device they
+// are checked on the same list (tests/test_gpu_field_edges.py) and through every affine output of the parity suite.
 #pragma once
 #include <stdint.h>
 

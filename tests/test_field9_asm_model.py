@@ -11,6 +11,8 @@ import re
 
 import pytest
 
+from field_edge_cases import DOT2_EXTREME, _limbs_of, _operand, _value, ntt_regime_trials, point_formula_trials, twiddle_limbs  # noqa: F401
+
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "halo2_amd", "csrc")
 P = {0: 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
      1: 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001}
@@ -92,34 +94,6 @@ def _run(ins, operands, field):
     return [_s32(reg[f"%[r{i}]"]) for i in range(9)], peak
 
 
-def _value(limbs):
-    return sum(x << (29 * i) for i, x in enumerate(limbs))
-
-
-def _limbs_of(value, rng, spread):
-    """A signed 9-limb representation of `value` (limbs 0..7 within +-2^spread around their canonical digits)."""
-    out, carry = [], 0
-    for i in range(8):
-        digit = ((value >> (29 * i)) & M29) + carry
-        wobble = rng.randrange(-(1 << spread) // (1 << 29), (1 << spread) // (1 << 29) + 1) if spread > 29 else 0
-        out.append(digit - (wobble << 29))
-        carry = wobble
-    out.append((value >> 232) + carry)
-    assert _value(out) == value
-    return out
-
-
-def _operand(rng, p, kind):
-    if kind == "normalised":                   # what a product leaves: value in (-2^255, 2^255 + p), limbs 0..7 in [0, 2^29)
-        return _limbs_of(rng.randrange(-(1 << 255), (1 << 255) + p), rng, 29)
-    if kind == "difference":                   # normalised - normalised: limbs in (-2^29, 2^29), |value| < 2^257
-        a, b = _operand(rng, p, "normalised"), _operand(rng, p, "normalised")
-        return [x - y for x, y in zip(a, b)]
-    if kind == "wide":                         # limbs up to 2^30 in magnitude, |value| < 2^258
-        return _limbs_of(rng.randrange(-(1 << 258) + 1, 1 << 258), rng, 30)
-    raise ValueError(kind)
-
-
 def _check_result(r, want_mod_p, p, value_bound):
     assert all(0 <= x < (1 << 29) for x in r[1:8]) and 1 <= r[0] <= (1 << 29), r       # limb 0: the pending +1 lands here
     v = _value(r)
@@ -131,32 +105,29 @@ def _check_result(r, want_mod_p, p, value_bound):
 def test_generated_multipliers_against_big_integers(field):
     p = P[field]
     rinv = pow(1 << 261, -1, p)
-    rng = random.Random(0x9E37 + field)
     mul, sqr = _statement("field9_mul.inc"), _statement("field9_sqr.inc")
     dot2, sqr_minus = _statement("field9_dot2.inc"), _statement("field9_sqr_minus.inc")
     assert sum(i.startswith("v_mad") for i in mul) == 126 and sum(i.startswith("v_mad") for i in dot2) == 207
-    for trial in range(60):
-        kinds = ("normalised", "difference", "wide") if trial % 3 else ("normalised", "normalised", "normalised")
-        a, b = _operand(rng, p, kinds[trial % 2]), _operand(rng, p, "normalised")
-        if trial == 7:
-            a[0] = 1 << 29                      # the limb value only a product's limb 0 takes
+    trials = point_formula_trials(field)                           # the operands the device runs too (tests/field_edge_cases.py)
+    assert len(trials) == 60 and trials[7]["a"][0] == 1 << 29      # the limb value only a product's limb 0 takes
+    for t in trials:
+        a, b, d = t["a"], t["b"], t["d"]
         r, _ = _run(mul, {"a": a, "b": b}, field)
         _check_result(r, _value(a) * _value(b) * rinv, p, (1 << 255) + p + 1)
-        d = _operand(rng, p, "difference")
         r, _ = _run(sqr, {"a": d}, field)
         _check_result(r, _value(d) ** 2 * rinv, p, (1 << 255) + p + 1)
         # Y3 = R (Q - X3) + (-Y1) PPP: difference x difference + normalised x normalised (curve9.cuh)
-        c, e = _operand(rng, p, "difference"), _operand(rng, p, "normalised")
-        f = [-x for x in _operand(rng, p, "normalised")]
+        c, e, f = t["c"], t["e"], t["f"]
         r, peak = _run(dot2, {"a": d, "b": c, "c": f, "d": e}, field)
         _check_result(r, (_value(d) * _value(c) + _value(f) * _value(e)) * rinv, p, 1 << 256)
         assert peak < 1 << 63
         # X3 = R^2 - (PPP + 2 Q): the subtrahend's limbs reach 3 * 2^29
-        s = [x + 2 * y for x, y in zip(_operand(rng, p, "normalised"), _operand(rng, p, "normalised"))]
+        s = t["s"]
         r, _ = _run(sqr_minus, {"a": d, "s": s}, field)
         _check_result(r, _value(d) ** 2 * rinv - _value(s), p, 1 << 258)
     # extreme limbs: every limb of every operand at +-2^29 (the column bound of fe9_dot2: 18 + 5 terms below 2^58)
-    top = [(1 << 29)] * 8 + [1 << 24]
+    top = DOT2_EXTREME
+    assert top == [(1 << 29)] * 8 + [1 << 24]
     neg = [-x for x in top]
     r, peak = _run(dot2, {"a": top, "b": top, "c": neg, "d": neg}, field)
     assert peak < 1 << 63 and _value(r) % p == (2 * _value(top) ** 2 * rinv) % p
@@ -171,24 +142,15 @@ def test_ntt_operand_regime_of_the_multiplier(field):
     is small again (below 2^255 + p: what the next rounds add to an element), also at the corners of the limb range."""
     p = P[field]
     rinv = pow(1 << 261, -1, p)
-    rng = random.Random(0x4E5454 + field)
     mul = _statement("field9_mul.inc")
     lo, hi = -(1 << 30) + 1, 3 * (1 << 29) - 1
-
-    def twiddle(v):
-        return [(v >> (29 * i)) & M29 for i in range(8)] + [v >> 232]
-
+    trials = ntt_regime_trials(field)                              # the operands the device runs too (tests/field_edge_cases.py)
+    assert len(trials) == 80 and trials[0][0] == [hi] * 8 + [1 << 29] and trials[1][0] == [lo] * 8 + [-(1 << 29)]
+    assert [w for _, w in trials[:4]] == [p - 1 - i for i in range(4)]
     worst = 0
-    for trial in range(80):
-        a = [rng.randrange(lo, hi + 1) for _ in range(8)] + [rng.randrange(-(1 << 29), (1 << 29) + 1)]
-        if trial == 0:
-            a = [hi] * 8 + [1 << 29]                   # every limb at the top of the RAW range
-        elif trial == 1:
-            a = [lo] * 8 + [-(1 << 29)]                # ... at the bottom
-        elif trial == 2:
-            a = [hi if i % 2 else lo for i in range(8)] + [1 << 29]
-        w = p - 1 - trial if trial < 4 else rng.randrange(0, p)
-        b = twiddle(w)
+    for trial, (a, w) in enumerate(trials):
+        assert all(lo <= x <= hi for x in a[:8]) and abs(a[8]) <= 1 << 29 and 0 <= w < p
+        b = twiddle_limbs(w)
         assert _value(b) == w and all(0 <= x < (1 << 29) for x in b[:8])
         r, peak = _run(mul, {"a": a, "b": b}, field)
         worst = max(worst, peak)

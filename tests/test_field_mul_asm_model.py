@@ -6,10 +6,11 @@ vcc.  The product is congruent to a b 2^-256 and stays below 2p for canonical op
 a carry written to an SGPR by a VALU instruction is read no sooner than three instructions later (hipcc pads its own code, not asm text).
 The device checks the same statement against the C oracle (tests/native/field_check.hip); this needs no GPU."""
 import os
-import random
 import re
 
 import pytest
+
+from field_edge_cases import LAZY_D, mul_model_edges, mul_model_pairs
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "halo2_amd", "csrc")
 P = {0: 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
@@ -69,17 +70,18 @@ def test_generated_8x32_multiplier_against_big_integers(field):
     ins = _instructions()
     assert sum(op == "v_mad_u64_u32" for op, _ in ins) == 96
     rinv = pow(1 << 256, -1, p)
-    rng = random.Random(0x8832 + field)
-    edge = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (1 << 254), (1 << 254) - 1, (1 << 255) - 1 if (1 << 255) - 1 < p else p - 3]
-    pairs = [(x, y) for x in edge for y in edge] + [(rng.randrange(p), rng.randrange(p)) for _ in range(300)]
+    pairs, lazy = mul_model_pairs(field)                           # the operands the device runs too (tests/field_edge_cases.py)
+    edge = mul_model_edges(field)
+    assert {0, 1, 2, p - 1, p - 2, (p - 1) // 2, 1 << 254, (1 << 254) - 1, p - 3} == set(edge) and len(pairs) == len(edge) ** 2 + 300
+    assert pairs[:len(edge) ** 2] == [(x, y) for x in edge for y in edge] and all(x < p and y < p for x, y in pairs)
     for a, b in pairs:
         r = _run(ins, a, b, p)
         assert r % p == a * b * rinv % p
         assert r < 2 * p                                           # fe_mul_sched: one conditional subtraction is enough
     # lazy operands (fe_mul_lazy: no subtraction after the product): a, b in [0, 2p + d) give a result below 2p + d again (d ~ 2^130)
     d = 1 << 130
-    for _ in range(300):
-        a, b = rng.randrange(2 * p + d), rng.randrange(2 * p + d)
+    assert d == LAZY_D and len(lazy) == 300 and all(a < 2 * p + d and b < 2 * p + d for a, b in lazy)
+    for a, b in lazy:
         r = _run(ins, a, b, p)
         assert r % p == a * b * rinv % p and r < 2 * p + d
 
