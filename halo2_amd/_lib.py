@@ -50,6 +50,15 @@ class DebugCounters(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+POSEIDON_MAX_WIDTH = 12
+
+
+class PoseidonSpec(C.Structure):
+    """h2_poseidon_spec_t: the descriptor the caller of h2_poseidon_spec_*_device fills"""
+    _fields_ = [("field", C.c_int), ("width", C.c_uint), ("rate", C.c_uint), ("full_rounds", C.c_uint), ("partial_rounds", C.c_uint),
+                ("d_constants", C.c_void_p), ("stream", C.c_void_p)]
+
+
 # every symbol include/halo2_mi355x.h declares: name -> (argtypes, restype)
 SIGNATURES = {
     "h2_device_count": ([], C.c_int),
@@ -180,6 +189,9 @@ SIGNATURES = {
     "h2_poseidon_permute_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
     "h2_poseidon_hash_device": ([C.c_int, vp, C.c_size_t, C.c_size_t, vp, vp], C.c_int),
     "h2_poseidon_trace_device": ([C.c_int, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_poseidon_spec_permute_device": ([C.POINTER(PoseidonSpec), vp, C.c_size_t, vp], C.c_int),
+    "h2_poseidon_spec_hash_device": ([C.POINTER(PoseidonSpec), vp, C.c_size_t, C.c_size_t, vp], C.c_int),
+    "h2_poseidon_spec_trace_device": ([C.POINTER(PoseidonSpec), vp, C.c_size_t, vp], C.c_int),
     "h2_sinsemilla_hash_device": ([vp, C.c_size_t, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
     "h2_sinsemilla_merkle_layer_device": ([C.c_uint, vp, C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),
     "h2_sinsemilla_trace_device": ([vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, u64p, vp, vp, vp, vp], C.c_int),

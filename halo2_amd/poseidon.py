@@ -2,17 +2,23 @@
 circuit too -- the leaves and nodes of a Merkle tree, nullifiers, commitments to a witness -- and the witness of the Pow5 chip.
 
 Every argument is an array of (..., 4) uint64 Montgomery limbs: a CUDA int64 tensor is used in place and a CUDA tensor comes back;
-a numpy array is uploaded and a numpy array comes back.  `field` is FP or FQ.  The constants are `halo2_amd.poseidon_spec`'s."""
+a numpy array is uploaded and a numpy array comes back.  `field` is FP or FQ.  The constants are `halo2_amd.poseidon_spec`'s.
+
+Any other specification is a `Spec(field, width, rate, ...)` (halo2_amd/poseidon_spec.py, halo2_amd/csrc/poseidon_spec.hip) with the same
+four as methods and the same array conventions, `width` words a state; its table of constants is uploaded once per device and kept
+by the Spec."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
 from . import fields
-from ._lib import check, lib
+from ._lib import PoseidonSpec, check, lib
 from .arithmetic import _is_torch, _stream_ptr
-from .poseidon_spec import ROWS, WIDTH
+from .poseidon_spec import ROWS, WIDTH, Spec
 
-__all__ = ["permute", "hash", "trace", "merkle_root"]
+__all__ = ["permute", "hash", "trace", "merkle_root", "Spec"]
 
 
 def _device(a, tail, what):
@@ -76,4 +82,74 @@ def merkle_root(leaves, field: int):
         raise ValueError("poseidon.merkle_root: a power-of-two number of leaves")
     while t.shape[0] > 1:
         t = hash(t.view(t.shape[0] // 2, 2, 4), field)
+    return _back(t[0], host)
+
+
+# ---- any Spec (halo2_amd/csrc/poseidon_spec.hip): the bodies of Spec.permute / hash / trace / merkle_root --------------------------------------
+def spec_constants(spec: Spec, device):
+    """The table the spec kernels read, on `device`: (rounds * width + width * width, 4) Montgomery limbs, the round constants and then
+    the MDS matrix row-major.  Uploaded once per device and kept by the Spec; the library holds none of it."""
+    import torch
+    device = torch.device(device)
+    table = spec._device_constants.get(device)
+    if table is None:
+        flat = [c for row in spec.round_constants for c in row] + [c for row in spec.mds for c in row]
+        table = torch.from_numpy(fields.to_limbs(flat, spec.field, True).view(np.int64)).to(device)
+        spec._device_constants[device] = table
+    return table
+
+
+def spec_descriptor(spec: Spec, device, stream=None) -> PoseidonSpec:
+    """h2_poseidon_spec_t for `spec` with its table on `device`; the stream is torch's current one unless given."""
+    return PoseidonSpec(spec.field, spec.width, spec.rate, spec.full_rounds, spec.partial_rounds,
+                        spec_constants(spec, device).data_ptr(), _stream_ptr().value if stream is None else stream)
+
+
+def spec_permute(spec: Spec, states, out=None):
+    import torch
+    s, host = _device(states, (spec.width, 4), "Spec.permute")
+    res = torch.empty_like(s) if out is None else out
+    if out is not None and (not _is_torch(out) or out.shape != s.shape or out.dtype != torch.int64 or not out.is_contiguous()):
+        raise ValueError("Spec.permute: out is a contiguous int64 tensor of the states' shape")
+    d = spec_descriptor(spec, s.device)
+    check(lib().h2_poseidon_spec_permute_device(C.byref(d), _ptr(s), s.shape[0], _ptr(res)), "h2_poseidon_spec_permute_device")
+    return _back(res, host)
+
+
+def spec_hash(spec: Spec, messages):
+    import torch
+    m, host = _device(messages, (None, 4), "Spec.hash")
+    if m.shape[1] == 0:
+        raise ValueError("Spec.hash: a message has at least one element")
+    res = torch.empty((m.shape[0], 4), dtype=torch.int64, device=m.device)
+    d = spec_descriptor(spec, m.device)
+    check(lib().h2_poseidon_spec_hash_device(C.byref(d), _ptr(m), m.shape[0], m.shape[1], _ptr(res)), "h2_poseidon_spec_hash_device")
+    return _back(res, host)
+
+
+def spec_trace(spec: Spec, states):
+    import torch
+    if spec.partial_rounds % 2:
+        raise ValueError("Spec.trace: the Pow5 chip lays two partial rounds on a row; partial_rounds is even")
+    s, host = _device(states, (spec.width, 4), "Spec.trace")
+    res = torch.empty((spec.width + 1, spec.rows * s.shape[0], 4), dtype=torch.int64, device=s.device)
+    d = spec_descriptor(spec, s.device)
+    check(lib().h2_poseidon_spec_trace_device(C.byref(d), _ptr(s), s.shape[0], _ptr(res)), "h2_poseidon_spec_trace_device")
+    return _back(res, host)
+
+
+def spec_merkle_root(spec: Spec, leaves, arity=None):
+    """One `hash` launch per layer; every layer stays on the device."""
+    arity = spec.rate if arity is None else arity
+    t, host = _device(leaves, (4,), "Spec.merkle_root")
+    n = t.shape[0]
+    if arity < 2:
+        raise ValueError("Spec.merkle_root: an arity of at least 2")
+    size = 1
+    while size < n:
+        size *= arity
+    if n == 0 or size != n:
+        raise ValueError("Spec.merkle_root: a power of the arity as the number of leaves")
+    while t.shape[0] > 1:
+        t = spec_hash(spec, t.view(t.shape[0] // arity, arity, 4))
     return _back(t[0], host)

@@ -689,6 +689,41 @@ int h2_poseidon_hash_device(int field, const void *d_messages, size_t n, size_t 
  * rows are zero.  Every one of the 4 * 37 * count elements is written.  d_columns must not overlap d_states. */
 int h2_poseidon_trace_device(int field, const void *d_states, size_t count, void *d_columns, void *stream);
 
+/* ---- Poseidon for any specification (halo2_poseidon Spec<F, T, RATE>: width 2 .. 12, S-box x^5), batched ---- */
+/* The three entry points above with the width, the rate and the round counts taken at run time (csrc/poseidon_spec.hip); at
+ * (3, 2, 8, 56) with P128Pow5T3's constants they give the same bytes.  The caller fills the descriptor.  d_constants is the CALLER's
+ * device buffer of Montgomery elements (4 x u64 each): (full_rounds + partial_rounds) * width round constants, round after round,
+ * then the width * width entries of the MDS matrix, row-major.  The library keeps no device memory for these calls -- no cached
+ * table, no workspace -- and every launch goes on `stream`, which travels in the descriptor as an FFT plan carries its stream: the
+ * calls are asynchronous on it and ordered by it alone, and d_constants must be complete on it.
+ *
+ * H2_ERR_ARGS before anything touches the device: a null spec; an unknown field; a width outside 2 .. H2_POSEIDON_MAX_WIDTH; a rate
+ * outside 1 .. width - 1; full_rounds odd or below 2; full_rounds + partial_rounds above 1024; a null buffer (d_constants included)
+ * with a nonzero count; a count above 2^30.  A count of 0 launches nothing. */
+#define H2_POSEIDON_MAX_WIDTH 12
+typedef struct h2_poseidon_spec {
+    int field;                                   /* H2_FP or H2_FQ */
+    unsigned width, rate, full_rounds, partial_rounds;
+    const void *d_constants;
+    void *stream;
+} h2_poseidon_spec_t;
+/* h2_poseidon_spec_permute_device: d_states holds n states of `width` elements, d_out receives the n permuted states.  d_out may be
+ * d_states (in place); any other overlap is not allowed. */
+int h2_poseidon_spec_permute_device(const h2_poseidon_spec_t *spec, const void *d_states, size_t n, void *d_out);
+/* h2_poseidon_spec_hash_device: Hash<_, S, ConstantLength<len>, T, RATE> of n messages of `len` elements each (d_messages: n * len
+ * elements, message after message).  The state starts as zeros with len * 2^64 in word `rate`; `rate` elements are added to words
+ * 0 .. rate - 1 per permutation, the last block zero-padded; d_out[i] is word 0 after the last permutation of message i.  len = 0,
+ * len >= 2^32 and n * len > 2^40 are H2_ERR_ARGS.  d_out must not overlap d_messages. */
+int h2_poseidon_spec_hash_device(const h2_poseidon_spec_t *spec, const void *d_messages, size_t n, size_t len, void *d_out);
+/* h2_poseidon_spec_trace_device: the witness of Pow5Chip<F, WIDTH, RATE> for `count` permutations; an odd partial_rounds is
+ * H2_ERR_ARGS (the chip lays two partial rounds on a row).  With rows = full_rounds + partial_rounds / 2 + 1, d_columns is ONE buffer of
+ * width + 1 vectors of rows * count elements, one after the other: state0 .. state(width - 1), partial_sbox.  Rows rows * i ..
+ * rows * i + rows - 1 of the state vectors belong to permutation i: row 0 the input, rows 1 .. full_rounds / 2 the state after the
+ * first full rounds, one row after each pair of partial rounds, then the last full rounds, the output on row rows - 1.  The
+ * partial_sbox cell of a partial row holds (state0 + rc)^5 of the first round of that row's pair, before the MDS; its other rows
+ * are zero.  Every one of the (width + 1) * rows * count elements is written.  d_columns must not overlap d_states. */
+int h2_poseidon_spec_trace_device(const h2_poseidon_spec_t *spec, const void *d_states, size_t count, void *d_columns);
+
 /* ---- Sinsemilla over Pallas (Zcash protocol specification 5.4.1.9; K = 10, C = 253), batched ---- */
 /* One lane per message.  q_xy is the domain's Q in HOST memory; d_table the 1024 points S(j) = hash_to_curve("z.cash:SinsemillaS")
  * (j as 4 bytes LE) in device memory; both Montgomery affine (8 limbs a point).  Every addition is the specification's INCOMPLETE
