@@ -561,7 +561,12 @@ def _verify_guard(params: Params, vk: VerifyingKey, instances, proof: bytes, msm
     queries += [Q(rot(r), vk.fixed_commitments[c], e) for (c, r), e in zip(cs.fixed_queries, fixed_evals)]
     queries += [Q(x, c, e) for c, e in zip(vk.permutation_commitments, sigma_evals)]
     queries += [Q(x, h_commitment, expected_h_eval), Q(x, random_poly_commitment, random_eval)]   # vanishing/verifier.rs:119-139
-    return multiopen_verify_proof(params, t, queries, msm)                                # :347
+    guard = multiopen_verify_proof(params, t, queries, msm)                               # :347
+    # the reference reads from an `io::Read` and never asks whether it is exhausted (transcript.rs:89-116); `proof` here is the whole proof, and one
+    # with bytes after the opening argument's last scalar is not the byte string a prover writes: accepting it would make proofs malleable
+    if t.pos != len(t.proof):
+        raise VerificationError("bytes after the end of the proof")
+    return guard
 
 
 # ---- verification strategies (plonk/verifier.rs:21-63; tests/plonk_api.rs:513-545) ------------------------------------------------

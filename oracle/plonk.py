@@ -152,7 +152,10 @@ def _verify_many(curve, k, g, w, u, vk, instances, proof: bytes) -> bool:
     queries += [(rot(r), vk["fixed_commitments"][c], e) for (c, r), e in zip(cs.fixed_queries, fixed_evals)]
     queries += [(x, c, e) for c, e in zip(vk["permutation_commitments"], sigma_evals)]
     queries += [(x, h_commitment, expected_h_eval), (x, random_poly_commitment, random_eval)]
-    return om.verify_proof(curve, k, g, w, u, t, queries)
+    ok = om.verify_proof(curve, k, g, w, u, t, queries)
+    # the reference reads from an `io::Read` and never asks whether it is exhausted (transcript.rs:89-116); here `proof` is the whole proof, so
+    # bytes the verifier did not read make it another byte string than the one the prover wrote
+    return ok and t.pos == len(proof)
 
 
 class _T:
