@@ -59,6 +59,11 @@ class PoseidonSpec(C.Structure):
                 ("d_constants", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class MerklePaths(C.Structure):
+    """h2_merkle_paths_t: the descriptor the caller of h2_sinsemilla_merkle_paths_device and h2_sinsemilla_merkle_trace_device fills"""
+    _fields_ = [("depth", C.c_uint), ("q_xy", u64p), ("d_table", C.c_void_p), ("stream", C.c_void_p)]
+
+
 # every symbol include/halo2_mi355x.h declares: name -> (argtypes, restype)
 SIGNATURES = {
     "h2_device_count": ([], C.c_int),
@@ -206,6 +211,8 @@ SIGNATURES = {
     "h2_ecc_add_trace_device": ([vp, vp, C.c_size_t, vp, vp], C.c_int),
     "h2_range_check_trace_device": ([C.c_int, vp, C.c_size_t, C.c_uint, vp, vp, vp], C.c_int),
     "h2_short_range_check_trace_device": ([C.c_int, vp, C.c_size_t, C.c_uint, vp, vp, vp], C.c_int),
+    "h2_sinsemilla_merkle_paths_device": ([C.POINTER(MerklePaths), vp, vp, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_sinsemilla_merkle_trace_device": ([C.POINTER(MerklePaths), vp, vp, vp, C.c_size_t, C.c_uint, C.c_uint, vp], C.c_int),
 }
 
 

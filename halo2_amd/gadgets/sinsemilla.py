@@ -1,6 +1,6 @@
 """The Sinsemilla gadget of halo2_gadgets (src/sinsemilla.rs, sinsemilla/chip.rs, chip/hash_to_point.rs, chip/generator_table.rs,
 sinsemilla/merkle.rs, merkle/chip.rs) against `halo2_amd.circuit`: `SinsemillaChip`, `Message` / `MessagePiece`, `HashDomain`,
-`MerkleChip`, `MerklePath` and `CommitDomain`, over the Pallas base field, with Q public or -- on a chip configured with
+`MerkleChip`, `MerklePath`, `MerklePaths` and `CommitDomain`, over the Pallas base field, with Q public or -- on a chip configured with
 `allow_init_from_private_point` -- a witnessed point (`hash_to_point_with_private_init`).
 
 The mirror assigns cell by cell with host `Assigned` rationals -- the same regions, offsets, gate and lookup shapes and copy
@@ -339,6 +339,31 @@ class SinsemillaChip:
         return x_a, y_a, zs
 
     # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def witness_message_pieces_many(self, layouter, num_words, values=None, column=None) -> list:
+        """`witness_message_piece` of len(num_words) pieces back to back in one region of the witness_pieces column; piece i carries
+        num_words[i] words.  values: the pieces as integers (None each, or None for all, without a witness); column: the
+        (len(num_words), 4) Montgomery vector where the caller has it on the device (then `values` is not read).  Without a witness
+        (keygen) the same shape is laid out.  -> the MessagePieces; one built from `column` carries its cell and no value."""
+        import torch
+        num_words = [int(w) for w in num_words]
+        count = len(num_words)
+        if not layouter.cs.collect_advice or not count:
+            column, known = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (count, 4)), [None] * count
+        elif column is None:
+            if values is None or any(v is None for v in values) or len(values) != count:
+                raise Synthesis("witness_message_pieces_many: a witness is needed and there is none")
+            known = [Assigned.trivial(int(v) % self.config.modulus, self.config.modulus) for v in values]
+            column = fields.to_limbs([int(v) % self.config.modulus for v in values], FP)
+        else:
+            known = [None] * count
+            if not torch.is_tensor(column):
+                column = torch.from_numpy(np.ascontiguousarray(column, dtype=np.uint64).view(np.int64))
+            if tuple(column.shape) != (count, 4):
+                raise ValueError("witness_message_pieces_many: the column is (len(num_words), 4)")
+        index = layouter.assign_region("witness message pieces many",
+                                       lambda region: region.assign_advice_column(self.config.witness_pieces, 0, column).region_index)
+        return [MessagePiece(AssignedCell(known[i], Cell(index, i, self.config.witness_pieces)), w) for i, w in enumerate(num_words)]
+
     def hash_to_point_many(self, layouter, Q, num_words, pieces, values=None, trace=None) -> HashMany:      # noqa: N803
         """`count` hashes of one piece structure back to back in one region; cell for cell what `count` calls of `hash_to_point` (or of
         `hash_to_point_with_private_init`) lay out.  Q: an (x, y) pair, public and shared, or a list of `count` NonIdentityEccPoint,
@@ -668,6 +693,69 @@ class MerkleChip:
         return digest
 
 
+    # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def swap_many(self, layouter, a_cells, b_values, swaps, trace=None):
+        return self._cond_swap.swap_many(layouter, a_cells, b_values, swaps, trace=trace)
+
+    def witness_message_pieces_many(self, layouter, num_words, values=None, column=None):
+        return self._sinsemilla.witness_message_pieces_many(layouter, num_words, values=values, column=column)
+
+    def hash_to_point_many(self, layouter, Q, num_words, pieces, values=None, trace=None):      # noqa: N803
+        return self._sinsemilla.hash_to_point_many(layouter, Q, num_words, pieces, values=values, trace=trace)
+
+    def hash_layer_many(self, layouter, Q, layers, lefts, rights, trace=None, hash_trace=None, copy_digests_to=None) -> HashMany:      # noqa: N803
+        """`hash_layer` of count = len(layers) items in five bulk regions: the 3 * count pieces, the two 5-bit range checks of b_1 and
+        b_2 (`short_range_check_many` on the chip's lookup config), the hashes (`hash_to_point_many`), and "Check piece decomposition
+        many": 2 * count rows over the five advice columns, q_decompose on every even row; per item the gates and equality
+        constraints of the single call.  layers[t]: the constant l of item t; lefts[t], rights[t]: the Cells (or AssignedCells) of
+        the pair.  trace: the `sinsemilla.MerklePathTrace` of exactly these items, hash_trace: their (5, 53 * count, 4) columns from
+        `sinsemilla.trace(trace.canonical, MERKLE_PIECE_WORDS, Q)` (computed here when absent); both None without a witness
+        (keygen): the same shape, nothing launched.  copy_digests_to[t]: a cell the digest of item t is copied into, or None -- a
+        swap row laid out before this hash.  -> the HashMany; `.x_a(t)` is the digest cell of item t."""
+        config, sin = self.config, self.config.sinsemilla_config
+        m, count = sin.modulus, len(layers)
+        structure = list(primitive.MERKLE_PIECE_WORDS)
+        if len(lefts) != count or len(rights) != count or (copy_digests_to is not None and len(copy_digests_to) != count):
+            raise ValueError("hash_layer_many: one left, one right and one digest target per layer")
+        witness = bool(layouter.cs.collect_advice and count)
+        if witness and (trace is None or trace.count != count):
+            raise Synthesis("hash_layer_many: a witness is needed: the MerklePathTrace of these items")
+        if not witness:
+            trace = hash_trace = None
+        elif hash_trace is None:
+            hash_trace = primitive.trace(trace.canonical, structure, Q, table=sin.injected_table)
+        flat = self.witness_message_pieces_many(layouter, structure * count, column=None if trace is None else trace.pieces,
+                                                values=None)
+        pieces = [flat[3 * t:3 * t + 3] for t in range(count)]
+        unknown = [None] * count
+        b_1 = sin.lookup_config.short_range_check_many(layouter, unknown, 5, values=None if trace is None else trace.b_1)
+        b_2 = sin.lookup_config.short_range_check_many(layouter, unknown, 5, values=None if trace is None else trace.b_2)
+        hashes = self.hash_to_point_many(layouter, Q, structure, pieces, values=None if trace is None else trace.canonical, trace=hash_trace)
+        blank = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (2 * count, 4))
+        cell_of = lambda c: c.cell() if isinstance(c, AssignedCell) else c
+
+        def assign(region):
+            index = region.region_index
+            for j, column in enumerate(config.advices):
+                region.assign_advice_column(column, 0, blank if trace is None else trace.decompose[j])
+            region.enable_selector_rows(config.q_decompose, 2 * np.arange(count, dtype=np.int64))
+            for t in range(count):
+                row = 2 * t
+                region.constrain_constant(Cell(index, row + 1, config.advices[4]), int(layers[t]) % m)
+                for j in range(3):
+                    region.constrain_equal(Cell(index, row, config.advices[j]), pieces[t][j].cell_value.cell())
+                region.constrain_equal(Cell(index, row, config.advices[3]), cell_of(lefts[t]))
+                region.constrain_equal(Cell(index, row, config.advices[4]), cell_of(rights[t]))
+                region.constrain_equal(Cell(index, row + 1, config.advices[0]), hashes.z(t, 0, 1))
+                region.constrain_equal(Cell(index, row + 1, config.advices[1]), hashes.z(t, 1, 1))
+                region.constrain_equal(Cell(index, row + 1, config.advices[2]), b_1[t])
+                region.constrain_equal(Cell(index, row + 1, config.advices[3]), b_2[t])
+                if copy_digests_to is not None and copy_digests_to[t] is not None:
+                    region.constrain_equal(cell_of(copy_digests_to[t]), hashes.x_a(t))
+        layouter.assign_region("Check piece decomposition many", assign)
+        return hashes
+
+
 class MerklePath:
     """merkle.rs:46-171: the path from a leaf to the root, its layers shared out over the chips (ceil(len / chips) layers each)."""
 
@@ -688,3 +776,70 @@ class MerklePath:
             pair = chip.swap(layouter, (node, path[l]), pos[l])
             node = chip.hash_layer(layouter, self.Q, l, pair[0], pair[1])
         return node
+
+
+class MerklePaths:
+    """`MerklePath` for n paths of one length at once: the walk comes from the device in one launch (`sinsemilla.merkle_paths`), and
+    every chip lays its layers of ALL paths out in bulk regions -- "swap many", then `hash_layer_many`'s "witness message pieces many",
+    two "Range check 5 bits many", "hash_to_point many" and "Check piece decomposition many" -- filled from one
+    `sinsemilla.merkle_path_trace` and one `sinsemilla.trace`.  The layers are shared out over the chips as `MerklePath` does (ceil(len / chips) consecutive layers
+    each); per (path, layer) the gates, lookups and equality constraints are those of `MerklePath.calculate_root`.
+
+    leaf_positions: n integers below 2^32; paths: n lists of path_length siblings, from the leaf up; None each for keygen."""
+
+    def __init__(self, chips, Q, leaf_positions, paths, path_length: int | None = None):      # noqa: N803
+        assert chips
+        self.chips, self.Q = list(chips), (int(Q[0]), int(Q[1]))
+        self.leaf_positions = None if leaf_positions is None else [int(p) for p in leaf_positions]
+        self.paths = None if paths is None else [list(p) for p in paths]
+        if path_length is None:
+            if not self.paths:
+                raise ValueError("MerklePaths: a path length, or paths to read it from")
+            path_length = len(self.paths[0])
+        self.path_length = int(path_length)
+        if not 1 <= self.path_length <= primitive.MAX_MERKLE_DEPTH:
+            raise ValueError("MerklePaths: 1 .. 32 layers")
+        if self.paths is not None and any(len(p) != self.path_length for p in self.paths):
+            raise ValueError("MerklePaths: every path has path_length siblings")
+
+    def calculate_roots(self, layouter, leaves) -> list:
+        """leaves: n AssignedCells.  -> the n root cells (with their values where there is a witness)"""
+        import torch
+        n, depth = len(leaves), self.path_length
+        per_chip = (depth + len(self.chips) - 1) // len(self.chips)
+        sin = self.chips[0].config.sinsemilla_config
+        m = sin.modulus
+        witness = bool(layouter.cs.collect_advice and n)
+        nodes = pos = sib = None
+        if witness:
+            leaf_ints = [value_int(leaf.value(), m) for leaf in leaves]
+            if self.leaf_positions is None or self.paths is None or any(v is None for v in leaf_ints):
+                raise Synthesis("MerklePaths: a witness is needed and there is none")
+            if len(self.leaf_positions) != n or len(self.paths) != n:
+                raise ValueError("MerklePaths: one position and one path per leaf")
+            dev = fields.current_device()
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)
+            sib = up(fields.to_limbs([int(s) % m for p in self.paths for s in p], FP)).reshape(n, depth, 4)
+            pos = torch.from_numpy(np.array(self.leaf_positions, dtype=np.uint32).view(np.int32)).to(dev)
+            nodes = primitive.merkle_paths(up(fields.to_limbs(leaf_ints, FP)), pos, sib, domain=primitive.HashDomain(self.Q, table=sin.injected_table))
+        previous, previous_layers = None, 0
+        for at, chip in enumerate(self.chips):
+            lo, hi = at * per_chip, min(depth, (at + 1) * per_chip)
+            if lo >= hi:
+                break
+            layers = hi - lo
+            count = n * layers
+            trace = primitive.merkle_path_trace(nodes, pos, sib, lo, hi) if witness else None
+            # the `a` of a chip's first layer is copied from the leaf or from the digest the chip before laid out; the `a` of its other
+            # layers from a digest of its own hash region, which comes after the swaps: hash_layer_many ties those
+            firsts = [leaves[p] if previous is None else previous.x_a(p * previous_layers + previous_layers - 1) for p in range(n)]
+            a_cells = [firsts[t // layers] if t % layers == 0 else None for t in range(count)]
+            swaps = chip.swap_many(layouter, a_cells, [None] * count, [None] * count, trace=None if trace is None else trace.swap_rows)
+            targets = [swaps.a(t + 1) if (t + 1) % layers else None for t in range(count)]
+            previous = chip.hash_layer_many(layouter, self.Q, [lo + t % layers for t in range(count)], [swaps.a_swapped(t) for t in range(count)],
+                                            [swaps.b_swapped(t) for t in range(count)], trace=trace, copy_digests_to=targets)
+            previous_layers = layers
+        roots = [None] * n
+        if witness:
+            roots = [Assigned.trivial(v, m) for v in fields.from_limbs(nodes[:, depth].cpu().numpy().view(np.uint64), FP)]
+        return [AssignedCell(roots[p], previous.x_a(p * previous_layers + previous_layers - 1)) for p in range(n)]

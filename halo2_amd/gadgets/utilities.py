@@ -10,7 +10,7 @@ calls, so that a circuit built from them prints the reference's pinned key.
 
 What the reference does not have is the bulk path: `range_check_many` and `short_range_check_many` lay the checks of many values back
 to back in ONE region whose running_sum column comes from the device (`halo2_amd.range_check`), cell for cell the layout of as many
-single calls."""
+single calls; `CondSwapChip.swap_many` does the same for the conditional swaps."""
 from __future__ import annotations
 
 import numpy as np
@@ -400,6 +400,22 @@ class LookupRangeCheck4_5BConfig(LookupRangeCheckConfig):
 
 
 # ---- CondSwapChip (cond_swap.rs:61-296) ----------------------------------------------------------------------------------------------------
+class SwapMany:
+    """What `swap_many` returns: the cells of pair i by position."""
+
+    def __init__(self, region_index, config, count):
+        self.region_index, self.config, self.count = region_index, config, count
+
+    def a(self, i: int) -> Cell:
+        return Cell(self.region_index, i, self.config.a)
+
+    def a_swapped(self, i: int) -> Cell:
+        return Cell(self.region_index, i, self.config.a_swapped)
+
+    def b_swapped(self, i: int) -> Cell:
+        return Cell(self.region_index, i, self.config.b_swapped)
+
+
 class CondSwapConfig:
     def __init__(self, q_swap: Selector, a, b, a_swapped, b_swapped, swap):
         self.q_swap, self.a, self.b, self.a_swapped, self.b_swapped, self.swap = q_swap, a, b, a_swapped, b_swapped, swap
@@ -446,6 +462,49 @@ class CondSwapChip:
             b_swapped = region.assign_advice(c.b_swapped, 0, lambda: second)
             return a_swapped, b_swapped
         return layouter.assign_region("swap", assign)
+
+    # ---- the bulk path ---------------------------------------------------------------------------------------------------------------------
+    def swap_many(self, layouter, a_cells, b_values, swaps, trace=None) -> "SwapMany":
+        """`swap` of count = len(a_cells) pairs back to back in one region of count rows; per pair the gate and the one equality
+        constraint of the single call.  a_cells[i]: the AssignedCell or Cell that row i's `a` is a copy of, or None where the caller
+        ties that cell itself (to a cell of a region laid out later); b_values[i], swaps[i]: an integer and a bool, None each without
+        a witness.  trace: the (5, count, 4) Montgomery columns a, b, a_swapped, b_swapped, swap where the caller has them on the
+        device (else they are formed here from the cells' values).  Without a witness (keygen) the same shape is laid out."""
+        import torch
+
+        from .. import fields
+        c, count = self.config, len(a_cells)
+        if len(b_values) != count or len(swaps) != count:
+            raise ValueError("swap_many: one b and one swap per a")
+        blank = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (count, 4))
+        if not layouter.cs.collect_advice or not count:
+            columns = [blank] * 5
+        else:
+            if trace is None:
+                m, field = layouter.cs.m, layouter.cs.field
+                a_ints = [value_int(a.value(), m) if isinstance(a, AssignedCell) else None for a in a_cells]
+                if any(v is None for v in a_ints) or any(v is None for v in b_values) or any(s is None for s in swaps):
+                    raise Synthesis("swap_many: a witness is needed and there is none")
+                b_ints, bits = [int(v) % m for v in b_values], [int(bool(s)) for s in swaps]
+                rows = [a_ints, b_ints, [b if s else a for a, b, s in zip(a_ints, b_ints, bits)],
+                        [a if s else b for a, b, s in zip(a_ints, b_ints, bits)], bits]
+                trace = fields.to_limbs([v for row in rows for v in row], field).reshape(5, count, 4)
+            if not torch.is_tensor(trace):
+                trace = torch.from_numpy(np.ascontiguousarray(trace, dtype=np.uint64).view(np.int64))
+            if tuple(trace.shape) != (5, count, 4):
+                raise ValueError("swap_many: the trace is (5, count, 4)")
+            columns = [trace[j] for j in range(5)]
+
+        def assign(region):
+            index = region.region_index
+            for column, values in zip((c.a, c.b, c.a_swapped, c.b_swapped, c.swap), columns):
+                region.assign_advice_column(column, 0, values)
+            region.enable_selector_rows(c.q_swap, np.arange(count, dtype=np.int64))
+            for i, a in enumerate(a_cells):
+                if a is not None:
+                    region.constrain_equal(Cell(index, i, c.a), a.cell() if isinstance(a, AssignedCell) else a)
+            return index
+        return SwapMany(layouter.assign_region("swap many", assign), c, count)
 
     def mux(self, layouter, choice: AssignedCell, left: AssignedCell, right: AssignedCell) -> AssignedCell:
         """cond_swap.rs:137-190: `left` where choice is 0, else `right`; the three cells are copied in"""

@@ -22,7 +22,8 @@ from ._lib import FORM_MONTGOMERY, check, lib
 from .arithmetic import _is_torch, _p, _stream_ptr
 
 __all__ = ["K", "C_MAX", "HashDomain", "generator_table", "generator_table_ints", "q_point", "merkle_crh", "merkle_root", "trace",
-           "trace_from", "CommitDomain", "Bottom", "MERKLE_CRH_DOMAIN"]
+           "trace_from", "CommitDomain", "Bottom", "MERKLE_CRH_DOMAIN", "merkle_paths", "merkle_path_trace", "MerklePathTrace",
+           "MERKLE_PIECE_WORDS", "MAX_MERKLE_DEPTH"]
 
 K = 10
 C_MAX = 253                                     # the specification's C: words per message
@@ -239,6 +240,109 @@ def merkle_root(leaves, domain=None):
     for level in range(depth):
         t = _merkle_layer(dom, depth - 1 - level, t.view(t.shape[0] // 2, 2, 4))
     return t[0].cpu().numpy().view(np.uint64) if host else t[0]
+
+
+MAX_MERKLE_DEPTH = 32                           # the reference's leaf_pos is a u32
+MERKLE_PIECE_WORDS = (25, 2, 25)                # the pieces a, b, c of MerkleChip.hash_layer
+
+
+def _paths_descriptor(dom, depth):
+    """-> (h2_merkle_paths_t on the current stream, what it points to: kept alive by the caller until the call has returned).
+    dom = None: a descriptor without Q and table, which the trace does not read."""
+    from ._lib import MerklePaths
+    if dom is None:
+        return MerklePaths(depth, None, None, _stream_ptr().value), None
+    q, tab = _q_limbs(dom.Q), _device_table(dom.table)
+    return MerklePaths(depth, q.ctypes.data_as(C.POINTER(C.c_uint64)), tab.data_ptr(), _stream_ptr().value), (q, tab)
+
+
+def _path_inputs(what, first, positions, siblings, width):
+    """The three arrays of a path call, all of the kind of `first` -> (first (n, width, 4) or (n, 4), positions (n,) int32, siblings
+    (n, depth, 4)) as CUDA tensors, and whether they came from the host"""
+    import torch
+    host = not _is_torch(first)
+    if host == _is_torch(siblings) or host == _is_torch(positions):
+        raise ValueError(f"{what}: every argument of one kind, numpy arrays or CUDA tensors")
+    dev = fields.current_device()
+    up = (lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)) if host else (lambda a: a.contiguous())
+    f, s = up(first), up(siblings)
+    if host:
+        pos = np.asarray(positions)
+        if pos.ndim != 1 or (pos.size and (int(pos.min()) < 0 or int(pos.max()) >= 1 << 32)):
+            raise ValueError(f"{what}: positions are n numbers below 2^32")
+        pos = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.uint32).view(np.int32)).to(dev)
+    else:
+        pos = positions.contiguous()
+    n = pos.shape[0] if pos.ndim == 1 else -1
+    if s.ndim != 3 or s.shape[0] != n or s.shape[2] != 4 or not 1 <= s.shape[1] <= MAX_MERKLE_DEPTH or s.dtype != torch.int64 or not s.is_cuda:
+        raise ValueError(f"{what}: siblings is an (n, depth, 4) array of Montgomery limbs, depth 1 .. 32")
+    depth = s.shape[1]
+    if tuple(f.shape) != ((n, 4) if width is None else (n, depth + width, 4)) or f.dtype != torch.int64 or not f.is_cuda:
+        raise ValueError(f"{what}: " + ("leaves is (n, 4)" if width is None else "nodes is (n, depth + 1, 4)") + " Montgomery limbs")
+    if pos.dtype != torch.int32 or not pos.is_cuda:
+        raise ValueError(f"{what}: positions is an (n,) array of uint32 (a CUDA int32 tensor holds their bits)")
+    return f, pos, s, host
+
+
+def merkle_paths(leaves, positions, siblings, domain=None, with_status: bool = False):
+    """The walk of n Merkle paths (merkle.rs MerklePath::calculate_root) in ONE launch, one lane per path: leaves (n, 4), positions
+    (n,) and siblings (n, depth, 4) -> nodes (n, depth + 1, 4): node 0 is the leaf, node l + 1 = MerkleCRH(l, left, right) with
+    (left, right) = (sibling_l, node_l) where bit l of the position is set, (node_l, sibling_l) where it is not; node `depth` is the
+    root.  Host arrays (positions any integer type below 2^32) or CUDA tensors (positions an int32 tensor holding the u32 bits), with
+    the conventions of `merkle_crh`.  A layer without a value raises `Bottom`; with_status: returns (nodes, status (n, depth) uint8)
+    instead, the node of such a layer 0 and the walk continued from it."""
+    import torch
+    dom = _merkle_domain(domain)
+    lv, pos, sib, host = _path_inputs("sinsemilla.merkle_paths", leaves, positions, siblings, None)
+    n, depth = sib.shape[0], sib.shape[1]
+    nodes = torch.empty((n, depth + 1, 4), dtype=torch.int64, device=sib.device)
+    status = torch.empty((n, depth), dtype=torch.uint8, device=sib.device)
+    d, keep = _paths_descriptor(dom, depth)
+    check(lib().h2_sinsemilla_merkle_paths_device(C.byref(d), _ptr(lv), _ptr(sib), _ptr(pos), n, _ptr(nodes), _ptr(status)),
+          "h2_sinsemilla_merkle_paths_device")
+    del keep
+    if with_status:
+        return (nodes.cpu().numpy().view(np.uint64), status.cpu().numpy()) if host else (nodes, status)
+    _raise_bottom(status, "sinsemilla.merkle_paths")
+    return nodes.cpu().numpy().view(np.uint64) if host else nodes
+
+
+class MerklePathTrace:
+    """What `merkle_path_trace` returns: views of the one buffer h2_sinsemilla_merkle_trace_device writes (include/halo2_mi355x.h), each
+    a whole column vector.  With count = n * (layer_hi - layer_lo) items, item t = path * layers + (l - layer_lo):
+        swap_rows   (5, count, 4)      a (node), b (sibling), a_swapped (left), b_swapped (right), swap
+        pieces      (3 * count, 4)     a, b, c of item t at 3 t .., Montgomery: the witness_pieces column
+        decompose   (5, 2 * count, 4)  the rows of "Check piece decomposition", advice columns 0 .. 4
+        canonical   (count, 3, 4)      the pieces as CANONICAL limbs: `trace`'s pieces
+        b_1, b_2    (count, 4)         CANONICAL: the values of the two 5-bit range checks"""
+
+    def __init__(self, out, n, layers):
+        self.out, self.n, self.layers, c = out, n, layers, n * layers
+        self.count = c
+        self.swap_rows = out[:5 * c].reshape(5, c, 4)
+        self.pieces = out[5 * c:8 * c]
+        self.decompose = out[8 * c:18 * c].reshape(5, 2 * c, 4)
+        self.canonical = out[18 * c:21 * c].reshape(c, 3, 4)
+        self.b_1, self.b_2 = out[21 * c:22 * c], out[22 * c:23 * c]
+
+
+def merkle_path_trace(nodes, positions, siblings, layer_lo: int, layer_hi: int, domain=None) -> MerklePathTrace:
+    """The cells MerkleChip.hash_layer and CondSwapChip.swap assign outside the hash region, for the layers [layer_lo, layer_hi) of
+    every path: nodes (n, depth + 1, 4) as `merkle_paths` returns them, positions and siblings as it takes them.  The 53-row chains
+    come from `trace(result.canonical, MERKLE_PIECE_WORDS, Q)`.  `domain` is accepted for symmetry; no cell here depends on it."""
+    import torch
+    nd, pos, sib, host = _path_inputs("sinsemilla.merkle_path_trace", nodes, positions, siblings, 1)
+    n, depth = sib.shape[0], sib.shape[1]
+    layer_lo, layer_hi = int(layer_lo), int(layer_hi)
+    if not 0 <= layer_lo < layer_hi <= depth:
+        raise ValueError("sinsemilla.merkle_path_trace: 0 <= layer_lo < layer_hi <= depth")
+    layers = layer_hi - layer_lo
+    out = torch.empty((23 * n * layers, 4), dtype=torch.int64, device=sib.device)
+    d, keep = _paths_descriptor(None, depth)
+    check(lib().h2_sinsemilla_merkle_trace_device(C.byref(d), _ptr(nd), _ptr(sib), _ptr(pos), n, layer_lo, layer_hi, _ptr(out)),
+          "h2_sinsemilla_merkle_trace_device")
+    del keep
+    return MerklePathTrace(out.cpu().numpy().view(np.uint64) if host else out, n, layers)
 
 
 def _trace(name, entry, lead, pieces, num_words, q_of, table, with_status):

@@ -869,6 +869,50 @@ int h2_range_check_trace_device(int field, const void *d_values, size_t count, u
 int h2_short_range_check_trace_device(int field, const void *d_values, size_t count, unsigned num_bits, void *d_rows, void *d_status,
                                       void *stream);
 
+/* ---- Sinsemilla Merkle paths over Pallas (halo2_gadgets sinsemilla/merkle.rs, merkle/chip.rs, utilities/cond_swap.rs), batched ---- */
+/* n paths of `depth` layers each (csrc/merkle_path.hip).  The caller fills the descriptor: q_xy is the domain's Q in HOST memory and
+ * d_table the 1024 points S(j) in device memory, both Montgomery affine as the Sinsemilla entry points above take them.  The library
+ * keeps NO device memory for these calls -- no workspace, no cached table -- and every launch goes on `stream`, which travels in the
+ * descriptor as h2_poseidon_spec_t carries its stream: the calls are asynchronous on it and ordered by it alone, and every input must
+ * be complete on it.  No two buffers of a call may overlap.
+ *
+ * H2_ERR_ARGS before anything touches the device: a null descriptor; a depth outside 1 .. 32 (the reference's leaf_pos is a u32);
+ * n * depth above 2^30 (what h2_sinsemilla_trace_device accepts as its count); a null buffer with n > 0 (for the walk q_xy, always,
+ * and d_table; the trace reads neither); for the trace layer_lo >= layer_hi or layer_hi > depth.  n = 0 launches nothing. */
+typedef struct h2_merkle_paths {
+    unsigned depth;                              /* 1 .. 32 */
+    const uint64_t *q_xy;                        /* the domain's Q, HOST memory, Montgomery affine */
+    const void *d_table;                         /* the 1024 points S(j), device memory */
+    void *stream;
+} h2_merkle_paths_t;
+/* h2_sinsemilla_merkle_paths_device: the walk of MerklePath::calculate_root, one lane per path, ONE launch for all layers.  d_leaves:
+ * n Montgomery elements; d_siblings: n * depth Montgomery elements, path after path, the sibling of layer 0 (the leaf's) first;
+ * d_positions: n uint32_t.  d_nodes receives n * (depth + 1) Montgomery elements, path after path: node 0 is the leaf, node l + 1 =
+ * MerkleCRH(l, left, right) with (left, right) = (sibling_l, node_l) where bit l of the position is set and (node_l, sibling_l)
+ * where it is not, node `depth` the root.  d_status receives n * depth bytes: d_status[path * depth + l] = 1 where the chain of layer l
+ * has no value (incomplete addition met equal or opposite operands), 0 elsewhere; node l + 1 is then 0 and the walk goes on from 0,
+ * as the reference's test fold does.  Every element of d_nodes and every byte of d_status is written. */
+int h2_sinsemilla_merkle_paths_device(const h2_merkle_paths_t *paths, const void *d_leaves, const void *d_siblings, const void *d_positions,
+                                      size_t n, void *d_nodes, void *d_status);
+/* h2_sinsemilla_merkle_trace_device: what MerkleChip::hash_layer and CondSwapChip::swap assign outside the 53-row hash region, for the
+ * layers [layer_lo, layer_hi) of every path; d_nodes, d_siblings, d_positions as above (d_nodes as the walk wrote it).  With
+ * layers = layer_hi - layer_lo there are count = n * layers items, item t = path * layers + (l - layer_lo).  With left and right the
+ * CANONICAL values of the swapped pair, the three pieces are
+ *     a = l | left[0..240) << 10,   b = left[240..250) | b_1 << 10 | b_2 << 15,   c = right[5..255),
+ *     b_1 = left[250..255),  b_2 = right[0..5),  z1_a = a >> 10,  z1_b = b >> 10.
+ * d_out is ONE buffer of 23 * count elements, whole column vectors one after the other (offsets in elements):
+ *     [0, 5 count)          the swap rows, five vectors of count Montgomery elements: a (the node), b (the sibling), a_swapped
+ *                           (left), b_swapped (right), swap (0 or 1)
+ *     [5 count, 8 count)    the pieces, Montgomery: a, b, c of item t at 3 t, 3 t + 1, 3 t + 2
+ *     [8 count, 18 count)   the rows of "Check piece decomposition", five vectors of 2 count Montgomery elements, the chip's advice
+ *                           columns 0 .. 4: rows 2 t and 2 t + 1 of item t hold (a, z1_a), (b, z1_b), (c, b_1), (left, b_2), (right, l)
+ *     [18 count, 21 count)  the pieces again as CANONICAL limbs: the (count, 3, 4) d_pieces of h2_sinsemilla_trace_device, whose
+ *                           piece structure is 25, 2, 25 words
+ *     [21 count, 23 count)  b_1, then b_2, count CANONICAL elements each: the values of the two 5-bit range checks
+ * Every element is written. */
+int h2_sinsemilla_merkle_trace_device(const h2_merkle_paths_t *paths, const void *d_nodes, const void *d_siblings, const void *d_positions,
+                                      size_t n, unsigned layer_lo, unsigned layer_hi, void *d_out);
+
 #ifdef __cplusplus
 }
 #endif
