@@ -64,6 +64,13 @@ class MerklePaths(C.Structure):
     _fields_ = [("depth", C.c_uint), ("q_xy", u64p), ("d_table", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class EccFixedSum(C.Structure):
+    """h2_ecc_fixed_sum_t: the descriptor the caller of h2_ecc_mul_fixed_short_trace_device and
+    h2_ecc_mul_fixed_base_field_trace_device fills"""
+    _fields_ = [("num_windows", C.c_uint), ("d_points", C.c_void_p), ("d_u", C.c_void_p), ("d_scratch", C.c_void_p),
+                ("scratch_elems", C.c_size_t), ("stream", C.c_void_p)]
+
+
 # every symbol include/halo2_mi355x.h declares: name -> (argtypes, restype)
 SIGNATURES = {
     "h2_device_count": ([], C.c_int),
@@ -213,6 +220,8 @@ SIGNATURES = {
     "h2_short_range_check_trace_device": ([C.c_int, vp, C.c_size_t, C.c_uint, vp, vp, vp], C.c_int),
     "h2_sinsemilla_merkle_paths_device": ([C.POINTER(MerklePaths), vp, vp, vp, C.c_size_t, vp, vp], C.c_int),
     "h2_sinsemilla_merkle_trace_device": ([C.POINTER(MerklePaths), vp, vp, vp, C.c_size_t, C.c_uint, C.c_uint, vp], C.c_int),
+    "h2_ecc_mul_fixed_short_trace_device": ([C.POINTER(EccFixedSum), vp, vp, C.c_size_t, vp, vp], C.c_int),
+    "h2_ecc_mul_fixed_base_field_trace_device": ([C.POINTER(EccFixedSum), vp, C.c_size_t, vp, vp], C.c_int),
 }
 
 

@@ -132,21 +132,31 @@ inline int ceil_log2(size_t n) {                                                
 // H2_OK or what failed; a launch error it left behind is picked up here.  per_lane = 0: nothing to invert, pass B alone runs.
 // The callers name pass A's kernel first (!emit ? k<false> : k<true>): a unit's kernels are laid out in the order of their first
 // use, and the other order moved ecc_mul_trace's timing (profiles/gadget_kernels_shared.txt).
+//
+// The first form runs over memory the CALLER holds (ecc_fixed_sum.hip, whose unit keeps none): `scratch` has room for `capacity`
+// elements and capacity / per_lane lanes go through per chunk; a capacity below per_lane is H2_ERR_ARGS.  The second grows a DevBuf
+// to the widest chunk within `budget` and forwards.
+template <typename Pass> int two_pass_trace(uint32_t *scratch, size_t capacity, size_t count, size_t per_lane, hipStream_t st, Pass pass) {
+    const size_t per_chunk = per_lane ? capacity / per_lane : count;
+    if (count && !per_chunk) return H2_ERR_ARGS;
+    int rc;
+    for (size_t first = 0; first < count; first += per_chunk) {
+        const size_t chunk = count - first < per_chunk ? count - first : per_chunk;
+        if (per_lane) {
+            if ((rc = pass(false, first, chunk, scratch)) != H2_OK) return rc;
+            H2_HIP(hipGetLastError());
+            if ((rc = h2_batch_invert_device(H2_FP, scratch, chunk * per_lane, H2_FORM_MONTGOMERY, st)) != H2_OK) return rc;
+        }
+        if ((rc = pass(true, first, chunk, scratch)) != H2_OK) return rc;
+        H2_HIP(hipGetLastError());
+    }
+    return H2_OK;
+}
 template <typename Pass> int two_pass_trace(DevBuf &scratch, size_t count, size_t per_lane, size_t budget, hipStream_t st, Pass pass) {
     const size_t per_chunk = per_lane ? budget / per_lane : count;
     int rc = scratch.reserve((count < per_chunk ? count : per_chunk) * per_lane * 32);
     if (rc != H2_OK) return rc;
-    for (size_t first = 0; first < count; first += per_chunk) {
-        const size_t chunk = count - first < per_chunk ? count - first : per_chunk;
-        if (per_lane) {
-            if ((rc = pass(false, first, chunk, scratch.as<uint32_t>())) != H2_OK) return rc;
-            H2_HIP(hipGetLastError());
-            if ((rc = h2_batch_invert_device(H2_FP, scratch.ptr, chunk * per_lane, H2_FORM_MONTGOMERY, st)) != H2_OK) return rc;
-        }
-        if ((rc = pass(true, first, chunk, scratch.as<uint32_t>())) != H2_OK) return rc;
-        H2_HIP(hipGetLastError());
-    }
-    return H2_OK;
+    return two_pass_trace(scratch.as<uint32_t>(), budget, count, per_lane, st, pass);
 }
 
 // Optional kernel timing with HIP events on the launching stream (h2_profile_enable): bench.py uses it to

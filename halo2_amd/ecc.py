@@ -7,6 +7,10 @@ Points are arrays of uint64 Montgomery limbs, (..., 8), the identity (0, 0); sca
 2^255; the alphas of `mul_trace` are Montgomery elements of Fp, as cells are.  A CUDA int64 tensor is used in place and a CUDA tensor
 comes back; a numpy array is uploaded and a numpy array comes back.
 
+`mul_fixed_short_trace` and `mul_fixed_base_field_trace` (halo2_amd/csrc/ecc_fixed_sum.hip) witness the two fixed-base forms whose
+scalar is a running sum (mul_fixed/short.rs, mul_fixed/base_field_elem.rs); their inputs are CANONICAL elements of Fp and the
+inverses' scratch is a tensor of the call's own.
+
 `add` and `add_trace` are the group's complete addition in bulk (halo2_amd/csrc/sinsemilla_commit.hip, ecc/chip/add.rs): n sums
 P_i + Q_i, and the nine cells the chip witnesses for each."""
 from __future__ import annotations
@@ -19,12 +23,14 @@ from .arithmetic import _is_torch, _stream_ptr, scale_add
 
 __all__ = ["ROWS", "AUX", "mul", "mul_trace", "OffCurve", "Vanishing",
            "NUM_WINDOWS", "NUM_WINDOWS_SHORT", "FIXED_AUX", "FixedBase", "mul_fixed", "mul_fixed_short", "mul_fixed_trace",
-           "add", "add_trace"]
+           "add", "add_trace", "SHORT_AUX", "BASE_FIELD_AUX", "SUM_SCRATCH_LANES", "mul_fixed_short_trace", "mul_fixed_base_field_trace"]
 
 ROWS = 137                                      # rows of the region "variable-base scalar mul" (mul.rs:164-293)
 AUX = 16                                        # s, the 14 running sums of its range check, eta (mul/overflow.rs:101-208)
 NUM_WINDOWS, NUM_WINDOWS_SHORT = 85, 22         # 3-bit windows of a full-width and of a 64-bit scalar (constants.rs:18-23)
 FIXED_AUX = 11                                  # the complete addition's nine cells and the product (add.rs:213-295)
+SHORT_AUX, BASE_FIELD_AUX = 12, 15              # FIXED_AUX and the signed y; FIXED_AUX and alpha_0', alpha_1, alpha_2, alpha_0' canonical
+SUM_SCRATCH_LANES = 1 << 16                     # multiplications per chunk of a running-sum trace: 174 MB of inverses at 85 windows
 
 
 class OffCurve(ValueError):
@@ -191,6 +197,68 @@ def mul_fixed_trace(fixed_base: FixedBase, scalars):
     aux = torch.empty((count, FIXED_AUX, 4), dtype=torch.int64, device=k.device)
     check(lib().h2_ecc_mul_fixed_trace_device(fixed_base.points.data_ptr(), fixed_base.us.data_ptr(), nw, _ptr(k), count, _ptr(columns),
                                               _ptr(aux), _stream_ptr()), "h2_ecc_mul_fixed_trace_device")
+    if host:
+        return columns.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
+    return columns, aux
+
+
+def _sum_scratch(nw: int, count: int, device):
+    """the inverses' scratch of a running-sum trace: nw - 2 elements per lane, for every lane up to SUM_SCRATCH_LANES of them, beyond
+    which the call goes through in chunks"""
+    import torch
+    lanes = max(1, min(count, SUM_SCRATCH_LANES))
+    return torch.empty((lanes * (nw - 2), 4), dtype=torch.int64, device=device)
+
+
+def _sum_descriptor(fixed_base: FixedBase, nw: int, scratch, what: str):
+    from ._lib import EccFixedSum
+    if fixed_base.num_windows != nw:
+        raise ValueError(f"{what}: the tables of a base at {nw} windows")
+    return EccFixedSum(nw, fixed_base.points.data_ptr(), fixed_base.us.data_ptr(), scratch.data_ptr(), scratch.shape[0], _stream_ptr())
+
+
+def mul_fixed_short_trace(fixed_base: FixedBase, magnitudes, signs):
+    """What the chip's `mul_fixed_short` witnesses for `count` pairs (mul_fixed/short.rs): magnitudes, signs (count, 4) CANONICAL
+    elements of Fp, a valid magnitude below 2^64 and a valid sign 1 or p - 1 -> (columns, aux): columns (6, 23 * count, 4), the advice
+    columns x_p, y_p, x_qr, y_qr, window, u with multiplication i in rows 23 i .., `window` holding the running sum z_0 .. z_22; aux
+    (count, SHORT_AUX, 4), the closing complete addition, the magnitude's product and the signed y (see include/halo2_mi355x.h).  An
+    invalid pair gets the cells the reference assigns for it, which its gates then reject.  The inverses' scratch is allocated here,
+    per call, and is at most SUM_SCRATCH_LANES multiplications wide."""
+    import ctypes as C
+
+    import torch
+    m, host = _device(magnitudes, 4, "ecc.mul_fixed_short_trace magnitudes")
+    s, host_s = _device(signs, 4, "ecc.mul_fixed_short_trace signs")
+    if m.shape[0] != s.shape[0] or host != host_s:
+        raise ValueError("ecc.mul_fixed_short_trace: as many signs as magnitudes, both of one kind")
+    count, nw = m.shape[0], NUM_WINDOWS_SHORT
+    scratch = _sum_scratch(nw, count, m.device)
+    d = _sum_descriptor(fixed_base, nw, scratch, "ecc.mul_fixed_short_trace")
+    columns = torch.empty((6, (nw + 1) * count, 4), dtype=torch.int64, device=m.device)
+    aux = torch.empty((count, SHORT_AUX, 4), dtype=torch.int64, device=m.device)
+    check(lib().h2_ecc_mul_fixed_short_trace_device(C.byref(d), _ptr(m), _ptr(s), count, _ptr(columns), _ptr(aux)),
+          "h2_ecc_mul_fixed_short_trace_device")
+    if host:
+        return columns.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
+    return columns, aux
+
+
+def mul_fixed_base_field_trace(fixed_base: FixedBase, alphas):
+    """What the chip's `mul_fixed_base_field_elem` witnesses for `count` elements (mul_fixed/base_field_elem.rs): alphas (count, 4)
+    CANONICAL elements of Fp -> (columns, aux): columns (6, 86 * count, 4) as `mul_fixed_short_trace`'s with the running sum
+    z_0 .. z_85; aux (count, BASE_FIELD_AUX, 4): the closing complete addition and the product, alpha_0', alpha_1, alpha_2, and
+    alpha_0' again as canonical limbs, the `values=` of `range_check_many` (see include/halo2_mi355x.h)."""
+    import ctypes as C
+
+    import torch
+    a, host = _device(alphas, 4, "ecc.mul_fixed_base_field_trace alphas")
+    count, nw = a.shape[0], NUM_WINDOWS
+    scratch = _sum_scratch(nw, count, a.device)
+    d = _sum_descriptor(fixed_base, nw, scratch, "ecc.mul_fixed_base_field_trace")
+    columns = torch.empty((6, (nw + 1) * count, 4), dtype=torch.int64, device=a.device)
+    aux = torch.empty((count, BASE_FIELD_AUX, 4), dtype=torch.int64, device=a.device)
+    check(lib().h2_ecc_mul_fixed_base_field_trace_device(C.byref(d), _ptr(a), count, _ptr(columns), _ptr(aux)),
+          "h2_ecc_mul_fixed_base_field_trace_device")
     if host:
         return columns.cpu().numpy().view(np.uint64), aux.cpu().numpy().view(np.uint64)
     return columns, aux

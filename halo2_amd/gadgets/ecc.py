@@ -21,6 +21,10 @@ multiplication the same gates, cells and equality constraints as `mul`, grouped 
 tables as integers, from the device (`FixedBaseTables.of(halo2_amd.ecc.FixedBase(...))`) or from anywhere else.
 `EccChip.mul_fixed_many` is the bulk path of `mul_fixed`: one region of 85 rows per multiplication whose six advice columns come from
 `halo2_amd.ecc.mul_fixed_trace` and whose fixed columns are the base's tables tiled, then one region with the complete additions.
+`EccChip.mul_fixed_short_many` and `EccChip.mul_fixed_base_field_elem_many` are the bulk paths of the two forms whose scalar is a
+running sum (23 and 86 rows per multiplication from `halo2_amd.ecc.mul_fixed_short_trace` / `mul_fixed_base_field_trace`, then the
+additions, and for the base-field form the range check of alpha_0' and the canonicity gate's rows), and `EccChip.add_many` is the bulk
+path of `add`; every bulk path closes on the one layout of `EccChip.additions_many`.
 
 The mirror of the reference's test circuit (`MyEccCircuit`, tests/ecc_fixed_cases.py) reproduces the reference's pinned `vk_ecc_chip`
 bit for bit and its stored proof verifies.  `CommitDomain`, which multiplies its R through `FixedPoint` and adds through `add`, is in
@@ -31,6 +35,7 @@ import numpy as np
 
 from .. import ecc as primitive
 from .. import fields
+from .. import range_check as range_primitive
 from ..circuit import AssignedCell, Cell, ConstraintSystem, Expression, Rotation, Synthesis
 from .sinsemilla import DoubleAndAdd, NonIdentityEccPoint
 from .utilities import K, LookupRangeCheckConfig, RunningSumConfig, bool_check, decompose_word, range_check, ternary, value_int
@@ -941,6 +946,65 @@ class MulFixedMany:
         return Cell(self.region_index, NUM_WINDOWS * i + w, self.config.mul_fixed.window)
 
 
+class MulFixedSumMany:
+    """What `mul_fixed_short_many` and `mul_fixed_base_field_elem_many` return: the cells of multiplication i by position.  outputs:
+    (count, 2, 4) Montgomery x and y of the results (None without a witness); for the short form the y is the signed one."""
+
+    def __init__(self, config: EccConfig, count: int, num_windows: int, short: bool):
+        self.config, self.count, self.num_windows, self.short = config, count, num_windows, short
+        self.region_index, self.add_region_index, self.canonicity_region_index, self.outputs = None, None, None, None
+        self.alpha_0_prime = None                                             # base field: per multiplication the range check's cells
+
+    def result_x(self, i: int) -> Cell:
+        return Cell(self.add_region_index, 2 * i + 1, self.config.add.x_qr)
+
+    def result_y(self, i: int) -> Cell:
+        """the short form's result is the signed y, in y_p beside the sum (short.rs:186-190)"""
+        return Cell(self.add_region_index, 2 * i + 1, self.config.add.y_p if self.short else self.config.add.y_qr)
+
+    def point(self, i: int) -> tuple:
+        return self.result_x(i), self.result_y(i)
+
+    def z(self, i: int, w: int) -> Cell:
+        """the running sum's z_w, w = 0 .. num_windows"""
+        return Cell(self.region_index, (self.num_windows + 1) * i + w, self.config.mul_fixed.window)
+
+
+class AddMany:
+    """What `add_many` returns: sum i is in row 2 i + 1 of one region.  outputs: (count, 2, 4) Montgomery (None without a witness)."""
+
+    def __init__(self, config: EccConfig, count: int):
+        self.config, self.count, self.region_index, self.outputs = config, count, None, None
+
+    def result_x(self, i: int) -> Cell:
+        return Cell(self.region_index, 2 * i + 1, self.config.add.x_qr)
+
+    def result_y(self, i: int) -> Cell:
+        return Cell(self.region_index, 2 * i + 1, self.config.add.y_qr)
+
+    def point(self, i: int) -> tuple:
+        return self.result_x(i), self.result_y(i)
+
+
+def _tensor(t):
+    import torch
+    return t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64))
+
+
+def _blank(rows: int):
+    return np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (rows, 4))
+
+
+def _cell_of(c) -> Cell:
+    return c.cell() if isinstance(c, AssignedCell) else c
+
+
+def _operand_cells(point) -> tuple:
+    """the two cells of an operand of a bulk addition: an EccPoint or NonIdentityEccPoint, or a pair of cells"""
+    x, y = (point.x(), point.y()) if hasattr(point, "x") else point
+    return _cell_of(x), _cell_of(y)
+
+
 class EccChip:
     def __init__(self, config: EccConfig):
         self.config = config
@@ -1094,23 +1158,236 @@ class EccChip:
             return index
         result.region_index = layouter.assign_region("Full-width fixed-base mul (incomplete addition) many", assign)
 
+        # the last window's point and the accumulator
+        result.add_region_index = self.additions_many(
+            layouter, "Full-width fixed-base mul (last window, complete addition) many", count, aux,
+            lambda i: [Cell(result.region_index, nw * i + nw - 1, column) for column in (add.x_p, add.y_p, add.x_qr, add.y_qr)])
+        if aux is not None and count:
+            result.outputs = aux[:, 9:11].contiguous()
+        return result
+
+    def additions_many(self, layouter, name: str, count: int, aux, operands, second=None, extra=None) -> int:
+        """`count` complete additions in ONE region of 2 * count rows, the layout every bulk path closes on: row 2 i holds the nine
+        cells of addition i (aux[:, 0:9]: x_p, y_p, x_qr, y_qr, lambda, alpha, beta, gamma, delta) with q_add on, row 2 i + 1 the sum
+        in x_qr, y_qr (aux[:, 9:11]) and zeros in the other seven -- but for a column of `second`, {column: (count, 4) Montgomery
+        values}, which holds those.  operands(i) -> the four cells that x_p, y_p, x_qr, y_qr of row 2 i are constrained equal to.
+        extra(region): what else the region holds.  aux None (keygen): zeros.  -> the region's index"""
+        import torch
+        add = self.config.add
+        second = second or {}
+
         def additions(region):
             index = region.region_index
             for j, column in enumerate((add.x_p, add.y_p, add.x_qr, add.y_qr, add.lambda_, add.alpha, add.beta, add.gamma, add.delta)):
                 if aux is None:
-                    values_ = blank(2 * count)
+                    values_ = _blank(2 * count)
                 else:
-                    second = aux[:, 9 + (j - 2)] if j in (2, 3) else torch.zeros_like(aux[:, j])
-                    values_ = torch.stack([aux[:, j], second], dim=1).reshape(2 * count, 4)
+                    below = second[column] if column in second else aux[:, 9 + (j - 2)] if j in (2, 3) else torch.zeros_like(aux[:, j])
+                    values_ = torch.stack([aux[:, j], below.to(aux.device)], dim=1).reshape(2 * count, 4)
                 region.assign_advice_column(column, 0, values_)
             region.enable_selector_rows(add.q_add, 2 * np.arange(count, dtype=np.int64))
             for i in range(count):
-                last = nw * i + nw - 1
-                for column in (add.x_p, add.y_p, add.x_qr, add.y_qr):         # the last window's point and the accumulator
-                    region.constrain_equal(Cell(index, 2 * i, column), Cell(result.region_index, last, column))
+                for column, source in zip((add.x_p, add.y_p, add.x_qr, add.y_qr), operands(i)):
+                    region.constrain_equal(Cell(index, 2 * i, column), source)
+            if extra is not None:
+                extra(region)
             return index
-        result.add_region_index = layouter.assign_region("Full-width fixed-base mul (last window, complete addition) many", additions)
-        if aux is not None and count:
+        return layouter.assign_region(name, additions)
+
+    def add_many(self, layouter, a_points, b_points, trace=None) -> AddMany:
+        """`count` complete additions a_i + b_i in one region of 2 * count rows filled from `ecc.add_trace`; both operands of every
+        row are copy-constrained to the given points, the gate and the cells are those of `add`.  A point is an EccPoint or a
+        NonIdentityEccPoint, or the pair of cells a bulk result names (`point(i)`).  trace: the (count, 11, 4) rows of `ecc.add_trace`
+        where the caller has them -- needed where the operands are bare cells, which carry no value; else the operands' values are read
+        from their cells.  Without a witness (keygen) the same shape is laid out and nothing is launched."""
+        c, m = self.config, self.config.add.modulus
+        count = len(a_points)
+        if len(b_points) != count:
+            raise ValueError("add_many: as many b as a")
+        aux = None
+        if layouter.cs.collect_advice and count:
+            if trace is None:
+                pts = [[_xy(p, m) if hasattr(p, "x") else None for p in side] for side in (a_points, b_points)]
+                if any(p is None for side in pts for p in side):
+                    raise Synthesis("add_many: a witness is needed and there is none")
+                on_device = [_tensor(fields.to_limbs([v for p in side for v in p], FP).reshape(count, 8)).to(fields.current_device())
+                             for side in pts]
+                trace = primitive.add_trace(on_device[0], on_device[1])
+            aux = _tensor(trace)
+            if tuple(aux.shape) != (count, primitive.FIXED_AUX, 4):
+                raise ValueError("add_many: the trace is (count, 11, 4)")
+        cells = [(_operand_cells(p) + _operand_cells(q)) for p, q in zip(a_points, b_points)]
+        result = AddMany(c, count)
+        result.region_index = self.additions_many(layouter, "complete point addition many", count, aux, lambda i: cells[i])
+        if aux is not None:
+            result.outputs = aux[:, 9:11].contiguous()
+        return result
+
+    def _running_sum_many(self, layouter, name: str, fixed_base: FixedBaseTables, sources, columns) -> int:
+        """The first region of a fixed-base multiplication by a running sum, `count` times in one: num_windows + 1 rows each, advice
+        columns 0 - 5 from `columns` (zeros without), the base's tables tiled with a zero last row, the running sum's q_range_check on
+        rows 0 .. nw-1 and q_add_incomplete on rows 1 .. nw-2 of each; z_0 copied from sources[i], z_nw constrained to 0, window 1's
+        addition starting from window 0's point.  -> the region's index"""
+        c = self.config
+        add, inc, fixed = c.add, c.add_incomplete, c.mul_fixed
+        a, count, nw = c.advices, len(sources), fixed_base.num_windows
+        rows = nw + 1
+        base_rows = rows * np.arange(count, dtype=np.int64)
+
+        def assign(region):
+            index = region.region_index
+            for j in range(6):
+                assert a[j] == (add.x_p, add.y_p, add.x_qr, add.y_qr, fixed.window, fixed.u)[j]
+                region.assign_advice_column(a[j], 0, _blank(rows * count) if columns is None else columns[j])
+            if count:
+                for k in range(H):
+                    coeffs = fields.to_limbs([row[k] for row in fixed_base.lagrange_coeffs] + [0], FP)
+                    region.assign_fixed_column(fixed.lagrange_coeffs[k], 0, np.tile(coeffs, (count, 1)))
+                region.assign_fixed_column(fixed.fixed_z, 0, np.tile(fields.to_limbs(list(fixed_base.z) + [0], FP), (count, 1)))
+            region.enable_selector_rows(fixed.running_sum_config.q_range_check,
+                                        (base_rows[:, None] + np.arange(nw, dtype=np.int64)[None, :]).reshape(-1))
+            region.enable_selector_rows(inc.q_add_incomplete, (base_rows[:, None] + np.arange(1, nw - 1, dtype=np.int64)[None, :]).reshape(-1))
+            for i in range(count):
+                region.constrain_equal(Cell(index, rows * i, fixed.window), sources[i].cell())
+                region.constrain_constant(Cell(index, rows * i + nw, fixed.window), 0)
+                region.constrain_equal(Cell(index, rows * i + 1, add.x_qr), Cell(index, rows * i, add.x_p))
+                region.constrain_equal(Cell(index, rows * i + 1, add.y_qr), Cell(index, rows * i, add.y_p))
+            return index
+        return layouter.assign_region(name, assign)
+
+    def _sum_trace(self, layouter, what: str, fixed_base: FixedBaseTables, cells, values, trace, launch, aux_width: int):
+        """(columns, aux) of a running-sum bulk path as device tensors, or (None, None) without a witness.  cells: per input the
+        AssignedCells the canonical limbs are read from where `values` has none; launch(FixedBase, *limbs) -> the trace"""
+        import torch
+        count, nw = len(cells[0]), fixed_base.num_windows
+        if not layouter.cs.collect_advice or not count:
+            return None, None
+        if trace is None:
+            if fixed_base.device is None:
+                raise ValueError(f"{what}: the tables have no device copy to multiply over")
+            values = list(values) if values is not None else [None] * len(cells)
+            for j, group in enumerate(cells):
+                if values[j] is None:
+                    ints = [value_int(cell.value(), self.config.add.modulus) for cell in group]
+                    if any(v is None for v in ints):
+                        raise Synthesis(f"{what}: a witness is needed and there is none")
+                    values[j] = fields.to_limbs(ints, FP, montgomery=False)
+            trace = launch(fixed_base.device, *[v if torch.is_tensor(v) else _tensor(v).to(fields.current_device()) for v in values])
+        columns, aux = (_tensor(t) for t in trace)
+        if tuple(columns.shape) != (6, (nw + 1) * count, 4) or tuple(aux.shape) != (count, aux_width, 4):
+            raise ValueError(f"{what}: the trace is ((6, {nw + 1} * count, 4), (count, {aux_width}, 4))")
+        return columns, aux
+
+    def mul_fixed_short_many(self, layouter, fixed_base: FixedBaseTables, magnitudes, signs, values=None, trace=None) -> MulFixedSumMany:
+        """`count` multiplications [sign_i magnitude_i]B over the base's 22-window tables: ONE region of 23 * count rows whose advice
+        columns 0 - 5 come from the device (`ecc.mul_fixed_short_trace`), the running sum of magnitude i in the `window` column of rows
+        23 i .., then one region of 2 * count rows: the complete addition of multiplication i in row 2 i, and in row 2 i + 1 the short
+        gate's cells -- the sign, z_21 and the signed y beside the sum.  Per multiplication the gates, cells and equality constraints
+        of `mul_fixed_short`.
+
+        magnitudes, signs: AssignedCells.  values: (magnitudes, signs), each (count, 4) CANONICAL limbs where the caller has them on
+        the device already (else they are read from the cells); trace: (columns, aux) where the caller has them.  The copy of sign i
+        in the gate's row is the one value no trace holds as a cell's: it is read from the sign's cell either way.  Without a witness
+        (keygen) the same shape is laid out and nothing is launched."""
+        import torch
+        c, m = self.config, self.config.add.modulus
+        if c.mul_fixed_short is None:
+            raise ValueError("mul_fixed_short_many: the chip was configured without fixed_bases")
+        count, nw = len(magnitudes), NUM_WINDOWS_SHORT
+        if len(signs) != count or fixed_base.num_windows != nw:
+            raise ValueError("mul_fixed_short_many: one sign per magnitude, over tables of 22 windows")
+        columns, aux = self._sum_trace(layouter, "mul_fixed_short_many", fixed_base, (magnitudes, signs), values, trace,
+                                       primitive.mul_fixed_short_trace, primitive.SHORT_AUX)
+        add, fixed = c.add, c.mul_fixed
+        result = MulFixedSumMany(c, count, nw, True)
+        result.region_index = self._running_sum_many(layouter, "Short fixed-base mul (incomplete addition) many", fixed_base, magnitudes,
+                                                     columns)
+        second = None
+        if aux is not None:
+            sign_ints = [value_int(s.value(), m) for s in signs]
+            if any(v is None for v in sign_ints):
+                raise Synthesis("mul_fixed_short_many: a witness is needed and there is none")
+            last = torch.from_numpy((nw + 1) * np.arange(count, dtype=np.int64) + nw - 1).to(columns.device)
+            second = {fixed.window: _tensor(fields.to_limbs(sign_ints, FP)), fixed.u: columns[4][last], add.y_p: aux[:, 11]}
+
+        def short_gate(region):
+            index = region.region_index
+            region.enable_selector_rows(c.mul_fixed_short.q_mul_fixed_short, 2 * np.arange(count, dtype=np.int64) + 1)
+            for i in range(count):
+                region.constrain_equal(Cell(index, 2 * i + 1, fixed.window), signs[i].cell())
+                region.constrain_equal(Cell(index, 2 * i + 1, fixed.u), result.z(i, nw - 1))      # the last window, in a free cell of u
+        result.add_region_index = self.additions_many(
+            layouter, "Short fixed-base mul (most significant word) many", count, aux,
+            lambda i: [Cell(result.region_index, (nw + 1) * i + nw - 1, column) for column in (add.x_p, add.y_p, add.x_qr, add.y_qr)],
+            second=second, extra=short_gate)
+        if aux is not None:
+            result.outputs = torch.stack([aux[:, 9], aux[:, 11]], dim=1).contiguous()
+        return result
+
+    def mul_fixed_base_field_elem_many(self, layouter, fixed_base: FixedBaseTables, alphas, values=None, trace=None) -> MulFixedSumMany:
+        """`count` multiplications [alpha_i]B for cells alpha_i of Fp read as integers, each with its canonicity check: ONE region of
+        86 * count rows whose advice columns 0 - 5 come from the device (`ecc.mul_fixed_base_field_trace`), one region with the `count`
+        complete additions, one `range_check_many` of the alpha_0' at 13 words, and one region of 3 * count rows with the gate
+        "Canonicity checks".  Per multiplication the gates, cells and equality constraints of `mul_fixed_base_field_elem`.
+
+        alphas: AssignedCells.  values: (count, 4) CANONICAL limbs where the caller has them on the device already (else they are read
+        from the cells); trace: (columns, aux) where the caller has them.  Without a witness (keygen) the same shape is laid out and
+        nothing is launched."""
+        import torch
+        c = self.config
+        config = c.mul_fixed_base_field
+        if config is None:
+            raise ValueError("mul_fixed_base_field_elem_many: the chip was configured without fixed_bases")
+        count, nw = len(alphas), NUM_WINDOWS
+        if fixed_base.num_windows != nw:
+            raise ValueError("mul_fixed_base_field_elem_many: tables of 85 windows")
+        columns, aux = self._sum_trace(layouter, "mul_fixed_base_field_elem_many", fixed_base, (alphas,), None if values is None else (values,),
+                                       trace, primitive.mul_fixed_base_field_trace, primitive.BASE_FIELD_AUX)
+        add, fixed = c.add, c.mul_fixed
+        result = MulFixedSumMany(c, count, nw, False)
+        result.region_index = self._running_sum_many(layouter, "Base-field elem fixed-base mul (incomplete addition) many", fixed_base, alphas,
+                                                     columns)
+        result.add_region_index = self.additions_many(
+            layouter, "Base-field elem fixed-base mul (complete addition) many", count, aux,
+            lambda i: [Cell(result.region_index, (nw + 1) * i + nw - 1, column) for column in (add.x_p, add.y_p, add.x_qr, add.y_qr)])
+        words = 13
+        prime_rows = None
+        if aux is not None:
+            canonical = aux[:, 14].contiguous()
+            prime_rows = range_primitive.decompose(canonical.to(fields.current_device()), words, field=FP)
+            sums = config.lookup_config.range_check_many(layouter, [None] * count, words, False, values=canonical, trace=prime_rows)
+            prime_rows = _tensor(prime_rows).reshape(count, words + 1, 4)
+        else:
+            sums = config.lookup_config.range_check_many(layouter, [None] * count, words, False)
+        result.alpha_0_prime = sums
+        canon = config.canon_advices
+
+        def canonicity(region):
+            index = region.region_index
+            if aux is None:
+                col0 = col1 = col2 = _blank(3 * count)
+            else:
+                dev_ = columns.device
+                at = torch.from_numpy((nw + 1) * np.arange(count, dtype=np.int64)).to(dev_)
+                z = columns[4]
+                zero = torch.zeros_like(z[at])
+                aux_d, prime_d = aux.to(dev_), prime_rows.to(dev_)
+                col0 = torch.stack([z[at], aux_d[:, 11], prime_d[:, words]], dim=1).reshape(3 * count, 4)
+                col1 = torch.stack([zero, aux_d[:, 12], z[at + 44]], dim=1).reshape(3 * count, 4)
+                col2 = torch.stack([z[at + 84], aux_d[:, 13], z[at + 43]], dim=1).reshape(3 * count, 4)
+            for column, values_ in zip(canon, (col0, col1, col2)):
+                region.assign_advice_column(column, 0, values_)
+            region.enable_selector_rows(config.q_mul_fixed_base_field, 3 * np.arange(count, dtype=np.int64) + 1)
+            for i in range(count):
+                region.constrain_equal(Cell(index, 3 * i, canon[0]), alphas[i].cell())
+                region.constrain_equal(Cell(index, 3 * i, canon[2]), result.z(i, 84))
+                region.constrain_equal(Cell(index, 3 * i + 1, canon[0]), sums[i][0])
+                region.constrain_equal(Cell(index, 3 * i + 2, canon[0]), sums[i][words])
+                region.constrain_equal(Cell(index, 3 * i + 2, canon[1]), result.z(i, 44))
+                region.constrain_equal(Cell(index, 3 * i + 2, canon[2]), result.z(i, 43))
+            return index
+        result.canonicity_region_index = layouter.assign_region("Canonicity checks many", canonicity)
+        if aux is not None:
             result.outputs = aux[:, 9:11].contiguous()
         return result
 

@@ -569,23 +569,9 @@ class CommitDomain:
             if tuple(aux.shape) != (count, ecc_primitive.FIXED_AUX, 4):
                 raise ValueError("commit_many: the additions' trace is (count, 11, 4)")
 
-        def additions(region):
-            index = region.region_index
-            for j, column in enumerate((add.x_p, add.y_p, add.x_qr, add.y_qr, add.lambda_, add.alpha, add.beta, add.gamma, add.delta)):
-                if aux is None:
-                    values_ = np.broadcast_to(np.zeros((1, 4), dtype=np.uint64), (2 * count, 4))
-                else:
-                    second = aux[:, 9 + (j - 2)] if j in (2, 3) else torch.zeros_like(aux[:, j])
-                    values_ = torch.stack([aux[:, j], second], dim=1).reshape(2 * count, 4)
-                region.assign_advice_column(column, 0, values_)
-            region.enable_selector_rows(add.q_add, 2 * np.arange(count, dtype=np.int64))
-            for i in range(count):                                            # p = M_i, q = [r_i]R
-                region.constrain_equal(Cell(index, 2 * i, add.x_p), hashes.x_a(i))
-                region.constrain_equal(Cell(index, 2 * i, add.y_p), hashes.y_a(i))
-                region.constrain_equal(Cell(index, 2 * i, add.x_qr), blinds.result_x(i))
-                region.constrain_equal(Cell(index, 2 * i, add.y_qr), blinds.result_y(i))
-            return index
-        result.add_region_index = layouter.assign_region("M + [r] R many", additions)
+        # p = M_i, q = [r_i]R, in the layout of EccChip.add_many
+        result.add_region_index = self.ecc_chip.additions_many(
+            layouter, "M + [r] R many", count, aux, lambda i: (hashes.x_a(i), hashes.y_a(i), blinds.result_x(i), blinds.result_y(i)))
         if aux is not None:
             result.outputs = aux[:, 9:11].contiguous()
         return result

@@ -913,6 +913,51 @@ int h2_sinsemilla_merkle_paths_device(const h2_merkle_paths_t *paths, const void
 int h2_sinsemilla_merkle_trace_device(const h2_merkle_paths_t *paths, const void *d_nodes, const void *d_siblings, const void *d_positions,
                                       size_t n, unsigned layer_lo, unsigned layer_hi, void *d_out);
 
+/* ---- Fixed-base multiplication by a running sum (halo2_gadgets ecc/chip/mul_fixed/short.rs, mul_fixed/base_field_elem.rs), batched ---- */
+/* `count` multiplications over one base's tables, one lane each (csrc/ecc_fixed_sum.hip): the witness of the two fixed-base forms whose
+ * scalar is decomposed by a running sum in the `window` column.  The caller fills the descriptor: d_points and d_u are the base's
+ * tables as h2_ecc_fixed_tables_device writes them at num_windows windows, d_scratch is device memory of the CALLER's, 32 bytes per
+ * element, for the inverses of the accumulators' denominators: num_windows - 2 elements per multiplication, and
+ * scratch_elems / (num_windows - 2) multiplications go through per chunk, so any capacity from num_windows - 2 up gives the same
+ * bytes.  The library keeps NO device memory for these calls and every launch goes on `stream`, which travels in the descriptor as
+ * h2_merkle_paths_t carries its stream: the calls are asynchronous on it and ordered by it alone, every input must be complete on it,
+ * and the scratch is free again once the call's work on the stream is done.  No two buffers of a call may overlap.
+ *
+ * The inputs are `count` CANONICAL elements of 4 limbs below p.  d_columns is ONE buffer of 6 vectors of (num_windows + 1) * count
+ * Montgomery elements, the chip's advice columns 0 .. 5 one after the other: x_p, y_p, x_qr, y_qr, window, u.  Rows
+ * (num_windows + 1) i .. belong to multiplication i.  Row w < num_windows holds points[w][k_w] in x_p, y_p and u[w][k_w] in u, and in
+ * x_qr, y_qr what h2_ecc_mul_fixed_trace_device writes there: zeros on row 0, the accumulator before the row's addition on the others,
+ * on row num_windows - 1 the one the complete addition starts from.  `window` holds the running sum: z_0 is the input and
+ * z_(w+1) = (z_w - k_w) / 8 in Fp on rows 0 .. num_windows.  Row num_windows holds z_(num_windows) in `window` and zeros in the other
+ * five.  Every element is written.
+ *
+ * h2_ecc_mul_fixed_short_trace_device (num_windows = 22): k_w is bits 3w .. 3w+2 of the LOW 64 bits of the magnitude, window 21 bit
+ * 63 alone (decompose_word(magnitude, 64, 3)).  A magnitude below 2^64 has z_w = magnitude >> 3w and z_22 = 0; from 2^64 up the
+ * recurrence is still the field's, z_22 != 0, and the circuit's constant constraint fails as the reference's negative tests expect.
+ * d_signs holds `count` canonical elements.  d_aux holds 12 Montgomery elements per multiplication: the 11 of
+ * h2_ecc_add_trace_device for (the last window's point) + (the accumulator), then the signed y: -y where the sign is p - 1, y for
+ * every other sign, valid or not (short.rs:178-184); the identity's 0 stays 0.
+ *
+ * h2_ecc_mul_fixed_base_field_trace_device (num_windows = 85): k_w is bits 3w .. 3w+2 of the 255-bit alpha and z_85 = 0.  d_aux holds
+ * 15 elements per multiplication: the same 11, then alpha_0' = alpha - (alpha >> 252) 2^252 + 2^130 - t_p (t_p = p - 2^254),
+ * alpha_1 = alpha[252..254) and alpha_2 = alpha[254], Montgomery, and alpha_0' once more as CANONICAL limbs, the d_values of
+ * h2_range_check_trace_device.
+ *
+ * H2_ERR_ARGS before anything touches the device: a null descriptor; a num_windows that is not the entry point's; count above 2^30;
+ * with count > 0 a null buffer or scratch_elems < num_windows - 2.  count = 0 launches nothing. */
+typedef struct h2_ecc_fixed_sum {
+    unsigned num_windows;                        /* 22 for the short form, 85 for the base-field form */
+    const void *d_points;                        /* num_windows * 8 points, as h2_ecc_fixed_tables_device writes them */
+    const void *d_u;                             /* num_windows * 8 roots, likewise */
+    void *d_scratch;                             /* the CALLER's device memory, 32 bytes per element */
+    size_t scratch_elems;                        /* >= num_windows - 2 */
+    void *stream;
+} h2_ecc_fixed_sum_t;
+int h2_ecc_mul_fixed_short_trace_device(const h2_ecc_fixed_sum_t *d, const void *d_magnitudes, const void *d_signs, size_t count,
+                                        void *d_columns, void *d_aux);
+int h2_ecc_mul_fixed_base_field_trace_device(const h2_ecc_fixed_sum_t *d, const void *d_alphas, size_t count, void *d_columns,
+                                             void *d_aux);
+
 #ifdef __cplusplus
 }
 #endif
